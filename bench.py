@@ -6,16 +6,23 @@ message recomputed once + value selection).  Inputs are resident in HBM before t
 region (the graph is uploaded at engine creation).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--workload NAME] [--dtype f64|f32]
-                    [--configs all|main] [--no-cpu-baseline]
+                    [--dump-outputs DIR] [--full [--configs all|main] [--no-cpu-baseline]]
+
+A plain run does only what the headline needs: set up, warm up, time the K steps, write the
+outputs (--dump-outputs), print the line.  Everything else it measures moves behind --full.
 
 N = 1 (default): the top-level `value` / `config` / `roofline` are the configuration the metric
 is quoted on -- random 3-colouring, 100k variables, average degree 4, reference arithmetic
-(f64), one `k_sweep` launch per cycle.  Timing (round 5): W warm-up steps, then warm-up BY TIME
-(>= 100 ms of launches: a 20-step run is 0.4 ms, less than the part's clocks need to settle), then R
-repetitions of EXACTLY K steps enqueued back to back -- R chosen so that the timed region is
->= 50 ms -- bracketed by a synchronize on both sides; `ms_per_step` is the MEDIAN repetition
-(each delimited by HIP events on the engine's stream) / K, `value` = 1000 / that; `repeats`,
-the fastest / slowest repetition and the wall clock over the whole region ride in `timing`.  The same JSON line carries, under "configs", every
+(f64), one `k_sweep` launch per cycle.  Timing: warm-up BY TIME (>= 100 ms of launches: a 20-step
+run is 0.4 ms, less than the part's clocks need to settle), a reset of the engine to cycle 0, W
+warm-up steps, then EXACTLY K timed steps bracketed by HIP events on the engine's stream;
+`ms_per_step` is that time / K, `value` = 1000 / that.  The state after the W + K cycles does not
+depend on the warm-up by time, so --dump-outputs DIR (selection, beliefs, messages, send counters,
+cost as DIR/<name>.npy) is the same from run to run for the same arguments and can be compared
+across builds.  With --full: the timing rounds 5-6 quoted rides in `timing` (R repetitions of
+EXACTLY K steps enqueued back to back -- R chosen so that the region is >= 50 ms -- their median,
+fastest and slowest repetition, the wall clock over the region), and the same JSON line carries,
+under "configs", every
 other BASELINE.json configuration that runs on one GPU (coloring_10k, ising_1024,
 coloring_1m_deg6, meeting_50k; f64 and f32) with its own cycle time, roofline fraction and the
 id of the `-m gpu` test that compares it bit for bit with the oracle at that size, and under
@@ -34,7 +41,7 @@ the timed region) and `north_star_speedup` = value / that are the numbers a scal
 drawn from -- the N = 1 line is the metric's 100k-variable instance, a DIFFERENT workload, so
 value(N) / value(1) across the two lines is not a speed-up.  (Rounds 3-4 led with the weak-scaling
 aggregate N x iterations/s of an N x 100k-variable instance: by construction it grows with N even when
-every shard is exchange-bound.)  Labelled extras, never part of `value`: that weak-scaling aggregate
+every shard is exchange-bound.)  Labelled extras (--full), never part of `value`: that weak-scaling aggregate
 (`extras[].scaling == "weak"`, with the unmultiplied rate beside it) and the metric's own 100k instance
 partitioned N ways (strong: it is too small to gain).  --workload NAME: strong scaling of that workload.  After every timed region rank 0 re-runs the instance
 on a single engine: the sharded selection and beliefs must be bit-identical, otherwise the run
@@ -344,10 +351,67 @@ def roofline_of(workload, dtype, bytes_cycle, kernel_s, launches=None, graph=Non
     return r
 
 
+def timed_steps(runner, steps, warmup, warm_s=0.1, warm_chunk=64):
+    """The N = 1 timed region (module docstring): warm-up by time (>= `warm_s` of launches, so that the
+    clocks settle and the captured graph exists), a reset of the engine to cycle 0 (so that what the
+    timed steps compute does not depend on how many cycles that took), `warmup` steps, then EXACTLY
+    `steps` cycles bracketed by HIP events on the engine's stream.  -> (ms per step, the `timing`
+    object of the line)."""
+    t0 = time.perf_counter()
+    n_warm = 0
+    while time.perf_counter() - t0 < warm_s:
+        runner.run(warm_chunk)
+        runner.sync()
+        n_warm += warm_chunk
+    runner.reset()
+    runner.run(warmup)
+    runner.sync()
+    t0 = time.perf_counter()
+    ms = runner.run_timed(steps)   # returns after the last step (event synchronize)
+    wall = time.perf_counter() - t0
+    if ms <= 0.0:                  # (the emulated engine of the CPU tests has no event clock)
+        ms = 1e3 * wall
+    return ms / steps, {
+        "timed_steps": steps, "warmup_steps": warmup, "warmup_by_time_steps": n_warm,
+        "timed_region_ms": ms, "wall_ms_timed_region": 1e3 * wall,
+        "clock": "HIP events on the engine's stream around the timed steps"}
+
+
+DUMP_LIMIT_BYTES = 64_000_000   # --dump-outputs: every file together, headers included
+
+
+def dump_outputs(out_dir, arrays, seed=0):
+    """--dump-outputs: `arrays` (name -> 1-D array) as out_dir/<name>.npy in float64 (float32 where the
+    source is narrower than 32 bits).  If the set is larger than DUMP_LIMIT_BYTES, every array above
+    an equal share of it is replaced by a fixed sample (positions drawn with `seed`, sorted: the same
+    from run to run for the same instance) and the positions go to out_dir/<name>_positions.npy.
+    -> {name: number of values written}."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    conv = {}
+    for name, a in arrays.items():
+        a = np.ravel(np.asarray(a))
+        conv[name] = a.astype(np.float32 if a.dtype.itemsize < 4 else np.float64)
+    slack = 256 * 2 * len(conv)   # .npy headers, one value file + one positions file per array
+    share = (DUMP_LIMIT_BYTES - slack) // (2 * len(conv))
+    total = sum(a.nbytes for a in conv.values())
+    written = {}
+    for name, a in conv.items():
+        if total + slack > DUMP_LIMIT_BYTES and a.nbytes > share:
+            k = share // 8   # values (<= 8 bytes each) and their float64 positions each fit one share
+            pos = np.sort(np.random.default_rng(seed).choice(a.shape[0], size=k, replace=False))
+            np.save(os.path.join(out_dir, f"{name}_positions.npy"), pos.astype(np.float64))
+            a = a[pos]
+        np.save(os.path.join(out_dir, f"{name}.npy"), a)
+        written[name] = int(a.shape[0])
+    return written
+
+
 def timed_repetitions(runner, steps, warmup, warm_s=0.1, region_s=0.05, min_reps=9):
-    """The N = 1 timed region (module docstring): `warmup` steps, warm-up by time, then R back-to-back
-    repetitions of EXACTLY `steps` cycles, synchronize on both sides.  -> (ms per step = median
-    repetition / steps, the `timing` object of the line)."""
+    """--full: the timing of rounds 5-6 beside the headline (which times exactly `steps` cycles, see
+    timed_steps): `warmup` steps, warm-up by time, then R back-to-back repetitions of EXACTLY `steps`
+    cycles, synchronize on both sides.  -> (ms per step = median repetition / steps, the repetition
+    figures of the line's `timing` object)."""
     import math
     import numpy as np
     runner.run(warmup)
@@ -613,7 +677,8 @@ def sharded_run(graph, params, rank, world, dev, backend, warmup, steps, torch, 
         if diff:
             print(f"[bench] sharded run differs from the single engine in {diff} places", file=sys.stderr)
         out = {"elapsed": elapsed, "collective": collective, "one_gpu_iterations_per_s": one_gpu, "ranks_seen": ranks_seen,
-               "check": {"cycles": int(n_cycles), "identical_to_single_engine": diff == 0, "differences": diff}}
+               "check": {"cycles": int(n_cycles), "identical_to_single_engine": diff == 0, "differences": diff},
+               "selection": idx_sh, "belief": bel_sh}   # what the sharded run selected (--dump-outputs)
         out["shard_rank0"] = shard_info
     dist.barrier()
     return out
@@ -660,12 +725,19 @@ def main():
     ap.add_argument("--dtype", default="f64", choices=["f64", "f32"])
     ap.add_argument("--layout-flags", type=int, default=0)
     ap.add_argument("--graph-chunk", type=int, default=-1)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beside the headline: N = 1: the repetition timing, cpu_baseline, "
+                         "the other configurations and algorithms; N > 1: the labelled extras.  Off: set up, warm up, "
+                         "time the steps, write the outputs, print the line")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the timed path computed in its last step as DIR/<name>.npy "
+                         "(float32 / float64, at most 64 MB in all: larger outputs as a fixed seeded sample)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: no cpu_baseline")
     ap.add_argument("--reference-budget", type=float, default=25.0,
                     help="seconds of orchestrator time per agent count for the reference's thread-agent "
                          "runtime in cpu_baseline (0: C port only)")
     ap.add_argument("--configs", default="all", choices=["all", "main"],
-                    help="N = 1: all = also time the other BASELINE.json configurations (default); "
+                    help="with --full: N = 1: all = also time the other BASELINE.json configurations (default); "
                          "N > 1: all = also run configs[3] and the 100k instance strong-scaled")
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"],
                     help="N > 1: torch.distributed backend; gloo only for the CPU test of this script "
@@ -674,6 +746,8 @@ def main():
     ap.add_argument("--vars-per-gpu", type=int, default=100_000,
                     help="testing only: scales the colouring workloads (the metric is defined at 100000)")
     args = ap.parse_args()
+    if args.steps < 1:
+        raise SystemExit("--steps must be >= 1")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # a plain `python3 bench.py --gpus N` (the way the driver runs --gpus 1): become the launcher -- one rank per
@@ -711,7 +785,20 @@ def main():
 
     if world == 1:
         runner = MaxSumEngine(graph, params, device=local_rank)
-        ms_step, timing = timed_repetitions(runner, args.steps, args.warmup)
+        ms_step, timing = timed_steps(runner, args.steps, args.warmup)
+        if args.dump_outputs:
+            idx, belief = runner.assignment()
+            v2f, f2v, count_v2f, count_f2v = runner.messages()
+            cost, violations = runner.eval_cost()
+            out["outputs"] = dump_outputs(args.dump_outputs, {
+                "selection": idx, "belief": belief, "v2f": v2f, "f2v": f2v,
+                "count_v2f": count_v2f, "count_f2v": count_f2v, "cost": [cost, violations]})
+        if args.full:
+            # the repetition timing rounds 5-6 quoted (median of R repetitions of `steps` cycles): a labelled extra
+            _, reps = timed_repetitions(runner, args.steps, args.warmup)
+            timing.update({k: reps[k] for k in ("repeats", "steps_per_repetition", "ms_per_step_median", "ms_per_step_min",
+                                                 "ms_per_step_max", "ms_per_step_mean", "wall_ms_per_step_over_the_region",
+                                                 "wall_iterations_per_s", "region_ms")})
         _, launches = runner.cycle_bytes()
         storage = runner.table_storage()
         order = runner.factor_order()
@@ -722,14 +809,17 @@ def main():
             if wl == workload and workload != "coloring_100k":
                 parity = test.format(dtype=args.dtype)
         rf = roofline_of(workload, args.dtype, bytes_cycle, ms_step * 1e-3, launches, graph, storage)
-        emit_row("headline_detail", {"workload": workload, "dtype": args.dtype, "timing": timing, "factor_order": order,
-                                     "factor_kernels": {k: v for k, v in kernels.items() if v}, "roofline": dict(rf)})
+        if args.full:
+            emit_row("headline_detail", {"workload": workload, "dtype": args.dtype, "timing": dict(timing),
+                                         "factor_order": order, "factor_kernels": {k: v for k, v in kernels.items() if v},
+                                         "roofline": dict(rf)})
         rf.pop("table_storage", None)
-        tkeep = ("repeats", "steps_per_repetition", "ms_per_step_median", "ms_per_step_min", "ms_per_step_max",
+        tkeep = ("timed_steps", "warmup_steps", "warmup_by_time_steps", "timed_region_ms", "wall_ms_timed_region",
+                 "repeats", "steps_per_repetition", "ms_per_step_median", "ms_per_step_min", "ms_per_step_max",
                  "wall_ms_per_step_over_the_region", "wall_iterations_per_s", "clock")
         out.update({
             "value": 1e3 / ms_step, "ms_per_step": ms_step, "scaling": "weak",
-            "timing": {k: timing[k] for k in tkeep},
+            "timing": {k: timing[k] for k in tkeep if k in timing},
             "config": {"workload": workload, "n_vars": graph.n_vars, "n_factors": graph.n_factors,
                        "n_edges": graph.n_edges, "domain": int(graph.dom_size.max()),
                        "edge_messages_per_s": 1e3 / ms_step * 2 * graph.n_edges,
@@ -738,9 +828,9 @@ def main():
                        "parity_checked": True, "parity_test": parity},
             "roofline": rf,
         })
-        if not args.no_cpu_baseline:
+        if args.full and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(graph, mode, args.dtype, reference_budget_s=args.reference_budget)
-        if args.configs == "all" and args.workload is None:
+        if args.full and args.configs == "all" and args.workload is None:
             del graph
             rows = extra_configs(skip={(workload, args.dtype)})
             # the headline instance fits the Infinity Cache: the HBM-resident figure of the same kernel rides
@@ -802,7 +892,9 @@ def main():
                          "algorithmic_bytes_per_launch": bytes_cycle // args.gpus,
                          "avg_launch_us": 1e6 * elapsed / args.steps, "per_gpu": True},
         })
-    if args.configs == "all" and args.workload is None:
+    if rank == 0 and args.dump_outputs:
+        out["outputs"] = dump_outputs(args.dump_outputs, {"selection": res["selection"], "belief": res["belief"]})
+    if args.full and args.configs == "all" and args.workload is None:
         # labelled extras, never part of `value`: (1) WEAK scaling of the metric's own family -- ONE instance of
         # N x 100k variables, 100k per GPU; its aggregate N x iterations/s (iterations/s per 100k variables of work)
         # is what rounds 3-4 led with -- (2) the metric's own 100k instance split N ways (strong: too small to gain)

@@ -48,7 +48,7 @@ def test_bench_two_ranks_gloo(collective, tmp_path):
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
            "--master-addr", "127.0.0.1", "--master-port", str(_free_port()),
            os.path.join(ROOT, "tests", "emu", "run_emulated.py"), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "6", "--warmup", "2",
-           "--backend", "gloo", "--vars-per-gpu", "300", "--rows-file", str(tmp_path / "rows.json")]
+           "--full", "--backend", "gloo", "--vars-per-gpu", "300", "--rows-file", str(tmp_path / "rows.json")]
     r = subprocess.run(cmd, env=env, cwd=ROOT, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
     out, rows = _final_and_rows(r.stdout, tmp_path / "rows.json")
@@ -92,7 +92,7 @@ def test_bench_single_gpu_line_carries_every_config(tmp_path):
     with roofline + traffic source + the parity test id."""
     from emu.build_emu import build
     code = (
-        f"import sys, runpy; sys.argv = ['bench.py', '--steps', '4', '--warmup', '1', '--vars-per-gpu', '400', '--reference-budget', '4', '--rows-file', {str(tmp_path / 'rows.json')!r}]\n"
+        f"import sys, runpy; sys.argv = ['bench.py', '--full', '--steps', '4', '--warmup', '1', '--vars-per-gpu', '400', '--reference-budget', '4', '--rows-file', {str(tmp_path / 'rows.json')!r}]\n"
         f"from pydcop_amd import engine; engine.register_test_engine({build()!r}, make_default=True)\n"
         "import pydcop_amd.generators as G\n"
         "_ising, _meet, _col = G.ising_grid, G.meeting_like, G.random_coloring\n"
@@ -122,11 +122,13 @@ def test_bench_single_gpu_line_carries_every_config(tmp_path):
     algos = [x for x in rows if x["row"] == "algorithm"]
     head = [x for x in rows if x["row"] == "headline_detail"]
     assert len(head) == 1 and head[0]["timing"]["warmup_by_time_steps"] > 0 and head[0]["factor_kernels"]
-    # the timed region: repetitions of exactly `steps` cycles, the median one is the line's ms_per_step
+    # the timed region: exactly `steps` cycles, their time / steps is the line's ms_per_step; --full adds the
+    # repetitions of exactly `steps` cycles (median, fastest, slowest)
     tm = out["timing"]
+    assert tm["timed_steps"] == out["steps"] == 4 and out["ms_per_step"] == tm["timed_region_ms"] / 4 > 0
     assert tm["steps_per_repetition"] == out["steps"] == 4 and tm["repeats"] >= 9
     assert tm["wall_iterations_per_s"] > 0   # the host-clock rate over the whole region, beside the event-clock median
-    assert tm["ms_per_step_min"] <= out["ms_per_step"] == tm["ms_per_step_median"] <= tm["ms_per_step_max"]
+    assert 0 < tm["ms_per_step_min"] <= tm["ms_per_step_median"] <= tm["ms_per_step_max"]
     assert abs(out["value"] - 1e3 / out["ms_per_step"]) < 1e-9 * out["value"]
     from oracle.stage_reference import locate
     cb = out["cpu_baseline"]
@@ -188,11 +190,15 @@ def test_bench_launches_its_own_ranks(tmp_path):
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "5", "--warmup", "2", "--backend", "gloo",
-           "--vars-per-gpu", "300", "--configs", "main", "--rows-file", str(tmp_path / "rows.json")]
+           "--vars-per-gpu", "300", "--configs", "main", "--rows-file", str(tmp_path / "rows.json"),
+           "--dump-outputs", str(tmp_path / "out")]
     r = subprocess.run(cmd, env=env, cwd=ROOT, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
     out, rows = _final_and_rows(r.stdout, tmp_path / "rows.json")
     assert out["n_gpus"] == 2 and out["steps"] == 5 and out["scaling"] == "strong" and rows == []
+    import numpy as np   # the sharded run's selection and beliefs after the timed steps, written by rank 0
+    assert out["outputs"] == {"selection": 3000, "belief": 3000}
+    assert np.load(tmp_path / "out" / "selection.npy").shape == (3000,)
     assert out["config"]["check"]["identical_to_single_engine"] and out["north_star_speedup"]["n_gpus"] == 2
     assert out["ranks_seen"] == 2
 
@@ -201,3 +207,74 @@ def test_bench_rejects_mismatched_world():
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "1"],
                        env=dict(os.environ, WORLD_SIZE="1"), cwd=ROOT, capture_output=True, text=True, timeout=120)
     assert r.returncode != 0 and "WORLD_SIZE" in (r.stdout + r.stderr)
+
+
+def _plain_run(tmp_path, tag, steps, warmup, extra=()):
+    from emu.build_emu import build
+    argv = ["bench.py", "--gpus", "1", "--steps", str(steps), "--warmup", str(warmup), "--vars-per-gpu", "400",
+            "--rows-file", str(tmp_path / f"rows_{tag}.json"), "--dump-outputs", str(tmp_path / tag), *extra]
+    code = (f"import sys, runpy; sys.argv = {argv!r}\n"
+            f"from pydcop_amd import engine; engine.register_test_engine({build()!r}, make_default=True)\n"
+            f"runpy.run_path({os.path.join(ROOT, 'bench.py')!r}, run_name='__main__')\n")
+    r = subprocess.run([sys.executable, "-c", code], env=dict(os.environ, OMP_NUM_THREADS="1"), cwd=ROOT,
+                       capture_output=True, text=True, timeout=900)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
+    return _final_and_rows(r.stdout, tmp_path / f"rows_{tag}.json")
+
+
+def test_bench_plain_run_is_lean_and_dumps_its_outputs(tmp_path, oracle_built):
+    """`bench.py --gpus 1 --steps N --warmup W` without --full: the headline only (no detail rows, no cpu_baseline,
+    no other configurations), exactly N timed steps, and --dump-outputs writes the state after W + N cycles --
+    the same in two runs, and what the oracle computes after W + N cycles."""
+    import numpy as np
+    from oracle.maxsum_oracle import OracleMaxSum
+    from pydcop_amd import generators as G
+    from pydcop_amd.graph import Params
+    out, rows = _plain_run(tmp_path, "a", steps=7, warmup=2)
+    out2, _ = _plain_run(tmp_path, "b", steps=7, warmup=2)
+    assert rows == []
+    for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "steps", "warmup", "timing"):
+        assert key in out, key
+    assert out["unit"] == "iterations/s" and out["higher_is_better"] is True and out["dtype"] == "f64"
+    assert "cpu_baseline" not in out and "rows" not in out
+    assert out["steps"] == out["timing"]["timed_steps"] == 7 and out["warmup"] == out["timing"]["warmup_steps"] == 2
+    assert out["ms_per_step"] > 0 and abs(out["value"] - 1e3 / out["ms_per_step"]) < 1e-9 * out["value"]
+    names = ("selection", "belief", "v2f", "f2v", "count_v2f", "count_f2v", "cost")
+    assert set(out["outputs"]) == set(names) and out["outputs"] == out2["outputs"]
+    got = {}
+    for name in names:
+        a, b = np.load(tmp_path / "a" / f"{name}.npy"), np.load(tmp_path / "b" / f"{name}.npy")
+        assert a.dtype in (np.float32, np.float64) and a.shape == (out["outputs"][name],)
+        assert np.array_equal(a, b), name
+        got[name] = a
+    assert sum(f.stat().st_size for f in (tmp_path / "a").iterdir()) <= 64_000_000
+    g = G.random_coloring(400, avg_degree=4, n_colors=3, seed=0, names=False)
+    ora = OracleMaxSum(g, Params(mode="min", dtype="f64"))
+    ora.run(2 + 7)
+    idx, belief = ora.assignment()
+    v2f, f2v, cv, cf = ora.messages()
+    cost, viol = ora.eval_cost()
+    ora.close()
+    assert np.array_equal(got["selection"], idx) and np.array_equal(got["belief"], belief)
+    assert np.array_equal(got["v2f"], v2f) and np.array_equal(got["f2v"], f2v)
+    assert np.array_equal(got["count_v2f"], cv) and np.array_equal(got["count_f2v"], cf)
+    assert got["cost"][1] == viol and abs(got["cost"][0] - cost) <= 1e-9 * max(1.0, abs(cost))
+
+
+def test_bench_dump_outputs_samples_what_exceeds_the_limit(tmp_path, monkeypatch):
+    """Outputs larger than the limit are written as a fixed, seeded sample with its positions."""
+    import numpy as np
+    import bench
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 40_000)
+    big, small = np.arange(10_000, dtype=np.float64), np.arange(10, dtype=np.int32)
+    for tag in ("a", "b"):
+        n = bench.dump_outputs(str(tmp_path / tag), {"big": big, "small": small, "flags": np.ones(5, np.uint8)})
+        assert n["small"] == 10 and n["flags"] == 5 and 0 < n["big"] < 10_000
+    assert sum(f.stat().st_size for f in (tmp_path / "a").iterdir()) <= 40_000
+    pos = np.load(tmp_path / "a" / "big_positions.npy")
+    vals = np.load(tmp_path / "a" / "big.npy")
+    assert vals.dtype == np.float64 and np.array_equal(vals, big[pos.astype(np.int64)]) and (np.diff(pos) > 0).all()
+    assert np.load(tmp_path / "a" / "flags.npy").dtype == np.float32
+    assert np.load(tmp_path / "a" / "small.npy").dtype == np.float64
+    for name in ("big", "big_positions", "small", "flags"):
+        assert np.array_equal(np.load(tmp_path / "a" / f"{name}.npy"), np.load(tmp_path / "b" / f"{name}.npy"))
