@@ -31,7 +31,6 @@
 #include "layout.h"
 
 namespace mxs {
-thread_local LaunchChain g_launch;
 
 static thread_local std::string g_err;
 
@@ -231,11 +230,6 @@ struct Engine : EngineBase {
     hipStream_t side = nullptr;
     hipEvent_t ev_fork = nullptr, ev_join = nullptr;
     bool overlap = false, capturing = false;
-    // The launches of a cycle after its first without the AQL barrier bit (kernels.h, LaunchChain): 0 off, 1 on (and no side
-    // stream: the wide variable launches ride in the chain), 2 on beside the side stream, 3 = 1 + the cut classes of a
-    // sharded cycle chained behind the halo wait.  $MAXSUM_ANYORDER; eager launches only.
-    int any_order = 0;
-    bool wide_last = false;
     bool streaming = false;  // non-temporal stores / index loads in the sweep (cycle larger than the Infinity Cache)
     hipEvent_t ev_p1 = nullptr;    // phase 1 of the current cycle enqueued (variables are done)
     hipEvent_t ev_halo = nullptr;  // ghost messages of the last exchange are in place
@@ -248,13 +242,7 @@ struct Engine : EngineBase {
     T* recv_buf = nullptr;  // halo_recv) or caller-owned memory (mxs_halo_bind)
     bool halo_ready = false;
     static constexpr int EVAL_BLOCKS = 1024;
-    static constexpr int FUSED_MAX_CUT_BLOCKS_DEFAULT = 1024;  // half of the 2048 resident workgroup slots
-    // ($MAXSUM_FUSED_MAX_CUT_BLOCKS: experiments with the fused sharded launch on shards with more cut workgroups -- together with
-    // $MAXSUM_COMM_CUS, which keeps CUs free for the exchange the parked workgroups wait for; profiles/r06_shard_fused_cus_v1.txt)
-    const int FUSED_MAX_CUT_BLOCKS = [] {
-        const char* e = getenv("MAXSUM_FUSED_MAX_CUT_BLOCKS");
-        return e ? std::max(1, atoi(e)) : FUSED_MAX_CUT_BLOCKS_DEFAULT;
-    }();
+    static constexpr int FUSED_MAX_CUT_BLOCKS = 1024;  // half of the 2048 resident workgroup slots
 
     ~Engine() override {
         for (int q = 0; q < MXS_MAX_PEERS; ++q) {
@@ -270,11 +258,6 @@ struct Engine : EngineBase {
         wide_profile_dump();
 #endif
         if (graph_exec) (void)hipGraphExecDestroy(graph_exec);
-        for (int q = 1; q < 3; ++q) {
-            if (ev_njoin[q]) (void)hipEventDestroy(ev_njoin[q]);
-            if (nstream[q]) (void)hipStreamDestroy(nstream[q]);
-        }
-        if (ev_nfork) (void)hipEventDestroy(ev_nfork);
         if (ev_fork) (void)hipEventDestroy(ev_fork);
         if (ev_join) (void)hipEventDestroy(ev_join);
         if (side) (void)hipStreamDestroy(side);
@@ -374,30 +357,30 @@ struct Engine : EngineBase {
         const dim3 grid(nb), block(BLOCK);
         if (p2p) {  // peer-store twin
             switch (L.dsel) {
-                case 2: MXS_LAUNCH((k_sweep_p2p<T, 2>), grid, block, 0, stream, a); break;
-                case 3: MXS_LAUNCH((k_sweep_p2p<T, 3>), grid, block, 0, stream, a); break;
-                case 4: MXS_LAUNCH((k_sweep_p2p<T, 4>), grid, block, 0, stream, a); break;
-                default: MXS_LAUNCH((k_sweep_p2p<T, 0>), grid, block, 0, stream, a); break;
+                case 2: hipLaunchKernelGGL((k_sweep_p2p<T, 2>), grid, block, 0, stream, a); break;
+                case 3: hipLaunchKernelGGL((k_sweep_p2p<T, 3>), grid, block, 0, stream, a); break;
+                case 4: hipLaunchKernelGGL((k_sweep_p2p<T, 4>), grid, block, 0, stream, a); break;
+                default: hipLaunchKernelGGL((k_sweep_p2p<T, 0>), grid, block, 0, stream, a); break;
             }
         } else if (timeline_on && has_hub) {  // profiling twin, hub class on board
-            if (L.dsel == 3) MXS_LAUNCH((k_sweep_timeline_hub<T, 3>), grid, block, 0, stream, a);
-            else MXS_LAUNCH((k_sweep_timeline_hub<T, 0>), grid, block, 0, stream, a);
+            if (L.dsel == 3) hipLaunchKernelGGL((k_sweep_timeline_hub<T, 3>), grid, block, 0, stream, a);
+            else hipLaunchKernelGGL((k_sweep_timeline_hub<T, 0>), grid, block, 0, stream, a);
         } else if (timeline_on) {  // profiling twin
             switch (L.dsel) {
-                case 2: MXS_LAUNCH((k_sweep_timeline<T, 2>), grid, block, 0, stream, a); break;
-                case 3: MXS_LAUNCH((k_sweep_timeline<T, 3>), grid, block, 0, stream, a); break;
-                case 4: MXS_LAUNCH((k_sweep_timeline<T, 4>), grid, block, 0, stream, a); break;
-                default: MXS_LAUNCH((k_sweep_timeline<T, 0>), grid, block, 0, stream, a); break;
+                case 2: hipLaunchKernelGGL((k_sweep_timeline<T, 2>), grid, block, 0, stream, a); break;
+                case 3: hipLaunchKernelGGL((k_sweep_timeline<T, 3>), grid, block, 0, stream, a); break;
+                case 4: hipLaunchKernelGGL((k_sweep_timeline<T, 4>), grid, block, 0, stream, a); break;
+                default: hipLaunchKernelGGL((k_sweep_timeline<T, 0>), grid, block, 0, stream, a); break;
             }
         } else if (has_hub) {  // the instantiations that carry the hub class (kernels.h variable_hub): D = 3 or any
-#define MXS_SWEEP_HUB(DS)                                                                                         \
+#define MXS_SWEEP_HUB(DS)                                                                                          \
     do {                                                                                                           \
         if (streaming) {                                                                                           \
-            if (a.sched) MXS_LAUNCH((k_sweep_hub<T, DS, NT_STREAMING, true>), grid, block, 0, stream, a);  \
-            else MXS_LAUNCH((k_sweep_hub<T, DS, NT_STREAMING, false>), grid, block, 0, stream, a);         \
+            if (a.sched) hipLaunchKernelGGL((k_sweep_hub<T, DS, NT_STREAMING, true>), grid, block, 0, stream, a);  \
+            else hipLaunchKernelGGL((k_sweep_hub<T, DS, NT_STREAMING, false>), grid, block, 0, stream, a);         \
         } else {                                                                                                   \
-            if (a.sched) MXS_LAUNCH((k_sweep_hub<T, DS, MXS_NT, true>), grid, block, 0, stream, a);        \
-            else MXS_LAUNCH((k_sweep_hub<T, DS, MXS_NT, false>), grid, block, 0, stream, a);               \
+            if (a.sched) hipLaunchKernelGGL((k_sweep_hub<T, DS, MXS_NT, true>), grid, block, 0, stream, a);        \
+            else hipLaunchKernelGGL((k_sweep_hub<T, DS, MXS_NT, false>), grid, block, 0, stream, a);               \
         }                                                                                                          \
     } while (0)
             if (L.dsel == 3) MXS_SWEEP_HUB(3);
@@ -407,23 +390,23 @@ struct Engine : EngineBase {
             // <.., policy, schedule>: NT_STREAMING when the cycle does not fit the Infinity Cache (kernels.h);
             // the lean instantiation when the launch has a block schedule
 #define MXS_SWEEP(DS)                                                                                          \
-    do {                                                                                                        \
-        if (streaming) {                                                                                        \
-            if (a.sched) MXS_LAUNCH((k_sweep<T, DS, NT_STREAMING, true>), grid, block, 0, stream, a);   \
-            else MXS_LAUNCH((k_sweep<T, DS, NT_STREAMING, false>), grid, block, 0, stream, a);          \
-        } else {                                                                                                \
-            if (a.sched) MXS_LAUNCH((k_sweep<T, DS, MXS_NT, true>), grid, block, 0, stream, a);         \
-            else MXS_LAUNCH((k_sweep<T, DS, MXS_NT, false>), grid, block, 0, stream, a);                \
-        }                                                                                                       \
+    do {                                                                                                       \
+        if (streaming) {                                                                                       \
+            if (a.sched) hipLaunchKernelGGL((k_sweep<T, DS, NT_STREAMING, true>), grid, block, 0, stream, a);  \
+            else hipLaunchKernelGGL((k_sweep<T, DS, NT_STREAMING, false>), grid, block, 0, stream, a);         \
+        } else {                                                                                               \
+            if (a.sched) hipLaunchKernelGGL((k_sweep<T, DS, MXS_NT, true>), grid, block, 0, stream, a);        \
+            else hipLaunchKernelGGL((k_sweep<T, DS, MXS_NT, false>), grid, block, 0, stream, a);               \
+        }                                                                                                      \
     } while (0)
             switch (L.dsel) {
                 case 2:  // its own kernel (SGPR budget, kernels.h)
                     if (streaming) {
-                        if (a.sched) MXS_LAUNCH((k_sweep_d2<T, NT_STREAMING, true>), grid, block, 0, stream, a);
-                        else MXS_LAUNCH((k_sweep_d2<T, NT_STREAMING, false>), grid, block, 0, stream, a);
+                        if (a.sched) hipLaunchKernelGGL((k_sweep_d2<T, NT_STREAMING, true>), grid, block, 0, stream, a);
+                        else hipLaunchKernelGGL((k_sweep_d2<T, NT_STREAMING, false>), grid, block, 0, stream, a);
                     } else {
-                        if (a.sched) MXS_LAUNCH((k_sweep_d2<T, MXS_NT, true>), grid, block, 0, stream, a);
-                        else MXS_LAUNCH((k_sweep_d2<T, MXS_NT, false>), grid, block, 0, stream, a);
+                        if (a.sched) hipLaunchKernelGGL((k_sweep_d2<T, MXS_NT, true>), grid, block, 0, stream, a);
+                        else hipLaunchKernelGGL((k_sweep_d2<T, MXS_NT, false>), grid, block, 0, stream, a);
                     }
                     break;
                 case 3: MXS_SWEEP(3); break;
@@ -467,8 +450,6 @@ struct Engine : EngineBase {
                 for (int i = 0; i < (d.arity & 255); ++i) sumd += d.dom[i];
                 cap = std::max(cap, sumd);
             }
-            // ($MAXSUM_NARY_CAP_MIN: A/B runs of the occupancy a group's LDS footprint leaves -- elements, at most 1024)
-            if (const char* e = std::getenv("MAXSUM_NARY_CAP_MIN")) cap = std::max(cap, std::min(1024, std::atoi(e)));
             nary_cap_cache[idx] = (cap + 1) & ~1;
         }
         return nary_cap_cache[idx];
@@ -497,62 +478,26 @@ struct Engine : EngineBase {
         return best;
     }
 
-    // $MAXSUM_NARY_STREAMS = 2 / 3: the launch groups of a cycle (they read the same old buffers and write disjoint records)
-    // spread over that many streams, the longest first -- short launches (a SECP cycle is seven of 5..20 us) then overlap their
-    // ramps and tails.  Eager launches of an unsharded cycle only; one fork and one join event per extra stream and cycle.
-    int nary_streams = 1;
-    hipStream_t nstream[3] = {nullptr, nullptr, nullptr};
-    hipEvent_t ev_nfork = nullptr, ev_njoin[3] = {nullptr, nullptr, nullptr};
-
     int launch_nary(const SweepArgs<T>& a, int cut) {
         const int host8 = cut == 0 ? pack8_host_group() : -1;
-        int n_groups = 0;
-        for (const NaryLaunch& nl : L.nary_launches) n_groups += nl.cut == cut;
-        const bool multi = nary_streams > 1 && cut == 0 && !capturing && !halo_ready && n_groups >= 2;
-        std::vector<int> lane_of(L.nary_launches.size(), 0);
-        if (multi) {
-            // longest processing time first onto the least loaded stream; cost = factors x table entries
-            std::vector<std::pair<double, int>> cost;
-            for (size_t i = 0; i < L.nary_launches.size(); ++i) {
-                const NaryLaunch& nl = L.nary_launches[i];
-                if (nl.cut != cut) continue;
-                const NaryDesc& d0 = L.ndesc[nl.first];
-                double e = 1;
-                for (int k = 0; k < (d0.arity & 255); ++k) e *= d0.dom[k];
-                cost.push_back({(e + 64) * nl.count, (int)i});
-            }
-            std::sort(cost.begin(), cost.end(), [](const auto& x, const auto& y) { return x.first > y.first; });
-            double load[3] = {0, 0, 0};
-            for (const auto& c : cost) {
-                int best = 0;
-                for (int q = 1; q < nary_streams; ++q)
-                    if (load[q] < load[best]) best = q;
-                lane_of[c.second] = best;
-                load[best] += c.first;
-            }
-            HIP_TRY(hipEventRecord(ev_nfork, stream));
-            for (int q = 1; q < nary_streams; ++q) HIP_TRY(hipStreamWaitEvent(nstream[q], ev_nfork, 0));
-        }
-        for (size_t gi = 0; gi < L.nary_launches.size(); ++gi) {
-            const NaryLaunch& nl = L.nary_launches[gi];
+        for (const NaryLaunch& nl : L.nary_launches) {
             if (nl.cut != cut) continue;
-            hipStream_t st = (multi && lane_of[gi] > 0) ? nstream[lane_of[gi]] : stream;
             const NaryDesc* d = ndesc.p + nl.first;
             if (is_bin2(nl.box)) {  // binary / unary tables: a lane grid per factor (bin_box.h)
                 const bool host = host8 >= 0 && &nl == &L.nary_launches[host8];
                 const int nb8 = host ? (L.classes[L.pack8_classes[0]].count + BLOCK - 1) / BLOCK : 0;
-                if (!launch_factor_bin2<T>(nl, a, d, st, host ? (const ClassInfo*)classes8.p : nullptr, nb8))
+                if (!launch_factor_bin2<T>(nl, a, d, stream, host ? (const ClassInfo*)classes8.p : nullptr, nb8))
                     return fail(MXS_E_STATE, "no lane-grid kernel for this launch group");
                 HIP_TRY(hipGetLastError());
                 continue;
             }
             if (is_small(nl.box)) {  // arity 3..5 over small domains: a lane group per factor (small_box.h)
-                if (!launch_factor_small<T>(nl, a, d, st)) return fail(MXS_E_STATE, "no small-domain kernel for this launch group");
+                if (!launch_factor_small<T>(nl, a, d, stream)) return fail(MXS_E_STATE, "no small-domain kernel for this launch group");
                 HIP_TRY(hipGetLastError());
                 continue;
             }
             if (nl.box) {  // one wave per factor, minima in registers (nary_box.h)
-                if (!launch_factor_box3<T>(nl, a, d, st)) return fail(MXS_E_STATE, "no box kernel for this launch group");
+                if (!launch_factor_box3<T>(nl, a, d, stream)) return fail(MXS_E_STATE, "no box kernel for this launch group");
                 HIP_TRY(hipGetLastError());
                 continue;
             }
@@ -561,35 +506,35 @@ struct Engine : EngineBase {
             // LDS of a block: three arrays as long as the group's largest scope (sum of its domain sizes), in 8-byte words
             const int cap = nary_group_cap(nl);
             const size_t lds = (size_t)3 * cap * 8;
-#define MXS_NARY_PACKED(AR, NJ, TT)                                                                        \
-    do {                                                                                                    \
-        if (AR == 3 && ls) {  /* kernels.h, nary_batch: LS */                                               \
-            if (a.tab_neg) MXS_LAUNCH((k_factor_nary_packed<T, AR, NJ, TT, true, AR == 3>), grid, block, lds, st, a, d, cap);  \
-            else MXS_LAUNCH((k_factor_nary_packed<T, AR, NJ, TT, false, AR == 3>), grid, block, lds, st, a, d, cap);           \
-        } else if (a.tab_neg) MXS_LAUNCH((k_factor_nary_packed<T, AR, NJ, TT, true>), grid, block, lds, st, a, d, cap);  \
-        else MXS_LAUNCH((k_factor_nary_packed<T, AR, NJ, TT, false>), grid, block, lds, st, a, d, cap);           \
+#define MXS_NARY_PACKED(AR, NJ, TT)                                                                                                        \
+    do {                                                                                                                                   \
+        if (AR == 3 && ls) {  /* kernels.h, nary_batch: LS */                                                                              \
+            if (a.tab_neg) hipLaunchKernelGGL((k_factor_nary_packed<T, AR, NJ, TT, true, AR == 3>), grid, block, lds, stream, a, d, cap);  \
+            else hipLaunchKernelGGL((k_factor_nary_packed<T, AR, NJ, TT, false, AR == 3>), grid, block, lds, stream, a, d, cap);           \
+        } else if (a.tab_neg) hipLaunchKernelGGL((k_factor_nary_packed<T, AR, NJ, TT, true>), grid, block, lds, stream, a, d, cap);        \
+        else hipLaunchKernelGGL((k_factor_nary_packed<T, AR, NJ, TT, false>), grid, block, lds, stream, a, d, cap);                        \
     } while (0)
-#define MXS_NARY_CASE(AR, NJ)                                                                              \
-    case (AR) * 16 + (NJ):                                                                                  \
-        if (nl.tab_type == TAB_I8) MXS_NARY_PACKED(AR, NJ, int8_t);                                         \
-        else if (nl.tab_type == TAB_I16) MXS_NARY_PACKED(AR, NJ, int16_t);                                  \
-        else if (nl.tab_type == TAB_F32) MXS_NARY_PACKED(AR, NJ, float);                                    \
-        else MXS_LAUNCH((k_factor_nary<T, AR, NJ>), grid, block, lds, st, a, d, cap);           \
+#define MXS_NARY_CASE(AR, NJ)                                                                      \
+    case (AR) * 16 + (NJ):                                                                         \
+        if (nl.tab_type == TAB_I8) MXS_NARY_PACKED(AR, NJ, int8_t);                                \
+        else if (nl.tab_type == TAB_I16) MXS_NARY_PACKED(AR, NJ, int16_t);                         \
+        else if (nl.tab_type == TAB_F32) MXS_NARY_PACKED(AR, NJ, float);                           \
+        else hipLaunchKernelGGL((k_factor_nary<T, AR, NJ>), grid, block, lds, stream, a, d, cap);  \
         break;
             if (nl.nj == NARY_NJ_MULTI) {  // full-width tables in passes of NARY_MAX_R entries per value of the first variable
-#define MXS_NARY_MULTI(AR)                                                                                                     \
-    case AR:                                                                                                                   \
-        if (nl.tab_type == TAB_I8) {                                                                                           \
-            if (a.tab_neg) MXS_LAUNCH((k_factor_nary<T, AR, NARY_MAX_NJ, true, int8_t, true>), grid, block, lds, st, a, d, cap);    \
-            else MXS_LAUNCH((k_factor_nary<T, AR, NARY_MAX_NJ, true, int8_t, false>), grid, block, lds, st, a, d, cap);             \
-        } else if (nl.tab_type == TAB_I16) {                                                                                   \
-            if (a.tab_neg) MXS_LAUNCH((k_factor_nary<T, AR, NARY_MAX_NJ, true, int16_t, true>), grid, block, lds, st, a, d, cap);   \
-            else MXS_LAUNCH((k_factor_nary<T, AR, NARY_MAX_NJ, true, int16_t, false>), grid, block, lds, st, a, d, cap);            \
-        } else if (nl.tab_type == TAB_FULL) {                                                                                  \
-            MXS_LAUNCH((k_factor_nary<T, AR, NARY_MAX_NJ, true>), grid, block, lds, st, a, d, cap);                             \
-        } else {                                                                                                               \
-            return fail(MXS_E_STATE, "no multi-pass n-ary kernel for this storage type");                                      \
-        }                                                                                                                      \
+#define MXS_NARY_MULTI(AR)                                                                                                                     \
+    case AR:                                                                                                                                   \
+        if (nl.tab_type == TAB_I8) {                                                                                                           \
+            if (a.tab_neg) hipLaunchKernelGGL((k_factor_nary<T, AR, NARY_MAX_NJ, true, int8_t, true>), grid, block, lds, stream, a, d, cap);   \
+            else hipLaunchKernelGGL((k_factor_nary<T, AR, NARY_MAX_NJ, true, int8_t, false>), grid, block, lds, stream, a, d, cap);            \
+        } else if (nl.tab_type == TAB_I16) {                                                                                                   \
+            if (a.tab_neg) hipLaunchKernelGGL((k_factor_nary<T, AR, NARY_MAX_NJ, true, int16_t, true>), grid, block, lds, stream, a, d, cap);  \
+            else hipLaunchKernelGGL((k_factor_nary<T, AR, NARY_MAX_NJ, true, int16_t, false>), grid, block, lds, stream, a, d, cap);           \
+        } else if (nl.tab_type == TAB_FULL) {                                                                                                  \
+            hipLaunchKernelGGL((k_factor_nary<T, AR, NARY_MAX_NJ, true>), grid, block, lds, stream, a, d, cap);                                \
+        } else {                                                                                                                               \
+            return fail(MXS_E_STATE, "no multi-pass n-ary kernel for this storage type");                                                      \
+        }                                                                                                                                      \
         break;
                 switch (nl.arity) {
                     MXS_NARY_MULTI(3) MXS_NARY_MULTI(4) MXS_NARY_MULTI(5) MXS_NARY_MULTI(6)
@@ -610,11 +555,6 @@ struct Engine : EngineBase {
 #undef MXS_NARY_PACKED
             HIP_TRY(hipGetLastError());
         }
-        if (multi)
-            for (int q = 1; q < nary_streams; ++q) {
-                HIP_TRY(hipEventRecord(ev_njoin[q], nstream[q]));
-                HIP_TRY(hipStreamWaitEvent(stream, ev_njoin[q], 0));
-            }
         return MXS_OK;
     }
 
@@ -623,12 +563,12 @@ struct Engine : EngineBase {
     int launch_wide(const SweepArgs<T>& a, hipStream_t ws) {
         if (!L.pack8_classes.empty() && pack8_host_group() < 0) {
             const ClassInfo& ci = L.classes[L.pack8_classes[0]];
-            MXS_LAUNCH((k_variable_pack8<T>), dim3((unsigned)((ci.count + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, ws, a,
+            hipLaunchKernelGGL((k_variable_pack8<T>), dim3((unsigned)((ci.count + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, ws, a,
                                (const ClassInfo*)classes8.p);
             HIP_TRY(hipGetLastError());
         }
         if (!L.wide_blocks.empty()) {
-            MXS_LAUNCH((k_variable_wide<T>), dim3((unsigned)L.wide_blocks.size()), dim3(WIDE_TPB), 0, ws, a,
+            hipLaunchKernelGGL((k_variable_wide<T>), dim3((unsigned)L.wide_blocks.size()), dim3(WIDE_TPB), 0, ws, a,
                                (const WideBlock*)wide_blocks.p);
             HIP_TRY(hipGetLastError());
         }
@@ -642,10 +582,6 @@ struct Engine : EngineBase {
     //            the only work that depends on the halo exchange of the previous cycle)
     // A single-GPU engine has no phase-2 work.
     int launch_phase(int from, bool start, int phase) {
-        struct ChainScope {  // the set of independent launches this call enqueues
-            explicit ChainScope(bool on, bool first_free) { g_launch.chain = on; g_launch.flags = (on && first_free) ? hipExtAnyOrderLaunch : 0; }
-            ~ChainScope() { g_launch = LaunchChain{}; }
-        } chain_scope(any_order > 0 && !capturing, any_order == 3 && phase == 2);
         const SweepArgs<T> a = make_args(from, start, phase);
         if (phase == 3) {  // everything of the cycle; the cut factor blocks wait inside the sweep
             int rc = launch_sweep(a, L.n_blocks_fused);
@@ -664,21 +600,12 @@ struct Engine : EngineBase {
                 if (!factors_only) { rc = launch_wide(a, stream); if (rc) return rc; }
                 return vars_only ? MXS_OK : launch_nary(a, 0);
             }
-            const bool fork = overlap && !capturing && n_wide_launches() > 0 && !L.nary_launches.empty() && any_order != 1 && any_order != 3;
+            const bool fork = overlap && !capturing && n_wide_launches() > 0 && !L.nary_launches.empty();
             hipStream_t ws = stream;
             if (fork) {  // the side stream starts where the compute stream is now
                 HIP_TRY(hipEventRecord(ev_fork, stream));
                 HIP_TRY(hipStreamWaitEvent(side, ev_fork, 0));
                 ws = side;
-            }
-            if (fork && wide_last) {  // ($MAXSUM_WIDE_LAST=1, A/B runs: the factor launches reach the machine first)
-                rc = launch_nary(a, 0);
-                if (rc) return rc;
-                rc = launch_wide(a, ws);
-                if (rc) return rc;
-                HIP_TRY(hipEventRecord(ev_join, side));
-                HIP_TRY(hipStreamWaitEvent(stream, ev_join, 0));
-                return MXS_OK;
             }
             rc = launch_wide(a, ws);
             if (rc) return rc;
@@ -827,38 +754,10 @@ struct Engine : EngineBase {
             return fail(MXS_E_NODEVICE, std::string("device is ") + prop.gcnArchName +
                                             ", this library is built for gfx950 (MI355X) only");
         HIP_TRY(hipSetDevice(dev));
-        // A shard can keep a few CUs free of sweep blocks ($MAXSUM_COMM_CUS, default 0): the
-        // kernels of the comm stream (RCCL's workgroups are large) otherwise find no CU with
-        // enough free resources while a sweep grid still has blocks to dispatch.
-        int reserve = 0;
-        if (g.var_owned) {
-            const char* env = getenv("MAXSUM_COMM_CUS");
-            if (env) reserve = std::max(0, std::min(atoi(env), prop.multiProcessorCount / 2));
-        }
-        if (reserve > 0) {
-            const int n_cu = prop.multiProcessorCount, keep = n_cu - reserve;
-            std::vector<uint32_t> mask((size_t)(n_cu + 31) / 32, 0u);
-            for (int c = 0; c < keep; ++c) mask[c / 32] |= 1u << (c % 32);
-            HIP_TRY(hipExtStreamCreateWithCUMask(&stream, (uint32_t)mask.size(), mask.data()));
-        } else {
-            HIP_TRY(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
-        }
+        HIP_TRY(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
         HIP_TRY(hipEventCreate(&ev0));
         HIP_TRY(hipEventCreate(&ev1));
-        {   // $MAXSUM_SIDE_PRIO = hi / lo: the side stream's priority against the compute stream's (A/B runs; default: the same)
-            int lo = 0, hi = 0;
-            HIP_TRY(hipDeviceGetStreamPriorityRange(&lo, &hi));
-            const char* e = getenv("MAXSUM_SIDE_PRIO");
-            if (e && (e[0] == 'h' || e[0] == 'l')) HIP_TRY(hipStreamCreateWithPriority(&side, hipStreamNonBlocking, e[0] == 'h' ? hi : lo));
-            else HIP_TRY(hipStreamCreateWithFlags(&side, hipStreamNonBlocking));
-            if (const char* w = getenv("MAXSUM_WIDE_LAST")) wide_last = w[0] == '1';
-        }
-        if (const char* e = getenv("MAXSUM_NARY_STREAMS")) nary_streams = std::max(1, std::min(3, atoi(e)));
-        for (int q = 1; q < nary_streams; ++q) {
-            HIP_TRY(hipStreamCreateWithFlags(&nstream[q], hipStreamNonBlocking));
-            HIP_TRY(hipEventCreateWithFlags(&ev_njoin[q], hipEventDisableTiming));
-        }
-        if (nary_streams > 1) HIP_TRY(hipEventCreateWithFlags(&ev_nfork, hipEventDisableTiming));
+        HIP_TRY(hipStreamCreateWithFlags(&side, hipStreamNonBlocking));
         HIP_TRY(hipEventCreateWithFlags(&ev_fork, hipEventDisableTiming));
         HIP_TRY(hipEventCreateWithFlags(&ev_join, hipEventDisableTiming));
         {   // Two streams pay when a cycle is long: measured (profiles/r05_variable_wave_ab_v1.txt, flags=1048576 rows =
@@ -869,7 +768,6 @@ struct Engine : EngineBase {
             const char* env = getenv("MAXSUM_NARY_OVERLAP");
             overlap = L.algorithmic_bytes >= ((int64_t)400 << 20);
             if (env && (env[0] == '0' || env[0] == '1')) overlap = env[0] == '1';
-            if (const char* e = getenv("MAXSUM_ANYORDER")) any_order = std::max(0, std::min(3, atoi(e)));
         }
         {   // the comm stream's kernels (pack, RCCL, unpack) go first whenever a slot frees up
             int lo = 0, hi = 0;

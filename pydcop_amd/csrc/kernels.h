@@ -26,7 +26,6 @@
 // -ffp-contract=off so no FMA contraction changes a rounding.
 #pragma once
 #include <hip/hip_runtime.h>
-#include <hip/hip_ext.h>
 
 #include <cmath>
 #include <cstdint>
@@ -37,28 +36,6 @@
 #include "layout.h"
 
 namespace mxs {
-
-// The launches of ONE cycle (or of one phase of a sharded cycle) read the buffers of cycle t-1 and write disjoint
-// records of cycle t: they do not depend on each other.  On one stream HIP still sets the AQL barrier bit of every
-// dispatch, so launch k + 1 starts only when launch k has drained -- a cycle of seven 5..20-us launches (SECP) pays
-// seven ramps and seven tails.  With `chain` set the engine's FIRST launch of a set keeps the barrier (it waits for
-// everything of the cycle before), every later one goes out with hipExtAnyOrderLaunch (no barrier bit): the command
-// processor hands out its workgroups as soon as the launch before has handed out its own, the way the workgroups of
-// one grid follow each other.  No events, no second stream.  The next set's first launch waits for all of them.
-struct LaunchChain {
-    unsigned flags = 0;   // of the next launch
-    bool chain = false;   // later launches of the set go out without the barrier bit
-};
-extern thread_local LaunchChain g_launch;
-#define MXS_LAUNCH(kernel, grid, block, lds, stream, ...)                                                        \
-    do {                                                                                                         \
-        if (mxs::g_launch.flags)                                                                                 \
-            hipExtLaunchKernelGGL(kernel, grid, block, (std::uint32_t)(lds), stream, nullptr, nullptr,           \
-                                  mxs::g_launch.flags, __VA_ARGS__);                                             \
-        else                                                                                                     \
-            hipLaunchKernelGGL(kernel, grid, block, lds, stream, __VA_ARGS__);                                   \
-        if (mxs::g_launch.chain) mxs::g_launch.flags = hipExtAnyOrderLaunch;                                     \
-    } while (0)
 
 constexpr int SAME_COUNT = 4;  // maxsum.py:106
 #ifndef MXS_ASM_MIN
@@ -1010,9 +987,6 @@ __device__ __forceinline__ void variable_hub(const SweepArgs<T>& a, const ClassI
                 // blocks ahead requested from LDS before the additions of the current one (three register sets by hand:
                 // the chain waits for nothing but itself); no branch but the loop's own.
                 auto fetch = [&](T (&x)[8], int kk) __attribute__((always_inline)) {
-#if defined(MXS_HUB_EXP) && MXS_HUB_EXP == 3   // timing experiment (results wrong): the chain without its LDS reads
-                    if (kk > 16) return;
-#endif
 #pragma unroll
                     for (int u = 0; u < 8; ++u) x[u] = row[8 + kk + u];
                 };
@@ -1376,14 +1350,9 @@ __device__ __forceinline__ double min2(double x, double y) {
 }
 __device__ __forceinline__ float min2(float x, float y) { return __builtin_fminf(x, y); }
 
-// Wavefront minimum with DPP moves instead of ds_bpermute shuffles: quad swaps, row half mirror,
-// row mirror (every lane of a 16-lane row then holds the row minimum), row_bcast15 / row_bcast31
-// (rows 1,3 <- lane 15 of rows 0,2; rows 2,3 <- lane 31): LANE 63 ends up with the minimum of the
-// wave.  Plain VALU moves: nothing goes through the LDS crossbar.
-#ifndef MXS_NARY_DPP
-#define MXS_NARY_DPP 1  // measured: meeting_50k 1168 -> 1099 us (f32 681 -> 655), parity green
-#endif
-#if MXS_NARY_DPP  // (the emulated build of the CPU tests provides the same lane-selection rules: tests/emu/hip)
+// Lane moves of the wave reductions below: DPP moves instead of ds_bpermute shuffles, plain VALU moves that do not go
+// through the LDS crossbar (measured: meeting_50k 1168 -> 1099 us, f32 681 -> 655, parity green).  The emulated build
+// of the CPU tests provides the same lane-selection rules: tests/emu/hip.
 template <int CTRL, int ROW_MASK>
 __device__ __forceinline__ double dpp_mov(double x) {
     int lo = __double2loint(x), hi = __double2hiint(x);
@@ -1396,16 +1365,6 @@ __device__ __forceinline__ float dpp_mov(float x) {
     int b = __float_as_int(x);
     b = __builtin_amdgcn_update_dpp(b, b, CTRL, ROW_MASK, 0xf, false);
     return __int_as_float(b);
-}
-template <typename T>
-__device__ __forceinline__ T wave_min_to_lane63(T x) {
-    x = min2(x, dpp_mov<0xB1, 0xf>(x));   // quad_perm [1,0,3,2]
-    x = min2(x, dpp_mov<0x4E, 0xf>(x));   // quad_perm [2,3,0,1]
-    x = min2(x, dpp_mov<0x141, 0xf>(x));  // row_half_mirror
-    x = min2(x, dpp_mov<0x140, 0xf>(x));  // row_mirror
-    x = min2(x, dpp_mov<0x142, 0xa>(x));  // row_bcast15 -> rows 1, 3
-    x = min2(x, dpp_mov<0x143, 0xc>(x));  // row_bcast31 -> rows 2, 3
-    return x;
 }
 // The two registers a permlane swap of (x, x) leaves behind, per 32-bit half of T.
 typedef unsigned int swap2u __attribute__((ext_vector_type(2)));
@@ -1434,10 +1393,7 @@ template <typename T> __device__ __forceinline__ T swap32_hi(T x) { return swap_
 // the partner's copies of what it keeps; step B (partner l^2): one value per lane is left --
 // value index 2*(l&1) + ((l>>1)&1); then lanes l+4, l+8, l+12 of the row (row_ror keeps l & 3) and
 // the other rows (l^16, l^32).  Every lane returns the wave minimum of ITS value index.
-// 7 minima and 14 moves instead of 24 and 48.
-#ifndef MXS_NARY_REDUCE4
-#define MXS_NARY_REDUCE4 1  // measured: meeting_50k 774 -> 601 us (f32 483 -> 386), parity green
-#endif
+// 7 minima and 14 moves instead of 24 and 48 (measured: meeting_50k 774 -> 601 us, f32 483 -> 386, parity green).
 template <typename T>
 __device__ __forceinline__ T wave_min4(const T (&b)[4]) {
     const int l = (int)threadIdx.x & 63;
@@ -1459,7 +1415,6 @@ __device__ __forceinline__ T wave_min4(const T (&b)[4]) {
     k = min2(swap32_lo(k), swap32_hi(k));
     return k;
 }
-#endif
 
 constexpr int NARY_UNR = 4;  // values of d0 per batch: UNR * NJ table loads per lane in flight,
                              // and the next batch is requested before this one is reduced
@@ -1508,33 +1463,11 @@ __device__ __forceinline__ void nary_batch(const T (&tv)[NARY_UNR][NJ], int d0, 
         }
         best0[u] = b0;
     }
-#if MXS_NARY_DPP && MXS_NARY_REDUCE4
     static_assert(NARY_UNR == 4, "wave_min4 reduces four values");
-    {
-        const T m = wave_min4(best0);
-        const int l = (int)threadIdx.x & 63;
-        const int u = 2 * (l & 1) + ((l >> 1) & 1);
-        if (l < 4 && (!MASKED || d0 + u < D0)) atomicMin(&s_key0[d0 + u], OrdKey<T>::enc(m));
-    }
-    if (false) {
-#elif MXS_NARY_DPP
-#pragma unroll
-    for (int u = 0; u < NARY_UNR; ++u) best0[u] = wave_min_to_lane63(best0[u]);
-    if ((threadIdx.x & 63) == 63) {
-#else
-    // UNR independent wavefront reductions, interleaved step by step
-#pragma unroll
-    for (int sft = 32; sft > 0; sft >>= 1) {
-#pragma unroll
-        for (int u = 0; u < NARY_UNR; ++u)
-            best0[u] = min2(best0[u], __shfl(best0[u], (int)((threadIdx.x & 63) ^ sft), 64));
-    }
-    if ((threadIdx.x & 63) == 0) {
-#endif
-#pragma unroll
-        for (int u = 0; u < NARY_UNR; ++u)
-            if (!MASKED || d0 + u < D0) atomicMin(&s_key0[d0 + u], OrdKey<T>::enc(best0[u]));
-    }
+    const T m = wave_min4(best0);
+    const int l = (int)threadIdx.x & 63;
+    const int u = 2 * (l & 1) + ((l >> 1) & 1);
+    if (l < 4 && (!MASKED || d0 + u < D0)) atomicMin(&s_key0[d0 + u], OrdKey<T>::enc(m));
 }
 
 // x / D and x % D for a block-uniform D with the host's magic number (NaryDesc::magic): a multiply-high

@@ -51,14 +51,8 @@ __device__ __forceinline__ T box_entry(const uint32_t* w, int e) {
     else return (T)(int)(int16_t)(uint16_t)(w[e >> 1] >> (16 * (e & 1)));
 }
 
-#ifndef MXS_BOX_EU
-#define MXS_BOX_EU 0  // > 0: register budget for that many waves per SIMD (experiments: profiles/r06_box3_isa.txt)
-#endif
 template <typename T, typename TT, bool NEG, int B0, int B1, int B2>
 __global__ void __launch_bounds__(BOX_WAVES * 64)
-#if MXS_BOX_EU > 0
-__attribute__((amdgpu_waves_per_eu(MXS_BOX_EU, MXS_BOX_EU)))
-#endif
 k_factor_box3(SweepArgs<T> a, const NaryDesc* descs, int n_factors) {
     constexpr int E = B0 * B1 * B2, NV = B0 + B1 + B2;
     constexpr int NW = box_rec_words(E, (int)sizeof(TT)), FULL = NW / 4, REST = NW % 4;
@@ -259,11 +253,11 @@ k_factor_box3(SweepArgs<T> a, const NaryDesc* descs, int n_factors) {
 template <typename T>
 inline bool launch_factor_box3(const NaryLaunch& nl, const SweepArgs<T>& a, const NaryDesc* d, hipStream_t stream) {
     const dim3 grid((unsigned)((nl.count + BOX_WAVES - 1) / BOX_WAVES)), block((unsigned)(BOX_WAVES * 64));
-#define MXS_BOX_LAUNCH(TT, B0, B1, B2)                                                                              \
-    do {                                                                                                             \
-        if (a.tab_neg) MXS_LAUNCH((k_factor_box3<T, TT, true, B0, B1, B2>), grid, block, 0, stream, a, d, (int)nl.count);  \
-        else MXS_LAUNCH((k_factor_box3<T, TT, false, B0, B1, B2>), grid, block, 0, stream, a, d, (int)nl.count);           \
-        return true;                                                                                                 \
+#define MXS_BOX_LAUNCH(TT, B0, B1, B2)                                                                                             \
+    do {                                                                                                                           \
+        if (a.tab_neg) hipLaunchKernelGGL((k_factor_box3<T, TT, true, B0, B1, B2>), grid, block, 0, stream, a, d, (int)nl.count);  \
+        else hipLaunchKernelGGL((k_factor_box3<T, TT, false, B0, B1, B2>), grid, block, 0, stream, a, d, (int)nl.count);           \
+        return true;                                                                                                               \
     } while (0)
     if (nl.tab_type == TAB_I8) {
         switch (nl.box) {

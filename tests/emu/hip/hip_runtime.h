@@ -78,7 +78,6 @@ inline hipError_t hipDeviceSynchronize() { return hipSuccess; }
 inline hipError_t hipStreamCreateWithFlags(hipStream_t* s, unsigned) { *s = (void*)1; return hipSuccess; }
 inline hipError_t hipStreamSynchronize(hipStream_t) { return hipSuccess; }
 inline hipError_t hipDeviceGetStreamPriorityRange(int* lo, int* hi) { *lo = 0; *hi = -1; return hipSuccess; }
-inline hipError_t hipExtStreamCreateWithCUMask(hipStream_t* s, uint32_t, const uint32_t*) { *s = (void*)1; return hipSuccess; }
 inline hipError_t hipStreamCreateWithPriority(hipStream_t* s, unsigned, int) { *s = (void*)1; return hipSuccess; }
 inline hipError_t hipStreamDestroy(hipStream_t) { return hipSuccess; }
 inline hipError_t hipEventCreate(hipEvent_t* e) { *e = (void*)1; return hipSuccess; }
@@ -240,9 +239,8 @@ inline V __shfl(V var, int src_lane, int width = 64) {
     return out;
 }
 
-// DPP moves and the gfx950 permlane swaps the wave reductions of kernels.h use (wave_min_to_lane63,
-// wave_min4): the lane-selection rules of the ISA, so that the CPU suite runs the product's reduction and
-// not a stand-in.  old == what a lane keeps when its row is masked off or the control gives it no source.
+// DPP moves and the gfx950 permlane swaps the wave reductions of kernels.h use (wave_min4): the
+// lane-selection rules of the ISA, so that the CPU suite runs the product's reduction and not a stand-in.  old == what a lane keeps when its row is masked off or the control gives it no source.
 inline int __builtin_amdgcn_update_dpp(int old, int src, int ctrl, int row_mask, int bank_mask, bool bound_ctrl) {
     (void)bank_mask;
     (void)bound_ctrl;
@@ -251,10 +249,6 @@ inline int __builtin_amdgcn_update_dpp(int old, int src, int ctrl, int row_mask,
     hipemu::yield_barrier();
     int from = -1;
     if (ctrl < 0x100) from = (int)((lane & ~3u) + (((unsigned)ctrl >> (2 * (lane & 3))) & 3u));  // quad_perm
-    else if (ctrl == 0x140) from = (int)(row * 16 + 15 - i);                                        // row_mirror
-    else if (ctrl == 0x141) from = (int)((lane & ~7u) + 7 - (lane & 7));                            // row_half_mirror
-    else if (ctrl == 0x142) from = row > 0 ? (int)(row * 16 - 1) : -1;     // row_bcast15: lane 15 of the previous row
-    else if (ctrl == 0x143) from = row >= 2 ? 31 : -1;                     // row_bcast31: lane 31 to rows 2, 3
     else if (ctrl >= 0x150 && ctrl < 0x160) from = (int)(row * 16 + (unsigned)(ctrl - 0x150));     // row_newbcast:n
     else if (ctrl > 0x120 && ctrl < 0x130) from = (int)(row * 16 + ((i + 16 - (unsigned)(ctrl - 0x120)) & 15));  // row_ror:n
     else abort();

@@ -47,7 +47,7 @@ def timed(fn, sync):
 
 
 ONLY = os.environ.get("MAXSUM_COST_ONLY", "abcd")  # which of the three loops to time
-for k in ("MAXSUM_COMM_CUS", "MAXSUM_SHARD_FUSED", "MAXSUM_SHARD_DIRECT", "MAXSUM_LAYOUT_FLAGS"):
+for k in ("MAXSUM_SHARD_FUSED", "MAXSUM_SHARD_DIRECT", "MAXSUM_LAYOUT_FLAGS"):
     if os.environ.get(k):
         out[k] = os.environ[k]
 if "a" not in ONLY:
