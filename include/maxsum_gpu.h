@@ -505,6 +505,26 @@ int mxs_dsa_get_state(mxs_dsa *e, int32_t *idx, double *cost);
 int mxs_dsa_eval_cost(mxs_dsa *e, const int32_t *idx, double infinity, double *cost, int64_t *violations);
 int mxs_dsa_destroy(mxs_dsa *e);
 
+/* ---- MGM-2 (pydcop/algorithms/mgm2.py) on the same flat arrays ----------------------------------
+ * One round = the five phases of Mgm2Computation (value :742-786, offer :787-856, answer :858-890,
+ * gain :892-972, go :974-1001) for every variable -- n rounds = the reference with stop_cycle = n + 1.
+ * `threshold`: probability of being an offerer; favor: 0 = unilateral, 1 = no, 2 = coordinated;
+ * `name_rank` as for MGM (NULL: index order).  Every draw of the reference's unseeded `random` comes
+ * from the keyed generator of DSA (seed, variable, round, draw) over canonically ordered sequences
+ * (tests/mgm2_oracle.py): bit for bit the reference's own Mgm2Computation objects under that generator.
+ * Constraint tables must be finite.  Variable costs do not enter the search (as in the reference);
+ * eval_cost includes them. */
+typedef struct mxs_mgm2 mxs_mgm2;
+int mxs_mgm2_create(const mxs_graph *g, const mxs_params *p, const int32_t *name_rank, double threshold,
+                    int32_t favor, uint64_t seed, int32_t device, mxs_mgm2 **out);
+int mxs_mgm2_reset(mxs_mgm2 *e);
+int mxs_mgm2_run(mxs_mgm2 *e, int32_t n_rounds);
+int mxs_mgm2_rounds(const mxs_mgm2 *e, int64_t *rounds);
+/* current value index and the cost the computation holds (has_cost = 0: still None before round 1) */
+int mxs_mgm2_get_state(mxs_mgm2 *e, int32_t *idx, double *cost, uint8_t *has_cost);
+int mxs_mgm2_eval_cost(mxs_mgm2 *e, const int32_t *idx, double infinity, double *cost, int64_t *violations);
+int mxs_mgm2_destroy(mxs_mgm2 *e);
+
 /* Library/ABI version (major*100+minor). */
 int32_t mxs_version(void);
 

@@ -1,0 +1,125 @@
+"""mgm2_gpu -- the reference's MGM-2 (pydcop/algorithms/mgm2.py) on the GPU, behind the algorithm-module
+contract (same GRAPH_TYPE `constraints_hypergraph`, the same three parameters with the same defaults,
+the same footprint / load formulas), reusing the proxies and the session of `maxsum_gpu`.
+
+One round of MGM-2 = five launches over all variables (pydcop_amd/csrc/mgm2.h).  `stop_cycle: n` ends
+like the reference does: after n - 1 rounds (`_send_value` counts the cycle before it tests for the
+stop, mgm2.py:659-672); 0 = keep going, `chunk` rounds per report, until the orchestrator's timeout.
+Extra parameter `seed` (default 0): every stochastic choice -- start value, offerer test, partner,
+best unilateral value, the `favor: no` coin, the accepted offer -- comes from the counter-based
+generator of dsa_gpu keyed on (seed, variable, round, draw) over canonically ordered sequences, where
+the reference draws from Python's unseeded `random`: a run is reproducible, and bit for bit the
+reference's own Mgm2Computation under the same generator.
+"""
+from types import SimpleNamespace
+
+from pydcop.algorithms import AlgoParameterDef
+
+from pydcop_amd.algorithms import maxsum_gpu as _base
+from pydcop_amd.algorithms.mgm_gpu import _MgmSession
+from pydcop_amd.compile import compile_nodes
+from pydcop_amd.graph import Params
+
+GRAPH_TYPE = "constraints_hypergraph"
+HEADER_SIZE = 100
+UNIT_SIZE = 5
+
+algo_params = [
+    AlgoParameterDef("threshold", "float", None, 0.5),
+    AlgoParameterDef("favor", "str", ["unilateral", "no", "coordinated"], "unilateral"),
+    AlgoParameterDef("stop_cycle", "int", None, 0),
+    AlgoParameterDef("precision", "str", ["f64", "f32"], "f64"),
+    AlgoParameterDef("seed", "int", None, 0),
+    AlgoParameterDef("chunk", "int", None, 10),
+]
+
+
+def computation_memory(computation) -> float:
+    """pydcop/algorithms/mgm2.py:66-91: a value and a gain per neighbour."""
+    neighbors = set(n for link in computation.links for n in link.nodes if n not in computation.name)
+    return len(neighbors) * 2 * UNIT_SIZE
+
+
+def communication_load(src, target: str) -> float:
+    """pydcop/algorithms/mgm2.py:94-128: the offer message, (two values and a gain) per pair of values."""
+    target_v = None
+    for c in src.constraints:
+        for v in c.dimensions:
+            if v.name == target:
+                target_v = v
+    if not target_v:
+        raise ValueError("target variable {} not found in constraints for {}".format(target, src))
+    nb_pairs = len(target_v.domain) * len(src.variable.domain)
+    return nb_pairs * UNIT_SIZE * 3 + HEADER_SIZE
+
+
+def compile_dcop_for_local_search(dcop):
+    """A DCOP compiled as this plug-in compiles it: the nodes of the reference's constraints
+    hypergraph by name, each variable's constraints in the node's order."""
+    from pydcop.computations_graph import constraints_hypergraph as chg
+    cg = chg.build_computation_graph(dcop)
+    return _compile_hypergraph(list(cg.nodes))
+
+
+def _compile_hypergraph(nodes):
+    nodes = sorted(nodes, key=lambda n: n.name)
+    constraints = {}
+    for n in nodes:
+        for c in n.constraints:
+            constraints.setdefault(c.name, c)
+    fac_nodes = [SimpleNamespace(name=name, factor=constraints[name]) for name in sorted(constraints)]
+    var_nodes = [SimpleNamespace(name=n.name, variable=n.variable,
+                                 links=[SimpleNamespace(factor_node=c.name) for c in n.constraints])
+                 for n in nodes]
+    return compile_nodes(var_nodes, fac_nodes, noise=0.0)
+
+
+class _RoundEngine:
+    """Mgm2Engine behind the surface the session drives."""
+
+    def __init__(self, graph, params, p):
+        from pydcop_amd.mgm2 import Mgm2Engine
+        self.graph = graph
+        self._e = Mgm2Engine(graph, params, threshold=p["threshold"], favor=p["favor"], seed=int(p["seed"]))
+
+    def run(self, n: int):
+        self._e.run(int(n))
+
+    def assignment(self):
+        return self._e.assignment()
+
+    @property
+    def cycle_count(self) -> int:
+        return self._e.cycle_count + 1          # the reference's counter starts at 1 (mgm2.py:659)
+
+    def close(self):
+        self._e.close()
+
+
+class _Mgm2Session(_MgmSession):      # (same compilation of the hypergraph nodes and stop_cycle as mgm_gpu)
+    ALGO = "mgm2_gpu"
+
+    def _compile_graph(self, p):
+        return _compile_hypergraph(cd.node for cd in self.comp_defs.values())
+
+    def _make_engine(self, params, p):
+        return _RoundEngine(self.graph, params, p)
+
+    def update_factor(self, name, old, fn):
+        raise ValueError("mgm2_gpu: change_factor_function is a maxsum_gpu feature")
+
+
+_base.SESSION_CLASSES["mgm2_gpu"] = _Mgm2Session
+
+
+class Mgm2GpuComputation(_base.MaxSumGpuVariableComputation):
+    """Stands for an Mgm2Computation (pydcop/algorithms/mgm2.py:399)."""
+
+    def footprint(self) -> float:
+        return computation_memory(self.computation_def.node)
+
+
+def build_computation(comp_def):
+    if comp_def.node.type != "VariableComputationNode":
+        raise ValueError("mgm2_gpu: unsupported computation node type " + str(comp_def.node.type))
+    return Mgm2GpuComputation(comp_def)

@@ -1,5 +1,5 @@
 """Direct API: solve a pyDCOP `DCOP` object (or a YAML file, or an .npz instance) on the GPU
-without agents -- synchronous Max-Sum by default, `algo=` "amaxsum", "dsa" or "mgm" for the other
+without agents -- synchronous Max-Sum by default, `algo=` "amaxsum", "dsa", "mgm" or "mgm2" for the other
 engines of the library.
 
 `pydcop.infrastructure.run.solve` (pydcop/infrastructure/run.py:49) deploys one
@@ -18,7 +18,7 @@ from .compile import assignment_to_values, compile_nodes
 from .graph import FlatGraph, Params
 
 
-ALGOS = ("maxsum", "amaxsum", "dsa", "mgm")
+ALGOS = ("maxsum", "amaxsum", "dsa", "mgm", "mgm2")
 
 
 def _engine_for(graph: FlatGraph, params: Params, device: int, devices: int, lib_path, algo: str = "maxsum",
@@ -38,6 +38,9 @@ def _engine_for(graph: FlatGraph, params: Params, device: int, devices: int, lib
         if algo == "dsa":
             from .dsa import DsaEngine
             return DsaEngine(graph, params, device=device, lib_path=lib_path, **algo_kw)
+        if algo == "mgm2":
+            from .mgm2 import Mgm2Engine
+            return Mgm2Engine(graph, params, device=device, lib_path=lib_path, **algo_kw)
         from .mgm import MgmEngine
         return MgmEngine(graph, params, device=device, lib_path=lib_path)
     from .engine import MaxSumEngine
@@ -45,6 +48,14 @@ def _engine_for(graph: FlatGraph, params: Params, device: int, devices: int, lib
         from .sharded import LocalShardedMaxSum
         return LocalShardedMaxSum(graph, params, list(range(int(devices))), lib_path=lib_path)
     return MaxSumEngine(graph, params, device=device, lib_path=lib_path)
+
+
+def _algo_kw(algo, variant, probability, p_mode, seed, threshold, favor):
+    if algo == "dsa":
+        return dict(variant=variant, probability=probability, p_mode=p_mode, seed=seed)
+    if algo == "mgm2":
+        return dict(threshold=threshold, favor=favor, seed=seed)
+    return None
 
 
 def _run_and_trace(eng, algo: str, cycles: int, cost_every: int, infinity: float):
@@ -78,12 +89,14 @@ def solve_dcop(dcop, cycles: int = 30, *, damping: float = 0.5, damping_nodes: s
                stability: float = 0.1, noise: float = 0.01, start_messages: str = "leafs",
                precision: str = "f64", seed: int = 0, infinity: float = 10000, device: int = 0,
                cost_every: int = 0, lib_path: Optional[str] = None, devices: int = 1, algo: str = "maxsum",
-               variant: str = "B", probability: float = 0.7, p_mode: str = "fixed") -> Dict:
+               variant: str = "B", probability: float = 0.7, p_mode: str = "fixed", threshold: float = 0.5,
+               favor: str = "unilateral") -> Dict:
     """Synchronous Max-Sum for exactly `cycles` cycles; parameters and defaults are those
     of `pydcop.algorithms.maxsum` (maxsum.py:212-220), `infinity` that of
     `pydcop.infrastructure.run.solve` (run.py:49).  `algo`: "amaxsum" (`cycles` = generations of
     messages under FIFO delivery, same parameters), "dsa" (`variant`, `probability`, `p_mode` of
-    pydcop.algorithms.dsa, dsa.py:119-125; `seed` keys its draws) or "mgm"; the local-search
+    pydcop.algorithms.dsa, dsa.py:119-125; `seed` keys its draws), "mgm" or "mgm2" (`threshold`,
+    `favor` of pydcop.algorithms.mgm2, mgm2.py:142-146; `seed` keys its draws); the local-search
     algorithms take no noise (their variable costs enter as the reference's do).
 
     Returns {"assignment", "cost", "violation", "cycle", "cost_curve"}: the first three
@@ -94,7 +107,7 @@ def solve_dcop(dcop, cycles: int = 30, *, damping: float = 0.5, damping_nodes: s
     graph = compile_dcop(dcop, noise=noise if algo in ("maxsum", "amaxsum") else 0.0, seed=seed)
     params = Params(mode=dcop.objective, damping=damping, damping_nodes=damping_nodes,
                     stability=stability, start_messages=start_messages, dtype=precision)
-    algo_kw = dict(variant=variant, probability=probability, p_mode=p_mode, seed=seed) if algo == "dsa" else None
+    algo_kw = _algo_kw(algo, variant, probability, p_mode, seed, threshold, favor)
     with _engine_for(graph, params, device, devices, lib_path, algo, algo_kw) as eng:
         curve = _run_and_trace(eng, algo, cycles, cost_every, infinity)
         idx, _ = eng.assignment()
@@ -108,14 +121,15 @@ def solve_flat(graph: FlatGraph, objective: str = "min", cycles: int = 30, *, da
                damping_nodes: str = "both", stability: float = 0.1, start_messages: str = "leafs",
                precision: str = "f64", infinity: float = 10000, device: int = 0, cost_every: int = 0,
                lib_path: Optional[str] = None, devices: int = 1, algo: str = "maxsum", variant: str = "B",
-               probability: float = 0.7, p_mode: str = "fixed", seed: int = 0) -> Dict:
+               probability: float = 0.7, p_mode: str = "fixed", seed: int = 0, threshold: float = 0.5,
+               favor: str = "unilateral") -> Dict:
     """`solve_dcop` for an already compiled instance (`FlatGraph`, e.g. loaded from the
     .npz instance format): no pyDCOP import at all.  Cost and violations come from the
     device (`mxs_eval_cost` = DCOP.solution_cost, pydcop/dcop/dcop.py:308-367); noise, if
     wanted, is already folded into `graph.var_cost` by whoever compiled the instance."""
     params = Params(mode=objective, damping=damping, damping_nodes=damping_nodes,
                     stability=stability, start_messages=start_messages, dtype=precision)
-    algo_kw = dict(variant=variant, probability=probability, p_mode=p_mode, seed=seed) if algo == "dsa" else None
+    algo_kw = _algo_kw(algo, variant, probability, p_mode, seed, threshold, favor)
     with _engine_for(graph, params, device, devices, lib_path, algo, algo_kw) as eng:
         curve = _run_and_trace(eng, algo, cycles, cost_every, infinity)
         idx, _ = eng.assignment()
@@ -161,7 +175,7 @@ def main(argv=None):
     args = ap.parse_args(argv)
     kinds = {"damping": float, "stability": float, "noise": float, "seed": int,
              "damping_nodes": str, "start_messages": str, "precision": str, "devices": int,
-             "variant": str, "probability": float, "p_mode": str}
+             "variant": str, "probability": float, "p_mode": str, "threshold": float, "favor": str}
     kw = {}
     for item in args.algo_params:
         name, _, value = item.partition(":")
@@ -182,7 +196,7 @@ def main(argv=None):
     if len(args.dcop_files) == 1 and args.dcop_files[0].endswith(".npz"):
         graph, header = FlatGraph.load(args.dcop_files[0])
         kw.pop("noise", None)  # folded into the instance when it was compiled
-        if args.algo != "dsa":
+        if args.algo not in ("dsa", "mgm2"):
             kw.pop("seed", None)
         res = solve_flat(graph, header.get("objective", "min"), args.cycles, infinity=args.infinity,
                          cost_every=args.cost_every, algo=args.algo, **kw)

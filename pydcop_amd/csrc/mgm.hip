@@ -879,3 +879,6 @@ int mxs_mgm_destroy(mxs_mgm* e) {
 }
 
 }  // extern "C"
+
+// MGM-2 (pydcop/algorithms/mgm2.py) on the same slot view and helpers
+#include "mgm2.h"

@@ -53,6 +53,12 @@ ABI_SYMBOLS = (
     "mxs_dsa_eval_cost", "mxs_dsa_destroy",
 )
 
+# ... and the MGM-2 entry points (kept apart: the header check of tests/test_abi.py reads names without digits)
+MGM2_SYMBOLS = (
+    "mxs_mgm2_create", "mxs_mgm2_reset", "mxs_mgm2_run", "mxs_mgm2_rounds", "mxs_mgm2_get_state", "mxs_mgm2_eval_cost",
+    "mxs_mgm2_destroy",
+)
+
 
 MAX_PEERS = 8
 
@@ -167,6 +173,14 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
         "mxs_mgm_get_state": ([vp, vp, vp, vp, vp, vp], C.c_int),
         "mxs_mgm_eval_cost": ([vp, vp, C.c_double, C.POINTER(C.c_double), C.POINTER(i64)], C.c_int),
         "mxs_mgm_destroy": ([vp], C.c_int),
+        "mxs_mgm2_create": ([C.POINTER(CGraph), C.POINTER(CParams), vp, C.c_double, i32, C.c_uint64, i32,
+                             C.POINTER(vp)], C.c_int),
+        "mxs_mgm2_reset": ([vp], C.c_int),
+        "mxs_mgm2_run": ([vp, i32], C.c_int),
+        "mxs_mgm2_rounds": ([vp, C.POINTER(i64)], C.c_int),
+        "mxs_mgm2_get_state": ([vp, vp, vp, vp], C.c_int),
+        "mxs_mgm2_eval_cost": ([vp, vp, C.c_double, C.POINTER(C.c_double), C.POINTER(i64)], C.c_int),
+        "mxs_mgm2_destroy": ([vp], C.c_int),
         "mxs_dsa_create": ([C.POINTER(CGraph), C.POINTER(CParams), i32, C.c_double, i32, C.c_uint64, i32,
                             C.POINTER(vp)], C.c_int),
         "mxs_dsa_reset": ([vp], C.c_int),

@@ -1,13 +1,15 @@
-"""Cycles per second of the DSA and MGM engines (pydcop_amd/csrc/dsa.hip, mgm.hip) on the
+"""Cycles per second of the DSA, MGM and MGM-2 engines (pydcop_amd/csrc/dsa.hip, mgm.hip, mgm2.h) on the
 100k-variable colouring instance of the bench and on the meeting instance (24 values, arity 3):
 
-    python tools/local_search_bench.py [--cycles 500]
+    python tools/local_search_bench.py [--cycles 500] [--mgm2-rounds 200]
 
 One JSON line per (algorithm, instance, kernels); "kernels": "packed" = the default (lane per
 constraint where the instance allows it, local_search.h), "slots" = the thread-per-variable
 register-array kernels on the slot view (MAXSUM_LOCAL_SEARCH_GENERIC=2), "csr_walk" = the generic
 kernels (=1), "strided" = the default kernels without the private row copies of the variables the pack
 cannot take (MAXSUM_LOCAL_SEARCH_ROWS=0: their D entries per constraint a stride apart, round 3).
+MGM-2 has one family of kernels ("kernels": "mgm2"), timed in f64 and f32 after the MGM / DSA rows of an
+instance; every timing ends with the engine's stream synchronised (run() returns after it).
 """
 import argparse
 import json
@@ -21,6 +23,7 @@ from pydcop_amd import generators as G  # noqa: E402
 from pydcop_amd.dsa import DsaEngine  # noqa: E402
 from pydcop_amd.graph import Params  # noqa: E402
 from pydcop_amd.mgm import MgmEngine  # noqa: E402
+from pydcop_amd.mgm2 import Mgm2Engine  # noqa: E402
 
 
 def main():
@@ -29,6 +32,7 @@ def main():
     ap.add_argument("--lib", default=None)
     ap.add_argument("--instances", nargs="*", default=["coloring_100k", "meeting_50k"])
     ap.add_argument("--kernels", nargs="*", default=["packed", "strided", "slots", "csr_walk"])
+    ap.add_argument("--mgm2-rounds", type=int, default=200, help="0: no MGM-2 rows")
     a = ap.parse_args()
     instances = [("coloring_100k", lambda: G.random_coloring(100_000, seed=0, names=False), Params()),
                  ("meeting_50k", lambda: G.meeting_like(50_000, dom=24, seed=0, names=False), Params(mode="max"))]
@@ -54,6 +58,21 @@ def main():
                                   "cycles_per_s": round(a.cycles / dt, 1), "us_per_cycle": round(1e6 * dt / a.cycles, 2),
                                   "cost": eng.eval_cost()[0], "engine_setup_s": round(setup_s, 2)}), flush=True)
                 eng.close()
+        os.environ.pop("MAXSUM_LOCAL_SEARCH_GENERIC", None)
+        os.environ.pop("MAXSUM_LOCAL_SEARCH_ROWS", None)
+        for dtype in ("f64", "f32") if a.mgm2_rounds > 0 else ():
+            t0 = time.perf_counter()
+            eng = Mgm2Engine(g, Params(mode=p.mode, dtype=dtype), seed=1, lib_path=a.lib)
+            setup_s = time.perf_counter() - t0
+            eng.run(5)
+            t0 = time.perf_counter()
+            eng.run(a.mgm2_rounds)
+            dt = time.perf_counter() - t0
+            print(json.dumps({"algo": "mgm2", "instance": inst, "kernels": "mgm2", "dtype": dtype, "n_vars": g.n_vars,
+                              "cycles_per_s": round(a.mgm2_rounds / dt, 1),
+                              "us_per_cycle": round(1e6 * dt / a.mgm2_rounds, 2),
+                              "cost": eng.eval_cost()[0], "engine_setup_s": round(setup_s, 2)}), flush=True)
+            eng.close()
 
 
 if __name__ == "__main__":
