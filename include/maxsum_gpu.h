@@ -525,6 +525,40 @@ int mxs_mgm2_get_state(mxs_mgm2 *e, int32_t *idx, double *cost, uint8_t *has_cos
 int mxs_mgm2_eval_cost(mxs_mgm2 *e, const int32_t *idx, double infinity, double *cost, int64_t *violations);
 int mxs_mgm2_destroy(mxs_mgm2 *e);
 
+/* ---- DPOP (pydcop/algorithms/dpop.py) on the same flat arrays: the exact optimum -------------------
+ * The caller gives the pseudo-tree: parent[v] (-1: a root) and every node's children in order
+ * (child_idx[child_rowptr[v] .. child_rowptr[v+1])); pydcop_amd.dpop.build_pseudotree restates the
+ * reference's DFS heuristic.  The tree must be acyclic and every constraint's scope must lie on one
+ * root path ("not a pseudo-tree" otherwise).  A constraint belongs to the deepest variable of its
+ * scope, in that variable's var_edges order.  A node joins its own cost vector, its children's UTILs
+ * in children order, then its constraints, one IEEE add per term in that order, and projects itself
+ * out with the first optimum in domain order -- bit for bit the reference's DpopAlgo when the UTIL
+ * messages arrive in children order.  There are no draws and no cycles: solve runs UTIL then VALUE.
+ * Refused: inf / NaN entries; sum of the tables' and variable costs' largest magnitudes >= 2147483647
+ * (the reference's find_arg_optimal starts from the int32 extremes); UTIL tables that need more than
+ * `max_bytes` (0: 80 % of the device memory that is free), tested before anything is allocated and
+ * reported with the bytes needed (MXS_E_NOMEM).  `fuse_entries`: consecutive tree levels of at most
+ * this many entries run in one single-workgroup launch (< 0: the built-in cap, 0: one launch per level). */
+typedef struct mxs_dpop mxs_dpop;
+int mxs_dpop_create(const mxs_graph *g, const mxs_params *p, const int32_t *parent, const int32_t *child_rowptr,
+                    const int32_t *child_idx, int64_t max_bytes, int32_t fuse_entries, int32_t device,
+                    mxs_dpop **out);
+int mxs_dpop_solve(mxs_dpop *e);
+/* chosen value index and the cost the computation reports: the joined value at the chosen entry (the
+ * optimum of the whole component for a root) */
+int mxs_dpop_get_state(mxs_dpop *e, int32_t *idx, double *cost);
+int mxs_dpop_eval_cost(mxs_dpop *e, const int32_t *idx, double infinity, double *cost, int64_t *violations);
+/* out[0..n): components, depth, widest separator (variables), widest UTIL (entries), all UTIL entries,
+ * their bytes, UTIL launches, VALUE launches, then the last solve's UTIL and VALUE times in ns
+ * (HIP events); entries beyond what the library knows are 0 */
+int mxs_dpop_stats(const mxs_dpop *e, int64_t *out, int32_t n);
+/* the separator of `var` in the order of the UTIL's axes (C order); dims == NULL: only the count.
+ * A root has no UTIL. */
+int mxs_dpop_util_dims(const mxs_dpop *e, int32_t var, int32_t *dims, int32_t *n);
+/* the UTIL `var` sent to its parent, converted to double (after solve) */
+int mxs_dpop_get_util(mxs_dpop *e, int32_t var, double *buf, int64_t n_entries);
+int mxs_dpop_destroy(mxs_dpop *e);
+
 /* Library/ABI version (major*100+minor). */
 int32_t mxs_version(void);
 

@@ -18,7 +18,8 @@ from .compile import assignment_to_values, compile_nodes
 from .graph import FlatGraph, Params
 
 
-ALGOS = ("maxsum", "amaxsum", "dsa", "mgm", "mgm2")
+ALGOS = ("maxsum", "amaxsum", "dsa", "mgm", "mgm2")      # the iterative ones: `cycles` of them
+CLI_ALGOS = ALGOS + ("dpop",)                              # DPOP has no cycles: solve_dcop_dpop / solve_flat_dpop
 
 
 def _engine_for(graph: FlatGraph, params: Params, device: int, devices: int, lib_path, algo: str = "maxsum",
@@ -28,7 +29,8 @@ def _engine_for(graph: FlatGraph, params: Params, device: int, devices: int, lib
     Every engine has run / assignment / eval_cost / close."""
     algo_kw = algo_kw or {}
     if algo not in ALGOS:
-        raise ValueError(f"algo must be one of {ALGOS}")
+        raise ValueError(f"algo must be one of {ALGOS}" + (
+            " (DPOP runs no cycles: solve_dcop_dpop / solve_flat_dpop)" if algo == "dpop" else ""))
     if algo != "maxsum":
         if devices and int(devices) > 1:
             raise ValueError("devices > 1: synchronous Max-Sum only")
@@ -142,6 +144,43 @@ def solve_flat(graph: FlatGraph, objective: str = "min", cycles: int = 30, *, da
             "cost_curve": curve}
 
 
+def solve_dcop_dpop(dcop, *, precision: str = "f64", infinity: float = 10000, device: int = 0, max_bytes: int = 0,
+                    lib_path: Optional[str] = None) -> Dict:
+    """DPOP (pydcop/algorithms/dpop.py): the exact optimum, on the pseudo-tree the reference builds for the DCOP
+    (pydcop_amd/computations_graph/pseudotree_fast.py) and compiled as the dpop_gpu plug-in compiles it -- the
+    assignment `pydcop solve --algo dpop` returns.  Same result keys as `solve_dcop`; "cycle" is 0."""
+    from . import plugin
+    plugin.install()
+    from pydcop.computations_graph import pseudotree_fast
+    from pydcop_amd.algorithms.dpop_gpu import compile_pseudotree
+    from .dpop import DpopEngine
+    graph, tree = compile_pseudotree(pseudotree_fast.build_computation_graph(dcop).nodes)
+    with DpopEngine(graph, Params(mode=dcop.objective, dtype=precision), tree=tree, max_bytes=max_bytes,
+                    device=device, lib_path=lib_path) as eng:
+        eng.solve()
+        idx, _ = eng.assignment()
+    assignment = assignment_to_values(graph, idx)
+    violation, cost = dcop.solution_cost(assignment, infinity)
+    return {"assignment": assignment, "cost": cost, "violation": violation, "cycle": 0, "cost_curve": []}
+
+
+def solve_flat_dpop(graph: FlatGraph, objective: str = "min", *, precision: str = "f64", infinity: float = 10000,
+                    device: int = 0, max_bytes: int = 0, lib_path: Optional[str] = None) -> Dict:
+    """`solve_dcop_dpop` for a compiled instance: the tree is `build_pseudotree` over the instance's variable
+    and factor order; cost and violations are evaluated by the engine."""
+    from .dpop import DpopEngine
+    with DpopEngine(graph, Params(mode=objective, dtype=precision), max_bytes=max_bytes, device=device,
+                    lib_path=lib_path) as eng:
+        eng.solve()
+        idx, _ = eng.assignment()
+        cost, violation = eng.eval_cost(infinity=infinity)
+    if graph.var_names is not None and graph.domains is not None:
+        assignment = assignment_to_values(graph, idx)
+    else:
+        assignment = {f"v{i}": int(x) for i, x in enumerate(idx)}
+    return {"assignment": assignment, "cost": cost, "violation": violation, "cycle": 0, "cost_curve": []}
+
+
 def solve_yaml(paths, cycles: int = 30, **kw) -> Dict:
     """`solve_dcop` on DCOP YAML file(s) (pydcop/dcop/yamldcop.py:96)."""
     from . import plugin
@@ -165,7 +204,7 @@ def main(argv=None):
     ap = argparse.ArgumentParser(prog="python -m pydcop_amd.api")
     ap.add_argument("dcop_files", nargs="+")
     ap.add_argument("-c", "--cycles", type=int, default=30)
-    ap.add_argument("-a", "--algo", default="maxsum", choices=ALGOS)
+    ap.add_argument("-a", "--algo", default="maxsum", choices=CLI_ALGOS)   # (dpop: -c is ignored, cycle 0)
     ap.add_argument("-p", "--algo_params", action="append", default=[],
                     help="name:value, e.g. damping:0.7 noise:0 precision:f32 (maxsum.py:212-220)")
     ap.add_argument("--infinity", type=float, default=float("inf"))   # pydcop/commands/solve.py:316-324
@@ -198,8 +237,18 @@ def main(argv=None):
         kw.pop("noise", None)  # folded into the instance when it was compiled
         if args.algo not in ("dsa", "mgm2"):
             kw.pop("seed", None)
-        res = solve_flat(graph, header.get("objective", "min"), args.cycles, infinity=args.infinity,
-                         cost_every=args.cost_every, algo=args.algo, **kw)
+        if args.algo == "dpop":
+            res = solve_flat_dpop(graph, header.get("objective", "min"), infinity=args.infinity,
+                                  precision=kw.get("precision", "f64"))
+        else:
+            res = solve_flat(graph, header.get("objective", "min"), args.cycles, infinity=args.infinity,
+                             cost_every=args.cost_every, algo=args.algo, **kw)
+    elif args.algo == "dpop":
+        from . import plugin
+        plugin.install()
+        from pydcop.dcop.yamldcop import load_dcop_from_file
+        res = solve_dcop_dpop(load_dcop_from_file(list(args.dcop_files)), infinity=args.infinity,
+                              precision=kw.get("precision", "f64"))
     else:
         res = solve_yaml(args.dcop_files, args.cycles, infinity=args.infinity,
                          cost_every=args.cost_every, algo=args.algo, **kw)

@@ -882,3 +882,6 @@ int mxs_mgm_destroy(mxs_mgm* e) {
 
 // MGM-2 (pydcop/algorithms/mgm2.py) on the same slot view and helpers
 #include "mgm2.h"
+
+// DPOP (pydcop/algorithms/dpop.py): UTIL / VALUE over a pseudo-tree, tables in one flat pool
+#include "dpop.h"

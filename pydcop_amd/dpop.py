@@ -1,0 +1,198 @@
+"""DPOP (pydcop/algorithms/dpop.py) on the GPU: the ctypes binding of the `mxs_dpop_*` entry points
+(include/maxsum_gpu.h; device code: pydcop_amd/csrc/dpop.h) on the same FlatGraph as the other engines,
+and the reference's pseudo-tree heuristic restated on flat arrays.  DPOP is complete: `solve()` returns
+the optimum, or the engine refuses the instance when its UTIL tables do not fit.  No CPU fallback."""
+import ctypes as C
+from typing import List, Optional, Tuple
+
+import numpy as np
+
+from .engine import MaxSumGpuError, load_library
+from .graph import FlatGraph, Params
+
+STATS = ("components", "depth", "widest_separator", "widest_util_entries", "total_entries", "bytes",
+         "launches_util", "launches_value", "util_ns", "value_ns")
+
+
+def neighbor_lists(graph: FlatGraph) -> List[List[int]]:
+    """Every variable's neighbours in the reference's order, from the flat arrays."""
+    frow, evar = graph.factor_rowptr, graph.edge_var
+    return neighbor_lists_of_scopes(graph.n_vars, [evar[frow[f]:frow[f + 1]] for f in range(graph.n_factors)])
+
+
+def neighbor_lists_of_scopes(n_vars: int, scopes) -> List[List[int]]:
+    """pseudotree._find_neighbors_relations (pseudotree.py:303-322) in one pass: over the constraints in
+    their order, the other variables of the scope in variable order, each neighbour listed once."""
+    by_var = [[] for _ in range(n_vars)]      # the constraints of a variable, ascending
+    scopes = [sorted(set(int(u) for u in scope)) for scope in scopes]
+    for f, scope in enumerate(scopes):
+        for u in scope:
+            by_var[u].append(f)
+    nbrs = []
+    for v in range(n_vars):
+        seen, out = {v}, []
+        for f in by_var[v]:
+            for u in scopes[f]:
+                if u not in seen:
+                    seen.add(u)
+                    out.append(u)
+        nbrs.append(out)
+    return nbrs
+
+
+def dfs_pseudotree(nbrs: List[List[int]]):
+    """pseudotree._generate_dfs_tree / build_computation_graph (pseudotree.py:242-291, 325-364, 530-537) without
+    recursion and without `in token` scans: -> (roots, parent, children, pseudo_parents, pseudo_children), lists
+    in the reference's order.  The token a node receives is its root path, so `n in token` is one mark.
+    A node sorts its neighbours, stably and descending, by how many of THEIR neighbours are on the path
+    (itself included); it then walks them: the parent and descendants that already called back are skipped,
+    an ancestor gets the node as a pseudo-child, anything else is unvisited and becomes a child.
+    One tree per component; the next root is the remaining variable with most neighbours, the last of the ties."""
+    n = len(nbrs)
+    parent = [-1] * n
+    children = [[] for _ in range(n)]
+    pseudo_parents = [[] for _ in range(n)]
+    pseudo_children = [[] for _ in range(n)]
+    visited = bytearray(n)
+    on_path = bytearray(n)
+    roots = []
+    # (a stable ascending sort by the neighbour count, read from its end; the counts of the remaining
+    # variables never change: a component leaves as a whole)
+    for root in reversed(sorted(range(n), key=lambda v: len(nbrs[v]))):
+        if visited[root]:
+            continue
+        roots.append(root)
+        stack = []
+
+        def enter(v):
+            visited[v] = 1
+            pseudo_parents[v] = [u for u in nbrs[v] if on_path[u] and u != parent[v]]
+            on_path[v] = 1
+            keys = [sum(on_path[x] for x in nbrs[u]) for u in nbrs[v]]
+            order = sorted(range(len(keys)), key=lambda i: -keys[i])
+            stack.append((v, [nbrs[v][i] for i in order], 0))
+
+        enter(root)
+        while stack:
+            v, walk, i = stack.pop()
+            if i == len(walk):
+                on_path[v] = 0
+                continue
+            stack.append((v, walk, i + 1))
+            u = walk[i]
+            if u == parent[v] or (visited[u] and not on_path[u]):
+                continue
+            if on_path[u]:
+                pseudo_children[u].append(v)
+            else:
+                children[v].append(u)
+                parent[u] = v
+                enter(u)
+    return roots, parent, children, pseudo_parents, pseudo_children
+
+
+def build_pseudotree(graph: FlatGraph) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+    """-> (parent int32 [n_vars] with -1 for roots, child_rowptr int32 [n_vars + 1], child_idx int32): the tree
+    `pseudotree.build_computation_graph` builds for the same variables (index order) and constraints (factor order)."""
+    _, parent, children, _, _ = dfs_pseudotree(neighbor_lists(graph))
+    return pack_tree(parent, children)
+
+
+def pack_tree(parent, children):
+    rowptr = np.zeros(len(parent) + 1, dtype=np.int32)
+    np.cumsum([len(c) for c in children], out=rowptr[1:])
+    idx = np.array([c for cs in children for c in cs], dtype=np.int32)
+    return np.array(parent, dtype=np.int32), rowptr, idx
+
+
+class DpopEngine:
+    """>>> with DpopEngine(graph, Params(mode="min")) as eng:
+    ...     eng.solve()
+    ...     idx, cost = eng.assignment()      # cost[root]: the optimum of the root's component
+    """
+
+    def __init__(self, graph: FlatGraph, params: Optional[Params] = None, tree=None, max_bytes: int = 0,
+                 fuse_entries: int = -1, device: int = 0, lib_path: Optional[str] = None):
+        self._h = None
+        self._lib = load_library(lib_path)
+        self.graph = graph
+        self.params = params or Params()
+        parent, rowptr, idx = build_pseudotree(graph) if tree is None else tree
+        self.parent = np.ascontiguousarray(parent, dtype=np.int32)
+        self.child_rowptr = np.ascontiguousarray(rowptr, dtype=np.int32)
+        self.child_idx = np.ascontiguousarray(idx, dtype=np.int32)
+        if self.parent.shape[0] != graph.n_vars or self.child_rowptr.shape[0] != graph.n_vars + 1 or (
+                graph.n_vars and self.child_idx.shape[0] != int(self.child_rowptr[-1])):
+            raise ValueError("tree: (parent [n_vars], child_rowptr [n_vars + 1], child_idx [child_rowptr[-1]]) expected")
+        cg, cp = graph.to_c(), self.params.to_c()
+        h = C.c_void_p()
+        self._check(self._lib.mxs_dpop_create(C.byref(cg), C.byref(cp), self.parent.ctypes.data,
+                                              self.child_rowptr.ctypes.data, self.child_idx.ctypes.data,
+                                              int(max_bytes), int(fuse_entries), int(device), C.byref(h)))
+        self._h = h
+
+    def _check(self, rc: int):
+        if rc != 0:
+            raise MaxSumGpuError(f"maxsum_gpu error {rc}: {self._lib.mxs_last_error().decode()}")
+
+    def solve(self):
+        """UTIL bottom-up, then VALUE top-down."""
+        self._check(self._lib.mxs_dpop_solve(self._h))
+
+    cycle_count = 0      # DPOP has no cycles
+
+    def state(self) -> dict:
+        n = self.graph.n_vars
+        out = {"idx": np.empty(n, dtype=np.int32), "cost": np.empty(n)}
+        self._check(self._lib.mxs_dpop_get_state(self._h, out["idx"].ctypes.data, out["cost"].ctypes.data))
+        return out
+
+    def assignment(self) -> Tuple[np.ndarray, np.ndarray]:
+        s = self.state()
+        return s["idx"], s["cost"]
+
+    def stats(self) -> dict:
+        out = np.zeros(len(STATS), dtype=np.int64)
+        self._check(self._lib.mxs_dpop_stats(self._h, out.ctypes.data, len(STATS)))
+        return dict(zip(STATS, (int(x) for x in out)))
+
+    def util_dims(self, var: int) -> np.ndarray:
+        n = C.c_int32(0)
+        self._check(self._lib.mxs_dpop_util_dims(self._h, int(var), None, C.byref(n)))
+        dims = np.empty(n.value, dtype=np.int32)
+        self._check(self._lib.mxs_dpop_util_dims(self._h, int(var), dims.ctypes.data, C.byref(n)))
+        return dims
+
+    def util(self, var: int) -> Tuple[np.ndarray, np.ndarray]:
+        """-> (dims, table): the UTIL `var` sent to its parent, one axis per separator variable in `dims` order."""
+        dims = self.util_dims(var)
+        shape = tuple(int(self.graph.dom_size[u]) for u in dims)
+        table = np.empty(shape, dtype=np.float64)
+        self._check(self._lib.mxs_dpop_get_util(self._h, int(var), table.ctypes.data, int(table.size)))
+        return dims, table
+
+    def eval_cost(self, idx=None, infinity: float = float("inf")) -> Tuple[float, int]:
+        cost, viol = C.c_double(0), C.c_int64(0)
+        p = None
+        if idx is not None:
+            idx = np.ascontiguousarray(idx, dtype=np.int32)
+            p = idx.ctypes.data
+        self._check(self._lib.mxs_dpop_eval_cost(self._h, p, float(infinity), C.byref(cost), C.byref(viol)))
+        return float(cost.value), int(viol.value)
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._lib.mxs_dpop_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()

@@ -51,6 +51,8 @@ ABI_SYMBOLS = (
     "mxs_mgm_eval_cost", "mxs_mgm_destroy",
     "mxs_dsa_create", "mxs_dsa_reset", "mxs_dsa_set_value_rank", "mxs_dsa_run", "mxs_dsa_cycles", "mxs_dsa_get_state",
     "mxs_dsa_eval_cost", "mxs_dsa_destroy",
+    "mxs_dpop_create", "mxs_dpop_solve", "mxs_dpop_get_state", "mxs_dpop_eval_cost", "mxs_dpop_stats",
+    "mxs_dpop_util_dims", "mxs_dpop_get_util", "mxs_dpop_destroy",
 )
 
 # ... and the MGM-2 entry points (kept apart: the header check of tests/test_abi.py reads names without digits)
@@ -190,6 +192,14 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
         "mxs_dsa_get_state": ([vp, vp, vp], C.c_int),
         "mxs_dsa_eval_cost": ([vp, vp, C.c_double, C.POINTER(C.c_double), C.POINTER(i64)], C.c_int),
         "mxs_dsa_destroy": ([vp], C.c_int),
+        "mxs_dpop_create": ([C.POINTER(CGraph), C.POINTER(CParams), vp, vp, vp, i64, i32, i32, C.POINTER(vp)], C.c_int),
+        "mxs_dpop_solve": ([vp], C.c_int),
+        "mxs_dpop_get_state": ([vp, vp, vp], C.c_int),
+        "mxs_dpop_eval_cost": ([vp, vp, C.c_double, C.POINTER(C.c_double), C.POINTER(i64)], C.c_int),
+        "mxs_dpop_stats": ([vp, vp, i32], C.c_int),
+        "mxs_dpop_util_dims": ([vp, i32, vp, C.POINTER(i32)], C.c_int),
+        "mxs_dpop_get_util": ([vp, i32, vp, i64], C.c_int),
+        "mxs_dpop_destroy": ([vp], C.c_int),
         "mxs_cycle_bytes": ([vp, C.POINTER(i64), C.POINTER(i32)], C.c_int),
         "mxs_factor_order": ([vp, C.POINTER(i32)], C.c_int),
         "mxs_factor_kernels": ([vp, vp], C.c_int),
