@@ -559,6 +559,43 @@ int mxs_dpop_util_dims(const mxs_dpop *e, int32_t var, int32_t *dims, int32_t *n
 int mxs_dpop_get_util(mxs_dpop *e, int32_t var, double *buf, int64_t n_entries);
 int mxs_dpop_destroy(mxs_dpop *e);
 
+/* ---- GDBA (pydcop/algorithms/gdba.py) on the same flat arrays: the breakout algorithm -------------
+ * One round = the two phases of GdbaComputation for every variable: ok (:352-387: the modified cost
+ * of every value, the improvement, the violated constraints) and improve (:493-541: the move of a
+ * neighbourhood's winner by name, or the increase of the violated constraints' modifiers where
+ * nobody can improve).  The reference has no stop condition: the caller counts rounds.
+ * modifier: 0 = A (cost + m, base 0), 1 = M (cost * m, base 1); violation: 0 = NZ, 1 = NM, 2 = MX, on
+ * the raw table entry; increase_mode: 0 = E, 1 = R, 2 = C, 3 = T.  Modifiers are private to a SLOT
+ * (variable v, its k-th constraint: slot = var_rowptr[v] + k) and are integer counters.  As in the
+ * reference, an increase of E, R or C is written under the assignment of ALL of v's neighbours and
+ * read under the constraint's scope: it has an effect only where the scope is {v} + neighbours(v);
+ * only those slots store a table (in the layout of the constraint's table), mode T stores one counter
+ * per slot.  Counters are 16 bits wide, a counter grows by at most 1 per round: _run refuses to go
+ * past 65535 rounds.  `pool_budget_bytes`: the most the stored modifiers may take (0: 4 GiB); an
+ * instance past it is refused before anything is allocated.  `name_rank` as for MGM, `value_rank`
+ * as mxs_mgm_set_value_rank (both may be NULL).  The two draws of the reference's unseeded `random`
+ * (start value, one of the best values) come from the keyed generator of DSA (seed, variable, round,
+ * draw 6 / 7) over domain order.  Variable costs enter every evaluation as the reference adds them
+ * (inside the constraint loop, cumulatively, summed in ascending variable index).  Tables and
+ * variable costs must be finite. */
+typedef struct mxs_gdba mxs_gdba;
+int mxs_gdba_create(const mxs_graph *g, const mxs_params *p, const int32_t *name_rank, const int32_t *value_rank,
+                    int32_t modifier, int32_t violation, int32_t increase_mode, uint64_t seed,
+                    int64_t pool_budget_bytes, int32_t device, mxs_gdba **out);
+int mxs_gdba_reset(mxs_gdba *e);
+int mxs_gdba_run(mxs_gdba *e, int32_t n_rounds);
+int mxs_gdba_rounds(const mxs_gdba *e, int64_t *rounds);
+/* current value index, the cost the computation holds (has_cost = 0: still None before round 1), its
+ * last improvement and the value it would move to */
+int mxs_gdba_get_state(mxs_gdba *e, int32_t *idx, double *cost, uint8_t *has_cost, double *improve,
+                       int32_t *new_value);
+/* *n_entries = the number of modifiers stored for `slot` (0: none, no look-up can reach them); with
+ * `out` (capacity >= that number) they are copied, base included.  slot = -1: *n_entries = the bytes
+ * of the whole pool. */
+int mxs_gdba_get_modifiers(mxs_gdba *e, int32_t slot, int32_t *out, int64_t capacity, int64_t *n_entries);
+int mxs_gdba_eval_cost(mxs_gdba *e, const int32_t *idx, double infinity, double *cost, int64_t *violations);
+int mxs_gdba_destroy(mxs_gdba *e);
+
 /* Library/ABI version (major*100+minor). */
 int32_t mxs_version(void);
 

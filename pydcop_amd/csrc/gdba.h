@@ -1,0 +1,652 @@
+// gdba.h -- the reference's GDBA (pydcop/algorithms/gdba.py: Okamoto, Zivan, Nahon 2016) on gfx950, #included at
+// the end of mgm.hip (one translation unit for the gfx950 library and for the serial emulated build of
+// tests/emu).  The semantics restated here expression by expression, quirks included, are listed with the
+// reference's line numbers in tests/gdba_oracle.py, which this file follows bit for bit.
+//
+// Both phases of GdbaComputation wait for all neighbours and park early messages, so a round is
+// bulk-synchronous: two launches per round, each reading what the previous one wrote.
+//   k_gdba_eval    the modified cost of every value in the reference's constraint order (compute_eval_value,
+//                  :428-461), the cost and the violated constraints at the current value, the best values, the
+//                  improvement and the keyed choice of the new value                      (ok phase, :352-387)
+//   k_gdba_decide  maxi / max_list over the neighbourhood by name rank, the move -- or, where nobody can
+//                  improve, the increase of the violated constraints' modifiers      (improve phase, :493-541)
+// The modifiers are the new traffic: one table per (variable, constraint) SLOT, integer counters above a base of
+// 0 (`modifier: A`, cost + m) or 1 (`M`, cost * m).  The reference looks a modifier up under the assignment
+// filtered to the constraint's scope but, in modes E, R and C, writes it under the assignment of ALL neighbours:
+// an increase is read back only where the scope is {v} + neighbours(v).  The host plan marks those slots LIVE and
+// stores tables (in the layout of the constraint's table) for them alone; mode T adds 1 to every entry of the
+// constraint's own table, always live: one counter per slot.  The increase runs a wave at a time: the lanes of a
+// wave take the entries of one stuck variable's row (R) or slab (C) side by side.
+// Counters are 16 bits wide: a counter grows by at most 1 per round, and run() refuses to go past 65535 rounds.
+#pragma once
+
+namespace gdba {
+
+using mgm::Buf;
+using mgm::fail;
+using mgm2::uniform;
+
+constexpr int TPB = 64;  // one wave per block, as mgm2.h: 100k variables spread over every CU
+constexpr int64_t MAX_ROUNDS = 65535;
+constexpr int64_t DEFAULT_POOL_BUDGET = (int64_t)4 << 30;
+// draw ids, after those of DSA (0..2) and MGM-2 (0..5): 6 start value (cycle 0), 7 one of the best values
+enum { D_START = 6, D_BEST = 7 };
+enum { MOD_A = 0, MOD_M = 1 };
+enum { VIO_NZ = 0, VIO_NM = 1, VIO_MX = 2 };
+enum { INC_E = 0, INC_R = 1, INC_C = 2, INC_T = 3 };
+
+typedef uint16_t counter_t;
+
+template <typename T>
+struct alignas(8) Rec {  // what the ok phase leaves for the improve phase
+    T improve;           // _my_improve
+    int32_t newv;        // _new_value
+};
+
+template <typename T>
+struct Dev {
+    int32_t n_vars, is_max, modifier, violation, increase_mode, has_var_cost;
+    uint64_t seed;
+    int64_t round;                  // the reference's cycle_count during the round (1, 2, ...)
+    const int32_t *dom, *var_rowptr, *has_nb, *rank;
+    const T* tables;
+    const T* vref;                  // [n_slots] what a raw entry is compared with: 0 (NZ), the table's min (NM), max (MX)
+    const int64_t* mod_off;         // [n_slots] the slot's counters in the pool, -1: none stored (dead in E, R, C)
+    counter_t* pool;
+    const int32_t* conc_first;      // per entry of conc_var: the first slot (position in v's list) that holds it
+    const int64_t* cost_off;
+    const T* var_cost;
+    lsearch::Slots slots;           // base, stride_v, nb_rowptr / nb_var / nb_stride, conc_rowptr / conc_var
+    int32_t* cur;
+    T* cost;                        // __cost__
+    uint8_t* has_cost;
+    Rec<T>* rec;
+    uint8_t* viol;                  // [n_slots] violated at the current value (round r's ok phase)
+    T* slot_vc;                     // [n_slots] vars_cost after the slot, this round (written and read by the owner only)
+};
+
+// the offset the OTHER scope variables' current values contribute to the slot's table index
+template <typename T>
+__device__ inline int64_t others_offset(const Dev<T>& g, int s) {
+    int64_t off = 0;
+    for (int k = g.slots.nb_rowptr[s]; k < g.slots.nb_rowptr[s + 1]; ++k)
+        off += (int64_t)g.cur[g.slots.nb_var[k]] * g.slots.nb_stride[k];
+    return off;
+}
+
+// vars_cost after slot position `pos` of v (:443-459): cost_for_val, from 0, of the owner and of every variable
+// of the constraints seen so far, each at its current value, in ascending index
+template <typename T>
+__device__ inline T vars_cost(const Dev<T>& g, int v, int pos) {
+    T acc = (T)0;
+    for (int k = g.slots.conc_rowptr[v]; k < g.slots.conc_rowptr[v + 1]; ++k)
+        if (g.conc_first[k] <= pos) {
+            const int u = g.slots.conc_var[k];
+            acc += g.var_cost[g.cost_off[u] + g.cur[u]];
+        }
+    return acc;
+}
+
+// compute_eval_value(x): from 0, over v's constraints in order, += eff_cost, += vars_cost.  mark: also write
+// the violated bit of every slot (the caller passes the current value)
+template <typename T>
+__device__ inline T eval_at(const Dev<T>& g, int v, int x, bool mark) {
+    T acc = (T)0;
+    const int s0 = g.var_rowptr[v], s1 = g.var_rowptr[v + 1];
+    for (int s = s0; s < s1; ++s) {
+        const int64_t idx = (int64_t)x * g.slots.stride_v[s] + others_offset(g, s);
+        const T tv = g.tables[g.slots.base[s] + idx];
+        const int64_t mo = g.mod_off[s];
+        int m = g.modifier;  // the base: 0 (A), 1 (M)
+        if (mo >= 0) m += (int)g.pool[g.increase_mode == INC_T ? mo : mo + idx];
+        acc += g.modifier == MOD_M ? tv * (T)m : tv + (T)m;
+        if (g.has_var_cost) acc += g.slot_vc[s];
+        if (mark) g.viol[s] = g.violation == VIO_MX ? tv == g.vref[s] : tv != g.vref[s];
+    }
+    return acc;
+}
+
+template <typename T>
+__global__ void __launch_bounds__(TPB) k_gdba_eval(Dev<T> g) {
+    const int v = blockIdx.x * blockDim.x + threadIdx.x;
+    if (v >= g.n_vars || !g.has_nb[v]) return;
+    const int D = g.dom[v], cv = g.cur[v];
+    // vars_cost does not depend on the candidate value: once per slot and round, not once per (value, slot)
+    if (g.has_var_cost)
+        for (int s = g.var_rowptr[v]; s < g.var_rowptr[v + 1]; ++s) g.slot_vc[s] = vars_cost(g, v, s - g.var_rowptr[v]);
+    const T cost = eval_at(g, v, cv, true);
+    // _compute_best_improvement: strictly better starts a new list, equal joins it (domain order)
+    T best = (T)0;
+    int n_best = 0;
+    for (int x = 0; x < D; ++x) {
+        const T c = x == cv ? cost : eval_at(g, v, x, false);
+        if (n_best == 0 || (g.is_max ? c > best : c < best)) {
+            best = c;
+            n_best = 1;
+        } else if (c == best) {
+            ++n_best;
+        }
+    }
+    Rec<T> r;
+    r.improve = cost - best;
+    r.newv = cv;
+    if (g.is_max ? r.improve < (T)0 : r.improve > (T)0) {
+        int k = (int)(uniform(g.seed, v, g.round, D_BEST) * n_best);
+        for (int x = 0; x < D; ++x) {
+            const T c = x == cv ? cost : eval_at(g, v, x, false);
+            if (c == best && k-- == 0) {
+                r.newv = x;
+                break;
+            }
+        }
+    }
+    g.cost[v] = cost;
+    g.has_cost[v] = 1;
+    g.rec[v] = r;
+}
+
+// _increase_cost of every violated constraint of variable w (at value cw), by the 64 lanes of a wave together.
+// Every lane reads the same slot records (one broadcast request each); the entries are spread over the lanes.
+template <typename T>
+__device__ inline void increase_violated(const Dev<T>& g, int w, int cw, int lane) {
+    const int Dw = g.dom[w];
+    for (int s = g.var_rowptr[w]; s < g.var_rowptr[w + 1]; ++s) {
+        if (!g.viol[s]) continue;
+        const int64_t mo = g.mod_off[s];
+        if (mo < 0) continue;  // no look-up ever reads what the reference writes here
+        if (g.increase_mode == INC_T) {
+            if (lane == 0) g.pool[mo] = (counter_t)(g.pool[mo] + 1);
+            continue;
+        }
+        const int64_t sv = g.slots.stride_v[s];
+        if (g.increase_mode == INC_E) {
+            const int64_t i = mo + (int64_t)cw * sv + others_offset(g, s);
+            if (lane == 0) g.pool[i] = (counter_t)(g.pool[i] + 1);
+        } else if (g.increase_mode == INC_R) {  // every value of w, the neighbours as they are: one strided row
+            const int64_t b = mo + others_offset(g, s);
+            for (int x = lane; x < Dw; x += 64) g.pool[b + x * sv] = (counter_t)(g.pool[b + x * sv] + 1);
+        } else {  // C: every assignment of the neighbours, w as it is: a slab of size / D_w entries
+            const int k0 = g.slots.nb_rowptr[s], k1 = g.slots.nb_rowptr[s + 1];
+            int64_t n = 1;
+            for (int k = k0; k < k1; ++k) n *= g.dom[g.slots.nb_var[k]];
+            const int64_t b = mo + (int64_t)cw * sv;
+            for (int64_t e = lane; e < n; e += 64) {
+                int64_t rest = e, i = b;
+                for (int k = k0; k < k1; ++k) {
+                    const int d = g.dom[g.slots.nb_var[k]];
+                    i += (rest % d) * g.slots.nb_stride[k];
+                    rest /= d;
+                }
+                g.pool[i] = (counter_t)(g.pool[i] + 1);
+            }
+        }
+    }
+}
+
+template <typename T>
+__global__ void __launch_bounds__(TPB) k_gdba_decide(Dev<T> g) {
+    const int v = blockIdx.x * blockDim.x + threadIdx.x;
+    const int lane = threadIdx.x & 63;
+    const bool plays = v < g.n_vars && g.has_nb[v];
+    bool stuck = false;
+    int cv = 0;
+    if (plays) {
+        const Rec<T> me = g.rec[v];
+        cv = g.cur[v];
+        // maxi and max_list with > and == in both modes (:506-513); sorted(max_list)[0] is v's own name iff no
+        // neighbour improves more and none that improves as much has a smaller name
+        const int myrank = g.rank[v];
+        T maxi = me.improve;
+        bool wins = true;
+        for (int k = g.slots.conc_rowptr[v]; k < g.slots.conc_rowptr[v + 1]; ++k) {
+            const int u = g.slots.conc_var[k];
+            if (u == v) continue;
+            const T gu = g.rec[u].improve;
+            if (gu > maxi) {
+                maxi = gu;
+                wins = false;
+            } else if (gu == maxi && g.rank[u] < myrank) {
+                wins = false;
+            }
+        }
+        if (g.is_max ? me.improve < (T)0 : me.improve > (T)0) {
+            if (wins) {  // value_selection(_new_value, current_cost + _my_improve), as written (:521-523)
+                g.cur[v] = me.newv;
+                g.cost[v] = g.cost[v] + me.improve;
+            }
+        } else if (maxi == (T)0) {
+            stuck = true;
+        }
+    }
+    // A stuck variable's neighbours improve by at most 0 where they would need more (min) or improve less than
+    // it where the least improving one moves (max): none of them moves this round, so the values read below are
+    // those of the round's ok phase, as in the reference.
+    unsigned long long todo = __ballot(stuck);
+    while (todo) {
+        const int src = __builtin_ctzll(todo);
+        todo &= todo - 1;
+        const int w = __shfl(v, src, 64), cw = __shfl(cv, src, 64);
+        increase_violated(g, w, cw, lane);
+    }
+}
+
+// The host plan of the modifier pool: which slots are live, where their counters start, how many there are
+struct Plan {
+    std::vector<int64_t> mod_off, size;  // per slot: offset (-1: none) and number of counters
+    int64_t entries = 0;
+    void build(int increase_mode, const std::vector<int32_t>& dom, const std::vector<int32_t>& vrow,
+               const std::vector<int32_t>& has_nb, const lsearch::HostSlots& hs) {
+        const int nV = (int)dom.size();
+        const size_t nS = hs.base.size();
+        mod_off.assign(nS, -1);
+        size.assign(nS, 0);
+        entries = 0;
+        std::vector<int32_t> seen;
+        for (int v = 0; v < nV; ++v) {
+            if (!has_nb[v]) continue;  // never plays
+            const int n_conc = hs.conc_rowptr[v + 1] - hs.conc_rowptr[v];
+            for (int s = vrow[v]; s < vrow[v + 1]; ++s) {
+                int64_t n = 1;
+                if (increase_mode != INC_T) {  // live: the scope is {v} + every neighbour of v
+                    seen.assign(hs.nb_var.begin() + hs.nb_rowptr[s], hs.nb_var.begin() + hs.nb_rowptr[s + 1]);
+                    std::sort(seen.begin(), seen.end());
+                    seen.erase(std::unique(seen.begin(), seen.end()), seen.end());
+                    if ((int)seen.size() != n_conc - 1) continue;
+                    // the size of the constraint's table (v may hold several positions of the scope)
+                    n = (int64_t)hs.stride_v[s] * (dom[v] - 1) + 1;
+                    for (int k = hs.nb_rowptr[s]; k < hs.nb_rowptr[s + 1]; ++k)
+                        n += (int64_t)hs.nb_stride[k] * (dom[hs.nb_var[k]] - 1);
+                }
+                mod_off[s] = entries;
+                size[s] = n;
+                entries += n;
+            }
+        }
+    }
+};
+
+struct Base {
+    virtual ~Base() = default;
+    virtual int init(const mxs_graph& g, const mxs_params& p, const int32_t* rank, const int32_t* vrank, int32_t modifier,
+                     int32_t violation, int32_t increase_mode, uint64_t seed, int64_t budget, int device) = 0;
+    virtual int reset() = 0;
+    virtual int run(int32_t n) = 0;
+    virtual int get_state(int32_t* idx, double* cost, uint8_t* has_cost, double* improve, int32_t* newv) = 0;
+    virtual int get_modifiers(int32_t slot, int32_t* out, int64_t capacity, int64_t* n) = 0;
+    virtual int eval_cost(const int32_t* idx, double infinity, double* cost, int64_t* viol) = 0;
+    int64_t rounds = 0;
+};
+
+template <typename T>
+struct Engine : Base {
+    int device = 0;
+    hipStream_t stream = nullptr;
+    Dev<T> g{};
+    Plan plan;
+    std::vector<int32_t> h_dom, h_frow, h_evar, h_init, h_nb, h_vrow, h_vrank;
+    std::vector<int64_t> h_toff, h_coff;
+    std::vector<double> h_tables, h_eval_cost, h_var_cost;
+    lsearch::HostSlots hs;
+    Buf<int32_t> dom, var_rowptr, has_nb, rank, conc_first, cur;
+    Buf<int64_t> sl_base, mod_off, cost_off;
+    Buf<int32_t> sl_stride_v, sl_nb_rowptr, sl_nb_var, sl_nb_stride, sl_conc_rowptr, sl_conc_var;
+    Buf<T> tables, vref, var_cost, cost, slot_vc;
+    Buf<counter_t> pool;
+    Buf<uint8_t> has_cost, viol;
+    Buf<Rec<T>> rec;
+
+    ~Engine() override {
+        if (stream) (void)hipStreamDestroy(stream);
+    }
+
+    int init(const mxs_graph& G, const mxs_params& p, const int32_t* rk, const int32_t* vrk, int32_t modifier,
+             int32_t violation, int32_t increase_mode, uint64_t seed, int64_t budget, int dev) override {
+        device = dev;
+        int count = 0;
+        if (hipGetDeviceCount(&count) != hipSuccess || count <= 0)
+            return fail(MXS_E_NODEVICE, "no HIP device visible: the engine has no CPU fallback");
+        if (dev < 0 || dev >= count) return fail(MXS_E_INVALID, "device index out of range");
+        if (modifier < 0 || modifier > 1) return fail(MXS_E_INVALID, "gdba: modifier must be 0 (A) or 1 (M)");
+        if (violation < 0 || violation > 2) return fail(MXS_E_INVALID, "gdba: violation must be 0 (NZ), 1 (NM) or 2 (MX)");
+        if (increase_mode < 0 || increase_mode > 3)
+            return fail(MXS_E_INVALID, "gdba: increase_mode must be 0 (E), 1 (R), 2 (C) or 3 (T)");
+        if (budget < 0) return fail(MXS_E_INVALID, "gdba: negative pool budget");
+        if (budget == 0) budget = DEFAULT_POOL_BUDGET;
+        MGM_TRY(hipSetDevice(dev));
+        MGM_TRY(hipStreamCreateWithFlags(&stream, 0));
+        const int nV = G.n_vars, nF = G.n_factors, nE = G.n_edges;
+        if (nV < 0 || nF < 0 || nE < 0) return fail(MXS_E_INVALID, "negative size");
+        if (p.mode != MXS_MODE_MIN && p.mode != MXS_MODE_MAX) return fail(MXS_E_INVALID, "invalid mode");
+        h_dom.assign(G.dom_size, G.dom_size + nV);
+        h_frow.assign(G.factor_rowptr, G.factor_rowptr + nF + 1);
+        h_evar.assign(G.edge_var, G.edge_var + nE);
+        h_toff.assign(G.table_off, G.table_off + nF + 1);
+        h_coff.assign(nV + 1, 0);
+        for (int v = 0; v < nV; ++v) {
+            if (h_dom[v] < 1) return fail(MXS_E_INVALID, "empty domain");
+            h_coff[v + 1] = h_coff[v] + h_dom[v];
+        }
+        for (int f = 0; f < nF; ++f) {
+            if (h_frow[f + 1] <= h_frow[f]) return fail(MXS_E_INVALID, "factor without variable");
+            if (h_toff[f + 1] <= h_toff[f]) return fail(MXS_E_INVALID, "empty table");
+            for (int e = h_frow[f]; e < h_frow[f + 1]; ++e)
+                if (h_evar[e] < 0 || h_evar[e] >= nV) return fail(MXS_E_INVALID, "edge_var out of range");
+        }
+        h_vrow.assign(G.var_rowptr, G.var_rowptr + nV + 1);
+        std::vector<int32_t> vedges(G.var_edges, G.var_edges + nE);
+        h_tables.assign(G.tables, G.tables + h_toff[nF]);
+        // maxi over NaN improvements depends on message arrival in the reference: no defined result
+        for (double t : h_tables)
+            if (!std::isfinite(t)) return fail(MXS_E_INVALID, "gdba: constraint tables must be finite (no inf / NaN entries)");
+        h_var_cost.assign(G.var_cost, G.var_cost + h_coff[nV]);
+        bool any_vc = false;
+        for (double c : h_var_cost) {
+            if (!std::isfinite(c)) return fail(MXS_E_INVALID, "gdba: variable costs must be finite (no inf / NaN entries)");
+            any_vc |= c != 0.0;
+        }
+        const double* ev = G.eval_var_cost ? G.eval_var_cost : G.var_cost;
+        h_eval_cost.assign(ev, ev + h_coff[nV]);
+        if (vrk) h_vrank.assign(vrk, vrk + h_coff[nV]);
+        h_init.assign(nV, -1);
+        if (G.init_idx)
+            for (int v = 0; v < nV; ++v) {
+                if (G.init_idx[v] >= h_dom[v]) return fail(MXS_E_INVALID, "init_idx out of the domain");
+                h_init[v] = G.init_idx[v];
+            }
+        const std::string bad = hs.build(nV, nF, h_dom, h_frow, h_evar, h_toff, h_vrow, vedges);
+        if (!bad.empty()) return fail(MXS_E_INVALID, bad);
+        // neighbours: the other variables of v's constraints (the concerned list holds v itself once); the
+        // first slot of v's list that holds each concerned variable (v itself: slot 0, every scope holds it)
+        h_nb.assign(nV, 0);
+        std::vector<int32_t> h_first(hs.conc_var.size(), 0);
+        for (int v = 0; v < nV; ++v) {
+            const int c0 = hs.conc_rowptr[v], c1 = hs.conc_rowptr[v + 1];
+            h_nb[v] = c1 - c0 > 1;
+            for (int k = c0; k < c1; ++k) {
+                const int u = hs.conc_var[k];
+                int first = 0;
+                if (u != v)
+                    for (int s = h_vrow[v]; s < h_vrow[v + 1]; ++s) {
+                        bool in = false;
+                        for (int q = hs.nb_rowptr[s]; q < hs.nb_rowptr[s + 1]; ++q) in |= hs.nb_var[q] == u;
+                        if (in) {
+                            first = s - h_vrow[v];
+                            break;
+                        }
+                    }
+                h_first[k] = first;
+            }
+        }
+        // the plan of the modifier pool, checked against the budget before anything is allocated
+        plan.build(increase_mode, h_dom, h_vrow, h_nb, hs);
+        if (plan.entries > budget / (int64_t)sizeof(counter_t))
+            return fail(MXS_E_INVALID, "gdba: the modifier tables take " + std::to_string(plan.entries * (int64_t)sizeof(counter_t)) +
+                                           " bytes, more than the budget of " + std::to_string(budget));
+        // what a raw entry is compared with (_is_violated, :552-572): min / max over the flattened table
+        std::vector<T> h_vref(hs.base.size(), (T)0);
+        if (violation != VIO_NZ) {
+            std::vector<T> fref(nF);
+            for (int f = 0; f < nF; ++f) {
+                T r = (T)h_tables[h_toff[f]];
+                for (int64_t i = h_toff[f]; i < h_toff[f + 1]; ++i) {
+                    const T t = (T)h_tables[i];
+                    if (violation == VIO_NM ? t < r : t > r) r = t;
+                }
+                fref[f] = r;
+            }
+            std::vector<int32_t> efac(nE);
+            for (int f = 0; f < nF; ++f)
+                for (int e = h_frow[f]; e < h_frow[f + 1]; ++e) efac[e] = f;
+            for (size_t s = 0; s < h_vref.size(); ++s) h_vref[s] = fref[efac[vedges[s]]];
+        }
+        std::vector<int32_t> h_rank(nV);
+        for (int v = 0; v < nV; ++v) h_rank[v] = rk ? rk[v] : v;
+        std::vector<T> tt(h_tables.size()), vc(h_var_cost.size());
+        for (size_t i = 0; i < tt.size(); ++i) tt[i] = (T)h_tables[i];
+        for (size_t i = 0; i < vc.size(); ++i) vc[i] = (T)h_var_cost[i];
+        MGM_TRY(sl_base.upload(hs.base, stream));
+        MGM_TRY(sl_stride_v.upload(hs.stride_v, stream));
+        MGM_TRY(sl_nb_rowptr.upload(hs.nb_rowptr, stream));
+        MGM_TRY(sl_nb_var.upload(hs.nb_var, stream));
+        MGM_TRY(sl_nb_stride.upload(hs.nb_stride, stream));
+        MGM_TRY(sl_conc_rowptr.upload(hs.conc_rowptr, stream));
+        MGM_TRY(sl_conc_var.upload(hs.conc_var, stream));
+        MGM_TRY(conc_first.upload(h_first, stream));
+        MGM_TRY(dom.upload(h_dom, stream));
+        MGM_TRY(var_rowptr.upload(h_vrow, stream));
+        MGM_TRY(has_nb.upload(h_nb, stream));
+        MGM_TRY(rank.upload(h_rank, stream));
+        MGM_TRY(tables.upload(tt, stream));
+        MGM_TRY(vref.upload(h_vref, stream));
+        MGM_TRY(var_cost.upload(vc, stream));
+        MGM_TRY(cost_off.upload(h_coff, stream));
+        MGM_TRY(mod_off.upload(plan.mod_off, stream));
+        MGM_TRY(pool.alloc((size_t)plan.entries));
+        MGM_TRY(cur.alloc(nV));
+        MGM_TRY(cost.alloc(nV));
+        MGM_TRY(has_cost.alloc(nV));
+        MGM_TRY(rec.alloc(nV));
+        MGM_TRY(viol.alloc(hs.base.size()));
+        MGM_TRY(slot_vc.alloc(any_vc ? hs.base.size() : 0));
+        g.slots = lsearch::Slots{sl_base.p, sl_stride_v.p, sl_nb_rowptr.p, sl_nb_var.p, sl_nb_stride.p, nullptr, nullptr,
+                                 sl_conc_rowptr.p, sl_conc_var.p, nullptr, nullptr, nullptr, nullptr, 0};
+        g.n_vars = nV;
+        g.is_max = p.mode == MXS_MODE_MAX;
+        g.modifier = modifier;
+        g.violation = violation;
+        g.increase_mode = increase_mode;
+        g.has_var_cost = any_vc;
+        g.seed = seed;
+        g.dom = dom.p;
+        g.var_rowptr = var_rowptr.p;
+        g.has_nb = has_nb.p;
+        g.rank = rank.p;
+        g.tables = tables.p;
+        g.vref = vref.p;
+        g.mod_off = mod_off.p;
+        g.pool = pool.p;
+        g.conc_first = conc_first.p;
+        g.cost_off = cost_off.p;
+        g.var_cost = var_cost.p;
+        g.cur = cur.p;
+        g.cost = cost.p;
+        g.has_cost = has_cost.p;
+        g.rec = rec.p;
+        g.viol = viol.p;
+        g.slot_vc = slot_vc.p;
+        return reset();
+    }
+
+    // on_start (:302-333): a variable with neighbours takes its initial value or a random one (held cost None);
+    // one without takes optimal_cost_value (min / max over (cost, value) tuples, relations.py:1661-1665)
+    int reset() override {
+        MGM_TRY(hipSetDevice(device));
+        const int nV = g.n_vars;
+        std::vector<int32_t> c0(nV);
+        std::vector<T> k0(nV, (T)0);
+        std::vector<uint8_t> h0(nV, 0);
+        std::vector<Rec<T>> r0(nV);
+        for (int v = 0; v < nV; ++v) {
+            if (h_nb[v]) {
+                c0[v] = h_init[v] >= 0 ? h_init[v] : (int)(uniform(g.seed, v, 0, D_START) * h_dom[v]);
+            } else {
+                const int32_t* rk = h_vrank.empty() ? nullptr : h_vrank.data() + h_coff[v];
+                int best = 0;
+                for (int d = 1; d < h_dom[v]; ++d) {
+                    const T a = (T)h_var_cost[h_coff[v] + d], b = (T)h_var_cost[h_coff[v] + best];
+                    const int rd = rk ? rk[d] : d, rb = rk ? rk[best] : best;
+                    if (g.is_max ? (a > b || (a == b && rd > rb)) : (a < b || (a == b && rd < rb))) best = d;
+                }
+                c0[v] = best;
+                k0[v] = (T)h_var_cost[h_coff[v] + best];
+                h0[v] = 1;
+            }
+            r0[v].improve = (T)0;
+            r0[v].newv = c0[v];
+        }
+        if (nV) {
+            MGM_TRY(hipMemcpyAsync(cur.p, c0.data(), 4 * (size_t)nV, hipMemcpyHostToDevice, stream));
+            MGM_TRY(hipMemcpyAsync(cost.p, k0.data(), sizeof(T) * nV, hipMemcpyHostToDevice, stream));
+            MGM_TRY(hipMemcpyAsync(has_cost.p, h0.data(), nV, hipMemcpyHostToDevice, stream));
+            MGM_TRY(hipMemcpyAsync(rec.p, r0.data(), sizeof(Rec<T>) * nV, hipMemcpyHostToDevice, stream));
+        }
+        if (plan.entries) MGM_TRY(hipMemsetAsync(pool.p, 0, sizeof(counter_t) * (size_t)plan.entries, stream));
+        if (!hs.base.empty()) MGM_TRY(hipMemsetAsync(viol.p, 0, hs.base.size(), stream));
+        MGM_TRY(hipStreamSynchronize(stream));
+        rounds = 0;
+        return MXS_OK;
+    }
+
+    int run(int32_t n) override {
+        MGM_TRY(hipSetDevice(device));
+        if (rounds + (int64_t)n > MAX_ROUNDS)
+            return fail(MXS_E_INVALID, "gdba: the modifier counters are 16 bits wide, at most 65535 rounds");
+        const int nV = g.n_vars;
+        if (nV == 0) {
+            rounds += n;
+            return MXS_OK;
+        }
+        const dim3 grid((unsigned)((nV + TPB - 1) / TPB)), block(TPB);
+        for (int32_t r = 0; r < n; ++r) {
+            g.round = rounds + 1;
+            hipLaunchKernelGGL((k_gdba_eval<T>), grid, block, 0, stream, g);
+            MGM_TRY(hipGetLastError());
+            hipLaunchKernelGGL((k_gdba_decide<T>), grid, block, 0, stream, g);
+            MGM_TRY(hipGetLastError());
+            rounds += 1;
+        }
+        MGM_TRY(hipStreamSynchronize(stream));
+        return MXS_OK;
+    }
+
+    int get_state(int32_t* idx, double* cst, uint8_t* has, double* imp, int32_t* nv) override {
+        MGM_TRY(hipSetDevice(device));
+        const int nV = g.n_vars;
+        if (!nV) return MXS_OK;
+        std::vector<T> hc(nV);
+        std::vector<int32_t> hi(nV);
+        std::vector<uint8_t> hh(nV);
+        std::vector<Rec<T>> hr(nV);
+        MGM_TRY(hipMemcpyAsync(hi.data(), cur.p, 4 * (size_t)nV, hipMemcpyDeviceToHost, stream));
+        MGM_TRY(hipMemcpyAsync(hh.data(), has_cost.p, nV, hipMemcpyDeviceToHost, stream));
+        MGM_TRY(hipMemcpyAsync(hc.data(), cost.p, sizeof(T) * nV, hipMemcpyDeviceToHost, stream));
+        MGM_TRY(hipMemcpyAsync(hr.data(), rec.p, sizeof(Rec<T>) * nV, hipMemcpyDeviceToHost, stream));
+        MGM_TRY(hipStreamSynchronize(stream));
+        for (int v = 0; v < nV; ++v) {
+            if (idx) idx[v] = hi[v];
+            if (has) has[v] = hh[v];
+            if (cst) cst[v] = (double)hc[v];
+            if (imp) imp[v] = (double)hr[v].improve;
+            if (nv) nv[v] = hr[v].newv;
+        }
+        return MXS_OK;
+    }
+
+    // slot -1: *n = the bytes of the whole pool.  Otherwise *n = the number of modifiers stored for the slot (0:
+    // none); with `out`, they are copied (base + counter) -- capacity must hold them
+    int get_modifiers(int32_t slot, int32_t* out, int64_t capacity, int64_t* n) override {
+        if (slot == -1) {
+            if (n) *n = plan.entries * (int64_t)sizeof(counter_t);
+            return MXS_OK;
+        }
+        if (slot < 0 || (size_t)slot >= plan.size.size()) return fail(MXS_E_INVALID, "gdba: slot out of range");
+        const int64_t cnt = plan.size[slot];
+        if (n) *n = cnt;
+        if (!out || cnt == 0) return MXS_OK;
+        if (capacity < cnt) return fail(MXS_E_INVALID, "gdba: buffer too small for the slot's modifiers");
+        MGM_TRY(hipSetDevice(device));
+        std::vector<counter_t> h((size_t)cnt);
+        MGM_TRY(hipMemcpyAsync(h.data(), pool.p + plan.mod_off[slot], sizeof(counter_t) * (size_t)cnt, hipMemcpyDeviceToHost, stream));
+        MGM_TRY(hipStreamSynchronize(stream));
+        for (int64_t i = 0; i < cnt; ++i) out[i] = g.modifier + (int32_t)h[(size_t)i];
+        return MXS_OK;
+    }
+
+    // DCOP.solution_cost of an assignment (constraints and the variables' own costs)
+    int eval_cost(const int32_t* idx, double infinity, double* cst, int64_t* viol_out) override {
+        std::vector<int32_t> c;
+        if (!idx) {
+            c.resize(g.n_vars);
+            int rc = get_state(c.data(), nullptr, nullptr, nullptr, nullptr);
+            if (rc) return rc;
+            idx = c.data();
+        }
+        double soft = 0;
+        int64_t hard = 0;
+        const int nF = (int)h_frow.size() - 1;
+        for (int f = 0; f < nF; ++f) {
+            int64_t lin = 0;
+            for (int e = h_frow[f]; e < h_frow[f + 1]; ++e) {
+                const int v = h_evar[e];
+                if (idx[v] < 0 || idx[v] >= h_dom[v]) return fail(MXS_E_INVALID, "assignment index out of the domain");
+                lin = lin * h_dom[v] + idx[v];
+            }
+            const double r = h_tables[h_toff[f] + lin];
+            if (r != infinity) soft += r; else hard += 1;
+        }
+        for (int v = 0; v < g.n_vars; ++v) {
+            const double x = h_eval_cost[h_coff[v] + idx[v]];
+            if (x != infinity) soft += x; else hard += 1;
+        }
+        if (cst) *cst = soft;
+        if (viol_out) *viol_out = hard;
+        return MXS_OK;
+    }
+};
+
+}  // namespace gdba
+
+struct mxs_gdba {
+    gdba::Base* impl;
+};
+
+extern "C" {
+
+int mxs_gdba_create(const mxs_graph* g, const mxs_params* p, const int32_t* name_rank, const int32_t* value_rank,
+                    int32_t modifier, int32_t violation, int32_t increase_mode, uint64_t seed, int64_t pool_budget_bytes,
+                    int32_t device, mxs_gdba** out) {
+    if (!g || !p || !out) return mgm::fail(MXS_E_INVALID, "null argument");
+    *out = nullptr;
+    try {
+        gdba::Base* impl = p->dtype == MXS_DTYPE_F32 ? (gdba::Base*)new gdba::Engine<float>()
+                                                     : (gdba::Base*)new gdba::Engine<double>();
+        int rc = impl->init(*g, *p, name_rank, value_rank, modifier, violation, increase_mode, seed, pool_budget_bytes, device);
+        if (rc) {
+            delete impl;
+            return rc;
+        }
+        *out = new mxs_gdba{impl};
+        return MXS_OK;
+    } catch (const std::exception& ex) {
+        return mgm::fail(MXS_E_NOMEM, ex.what());
+    }
+}
+int mxs_gdba_reset(mxs_gdba* e) { return e ? e->impl->reset() : mgm::fail(MXS_E_INVALID, "null handle"); }
+int mxs_gdba_run(mxs_gdba* e, int32_t n_rounds) {
+    if (!e) return mgm::fail(MXS_E_INVALID, "null handle");
+    if (n_rounds < 0) return mgm::fail(MXS_E_INVALID, "negative round count");
+    return e->impl->run(n_rounds);
+}
+int mxs_gdba_rounds(const mxs_gdba* e, int64_t* rounds) {
+    if (!e) return mgm::fail(MXS_E_INVALID, "null handle");
+    if (rounds) *rounds = e->impl->rounds;
+    return MXS_OK;
+}
+int mxs_gdba_get_state(mxs_gdba* e, int32_t* idx, double* cost, uint8_t* has_cost, double* improve, int32_t* new_value) {
+    return e ? e->impl->get_state(idx, cost, has_cost, improve, new_value) : mgm::fail(MXS_E_INVALID, "null handle");
+}
+int mxs_gdba_get_modifiers(mxs_gdba* e, int32_t slot, int32_t* out, int64_t capacity, int64_t* n_entries) {
+    return e ? e->impl->get_modifiers(slot, out, capacity, n_entries) : mgm::fail(MXS_E_INVALID, "null handle");
+}
+int mxs_gdba_eval_cost(mxs_gdba* e, const int32_t* idx, double infinity, double* cost, int64_t* violations) {
+    return e ? e->impl->eval_cost(idx, infinity, cost, violations) : mgm::fail(MXS_E_INVALID, "null handle");
+}
+int mxs_gdba_destroy(mxs_gdba* e) {
+    if (e) {
+        delete e->impl;
+        delete e;
+    }
+    return MXS_OK;
+}
+
+}  // extern "C"

@@ -885,3 +885,6 @@ int mxs_mgm_destroy(mxs_mgm* e) {
 
 // DPOP (pydcop/algorithms/dpop.py): UTIL / VALUE over a pseudo-tree, tables in one flat pool
 #include "dpop.h"
+
+// GDBA (pydcop/algorithms/gdba.py): the two phases of MGM's round plus per-slot modifier tables
+#include "gdba.h"

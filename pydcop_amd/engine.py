@@ -53,6 +53,8 @@ ABI_SYMBOLS = (
     "mxs_dsa_eval_cost", "mxs_dsa_destroy",
     "mxs_dpop_create", "mxs_dpop_solve", "mxs_dpop_get_state", "mxs_dpop_eval_cost", "mxs_dpop_stats",
     "mxs_dpop_util_dims", "mxs_dpop_get_util", "mxs_dpop_destroy",
+    "mxs_gdba_create", "mxs_gdba_reset", "mxs_gdba_run", "mxs_gdba_rounds", "mxs_gdba_get_state",
+    "mxs_gdba_get_modifiers", "mxs_gdba_eval_cost", "mxs_gdba_destroy",
 )
 
 # ... and the MGM-2 entry points (kept apart: the header check of tests/test_abi.py reads names without digits)
@@ -200,6 +202,15 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
         "mxs_dpop_util_dims": ([vp, i32, vp, C.POINTER(i32)], C.c_int),
         "mxs_dpop_get_util": ([vp, i32, vp, i64], C.c_int),
         "mxs_dpop_destroy": ([vp], C.c_int),
+        "mxs_gdba_create": ([C.POINTER(CGraph), C.POINTER(CParams), vp, vp, i32, i32, i32, C.c_uint64, i64, i32,
+                             C.POINTER(vp)], C.c_int),
+        "mxs_gdba_reset": ([vp], C.c_int),
+        "mxs_gdba_run": ([vp, i32], C.c_int),
+        "mxs_gdba_rounds": ([vp, C.POINTER(i64)], C.c_int),
+        "mxs_gdba_get_state": ([vp, vp, vp, vp, vp, vp], C.c_int),
+        "mxs_gdba_get_modifiers": ([vp, i32, vp, i64, C.POINTER(i64)], C.c_int),
+        "mxs_gdba_eval_cost": ([vp, vp, C.c_double, C.POINTER(C.c_double), C.POINTER(i64)], C.c_int),
+        "mxs_gdba_destroy": ([vp], C.c_int),
         "mxs_cycle_bytes": ([vp, C.POINTER(i64), C.POINTER(i32)], C.c_int),
         "mxs_factor_order": ([vp, C.POINTER(i32)], C.c_int),
         "mxs_factor_kernels": ([vp, vp], C.c_int),

@@ -1,7 +1,7 @@
 """Cycles per second of the DSA, MGM and MGM-2 engines (pydcop_amd/csrc/dsa.hip, mgm.hip, mgm2.h) on the
 100k-variable colouring instance of the bench and on the meeting instance (24 values, arity 3):
 
-    python tools/local_search_bench.py [--cycles 500] [--mgm2-rounds 200]
+    python tools/local_search_bench.py [--cycles 500] [--mgm2-rounds 200] [--gdba-rounds 200]
 
 One JSON line per (algorithm, instance, kernels); "kernels": "packed" = the default (lane per
 constraint where the instance allows it, local_search.h), "slots" = the thread-per-variable
@@ -9,7 +9,10 @@ register-array kernels on the slot view (MAXSUM_LOCAL_SEARCH_GENERIC=2), "csr_wa
 kernels (=1), "strided" = the default kernels without the private row copies of the variables the pack
 cannot take (MAXSUM_LOCAL_SEARCH_ROWS=0: their D entries per constraint a stride apart, round 3).
 MGM-2 has one family of kernels ("kernels": "mgm2"), timed in f64 and f32 after the MGM / DSA rows of an
-instance; every timing ends with the engine's stream synchronised (run() returns after it).
+instance.  GDBA ("kernels": "gdba", pydcop_amd/csrc/gdba.h) follows, in f64 and f32, increase modes E and C (the
+heaviest mode with live tables): the median of three timed runs after a warm-up, next to an MGM row timed the same
+way in the same precision (both tagged "timing": "median3"; "ratio_to_mgm"), with the bytes the engine keeps on the device for the share of the HBM
+peak; every timing ends with the engine's stream synchronised (run() returns after it).
 """
 import argparse
 import json
@@ -21,6 +24,7 @@ sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."
 
 from pydcop_amd import generators as G  # noqa: E402
 from pydcop_amd.dsa import DsaEngine  # noqa: E402
+from pydcop_amd.gdba import GdbaEngine  # noqa: E402
 from pydcop_amd.graph import Params  # noqa: E402
 from pydcop_amd.mgm import MgmEngine  # noqa: E402
 from pydcop_amd.mgm2 import Mgm2Engine  # noqa: E402
@@ -33,6 +37,7 @@ def main():
     ap.add_argument("--instances", nargs="*", default=["coloring_100k", "meeting_50k"])
     ap.add_argument("--kernels", nargs="*", default=["packed", "strided", "slots", "csr_walk"])
     ap.add_argument("--mgm2-rounds", type=int, default=200, help="0: no MGM-2 rows")
+    ap.add_argument("--gdba-rounds", type=int, default=200, help="0: no GDBA rows")
     a = ap.parse_args()
     instances = [("coloring_100k", lambda: G.random_coloring(100_000, seed=0, names=False), Params()),
                  ("meeting_50k", lambda: G.meeting_like(50_000, dom=24, seed=0, names=False), Params(mode="max"))]
@@ -73,6 +78,39 @@ def main():
                               "us_per_cycle": round(1e6 * dt / a.mgm2_rounds, 2),
                               "cost": eng.eval_cost()[0], "engine_setup_s": round(setup_s, 2)}), flush=True)
             eng.close()
+        for dtype in ("f64", "f32") if a.gdba_rounds > 0 else ():
+            pd = Params(mode=p.mode, dtype=dtype)
+            word = 8 if dtype == "f64" else 4
+
+            def median_us(eng):
+                eng.run(10)
+                times = []
+                for _ in range(3):
+                    t0 = time.perf_counter()
+                    eng.run(a.gdba_rounds)
+                    times.append(1e6 * (time.perf_counter() - t0) / a.gdba_rounds)
+                return sorted(times)[1]
+
+            eng = MgmEngine(g, pd, lib_path=a.lib)
+            mgm_us = median_us(eng)
+            eng.close()
+            print(json.dumps({"algo": "mgm", "instance": inst, "kernels": "packed", "dtype": dtype, "timing": "median3",
+                              "n_vars": g.n_vars, "us_per_cycle": round(mgm_us, 2)}), flush=True)
+            for mode in ("E", "C"):
+                t0 = time.perf_counter()
+                eng = GdbaEngine(g, pd, modifier="A", violation="NZ" if p.mode == "min" else "NM", increase_mode=mode,
+                                 seed=1, lib_path=a.lib)
+                setup_s = time.perf_counter() - t0
+                us = median_us(eng)
+                # what a round can touch: the tables, the modifier pool, the slot view, the per-variable state
+                resident = (g.tables.shape[0] * word + eng.pool_bytes + len(g.var_edges) * (8 + 4 + 4 + 8 + word + 1)
+                            + (g.n_edges - len(g.var_edges) + g.n_edges) * 8 + g.n_vars * (4 + word + 1 + 8 + word))
+                print(json.dumps({"algo": "gdba", "instance": inst, "kernels": "gdba", "dtype": dtype, "timing": "median3", "increase_mode": mode,
+                                  "n_vars": g.n_vars, "us_per_cycle": round(us, 2), "ratio_to_mgm": round(us / mgm_us, 2),
+                                  "pool_bytes": eng.pool_bytes, "resident_bytes": int(resident),
+                                  "resident_gb_per_s": round(resident / us / 1e3, 1),
+                                  "cost": eng.eval_cost()[0], "engine_setup_s": round(setup_s, 2)}), flush=True)
+                eng.close()
 
 
 if __name__ == "__main__":
