@@ -1,0 +1,56 @@
+"""What the ctypes bindings of the `mxs_dsa_*`, `mxs_mgm_*`, `mxs_mgm2_*`, `mxs_gdba_*` and `mxs_dpop_*` entry points
+(include/maxsum_gpu.h) share: the handle, the error check, `eval_cost`, the cycle counter and the life cycle."""
+import ctypes as C
+from typing import Tuple
+
+import numpy as np
+
+from .engine import MaxSumGpuError
+
+
+class EngineBinding:
+    """A class sets PREFIX (`mxs_gdba`) and COUNTER (`rounds`: the entry point `mxs_gdba_rounds`), loads
+    `self._lib` and stores the handle of `<PREFIX>_create` in `self._h`."""
+    PREFIX = ""
+    COUNTER = ""
+    _h = None
+
+    def _check(self, rc: int):
+        if rc != 0:
+            raise MaxSumGpuError(f"maxsum_gpu error {rc}: {self._lib.mxs_last_error().decode()}")
+
+    def _call(self, name: str, *args):
+        """<PREFIX>_<name>(handle, *args), checked"""
+        self._check(getattr(self._lib, f"{self.PREFIX}_{name}")(self._h, *args))
+
+    @property
+    def cycle_count(self) -> int:
+        n = C.c_int64(0)
+        self._call(self.COUNTER, C.byref(n))
+        return int(n.value)
+
+    def eval_cost(self, idx=None, infinity: float = float("inf")) -> Tuple[float, int]:
+        cost, viol = C.c_double(0), C.c_int64(0)
+        p = None
+        if idx is not None:
+            idx = np.ascontiguousarray(idx, dtype=np.int32)
+            p = idx.ctypes.data
+        self._call("eval_cost", p, float(infinity), C.byref(cost), C.byref(viol))
+        return float(cost.value), int(viol.value)
+
+    def close(self):
+        if getattr(self, "_h", None):
+            getattr(self._lib, f"{self.PREFIX}_destroy")(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()

@@ -23,8 +23,8 @@
 
 namespace dpop {
 
-using mgm::Buf;
-using mgm::fail;
+using mxs_host::Buf;
+using mxs_host::fail;
 
 constexpr int TPB = 128;          // consecutive threads on consecutive entries: coalesced stores
 constexpr int MAX_DIGITS = 31;    // separator variables with more than one value: 2^31 entries at the very least
@@ -170,9 +170,9 @@ struct Engine : Base {
     bool solved = false;
     hipStream_t stream = nullptr;
     hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
-    std::vector<int32_t> h_dom, h_frow, h_evar, h_entries;
-    std::vector<int64_t> h_toff, h_coff, h_uoff;
-    std::vector<double> h_tables, h_eval_cost;
+    mxs_host::HostGraph hg;
+    std::vector<int32_t> h_entries;
+    std::vector<int64_t> h_uoff;
     std::vector<Launch> util_launches, value_launches;
     Buf<T> pool, cost;
     Buf<int32_t> dom, entries, sep_ptr, sep_var, sep_size, term_ptr, term_sv, dim_ptr, dim_pos, dim_stride, ulevel_ptr,
@@ -189,50 +189,30 @@ struct Engine : Base {
 
     int init(const mxs_graph& G, const mxs_params& p, const int32_t* parent, const int32_t* crow, const int32_t* cidx,
              int64_t max_bytes, int32_t fuse_entries, int32_t dev) override {
-        int count = 0;
-        if (hipGetDeviceCount(&count) != hipSuccess || count < 1)
-            return fail(MXS_E_NODEVICE, "no HIP device visible: the engine has no CPU fallback");
-        if (dev < 0 || dev >= count) return fail(MXS_E_INVALID, "device index out of range");
+        if (int rc = mxs_host::check_device(dev)) return rc;  // (the device itself is touched after the validation)
         device = dev;
-        const int nV = G.n_vars, nF = G.n_factors, nE = G.n_edges;
-        if (nV < 0 || nF < 0 || nE < 0) return fail(MXS_E_INVALID, "negative size");
-        if (p.mode != MXS_MODE_MIN && p.mode != MXS_MODE_MAX) return fail(MXS_E_INVALID, "invalid mode");
+        if (int rc = hg.load(G, p)) return rc;
+        const int nV = hg.nV, nF = hg.nF, nE = hg.nE;
         if (max_bytes < 0) return fail(MXS_E_INVALID, "dpop: negative max_bytes");
         if (nV && (!parent || !crow || (!cidx && crow[nV] > 0))) return fail(MXS_E_INVALID, "dpop: null tree arrays");
-        is_max = p.mode == MXS_MODE_MAX;
-        h_dom.assign(G.dom_size, G.dom_size + nV);
-        h_frow.assign(G.factor_rowptr, G.factor_rowptr + nF + 1);
-        h_evar.assign(G.edge_var, G.edge_var + nE);
-        h_toff.assign(G.table_off, G.table_off + nF + 1);
-        h_coff.assign(nV + 1, 0);
-        for (int v = 0; v < nV; ++v) {
-            if (h_dom[v] < 1) return fail(MXS_E_INVALID, "empty domain");
-            h_coff[v + 1] = h_coff[v] + h_dom[v];
-        }
-        for (int f = 0; f < nF; ++f) {
-            if (h_frow[f + 1] <= h_frow[f]) return fail(MXS_E_INVALID, "factor without variable");
-            if (h_toff[f + 1] - h_toff[f] > MAX_TABLE) return fail(MXS_E_INVALID, "dpop: constraint table larger than 2^31 - 1 entries");
-            for (int e = h_frow[f]; e < h_frow[f + 1]; ++e)
-                if (h_evar[e] < 0 || h_evar[e] >= nV) return fail(MXS_E_INVALID, "edge_var out of range");
-        }
-        h_tables.assign(G.tables, G.tables + h_toff[nF]);
-        const double* ev_cost = G.eval_var_cost ? G.eval_var_cost : G.var_cost;
-        h_eval_cost.assign(ev_cost, ev_cost + h_coff[nV]);
+        is_max = hg.is_max;
+        for (int f = 0; f < nF; ++f)
+            if (hg.toff[f + 1] - hg.toff[f] > MAX_TABLE) return fail(MXS_E_INVALID, "dpop: constraint table larger than 2^31 - 1 entries");
         // the reference is only defined while every partial sum lies strictly inside the int32 range
         double bound = 0;
         for (int f = 0; f < nF; ++f) {
             double m = 0;
-            for (int64_t i = h_toff[f]; i < h_toff[f + 1]; ++i) {
-                if (!std::isfinite(h_tables[i])) return fail(MXS_E_INVALID, "dpop: constraint tables must be finite (no inf / NaN entries)");
-                m = std::max(m, std::fabs(h_tables[i]));
+            for (int64_t i = hg.toff[f]; i < hg.toff[f + 1]; ++i) {
+                if (!std::isfinite(hg.tables[i])) return fail(MXS_E_INVALID, "dpop: constraint tables must be finite (no inf / NaN entries)");
+                m = std::max(m, std::fabs(hg.tables[i]));
             }
             bound += m;
         }
         for (int v = 0; v < nV; ++v) {
             double m = 0;
-            for (int64_t i = h_coff[v]; i < h_coff[v + 1]; ++i) {
-                if (!std::isfinite(G.var_cost[i])) return fail(MXS_E_INVALID, "dpop: variable costs must be finite (no inf / NaN entries)");
-                m = std::max(m, std::fabs(G.var_cost[i]));
+            for (int64_t i = hg.coff[v]; i < hg.coff[v + 1]; ++i) {
+                if (!std::isfinite(hg.var_cost[i])) return fail(MXS_E_INVALID, "dpop: variable costs must be finite (no inf / NaN entries)");
+                m = std::max(m, std::fabs(hg.var_cost[i]));
             }
             bound += m;
         }
@@ -292,28 +272,25 @@ struct Engine : Base {
         // ---- every constraint on one root path, owned by its deepest variable
         std::vector<int32_t> owner(nF);
         for (int f = 0; f < nF; ++f) {
-            int low = h_evar[h_frow[f]];
-            for (int e = h_frow[f]; e < h_frow[f + 1]; ++e)
-                if (depth[h_evar[e]] > depth[low]) low = h_evar[e];
-            for (int e = h_frow[f]; e < h_frow[f + 1]; ++e) {
-                const int u = h_evar[e];
+            int low = hg.evar[hg.frow[f]];
+            for (int e = hg.frow[f]; e < hg.frow[f + 1]; ++e)
+                if (depth[hg.evar[e]] > depth[low]) low = hg.evar[e];
+            for (int e = hg.frow[f]; e < hg.frow[f + 1]; ++e) {
+                const int u = hg.evar[e];
                 if (!(tin[u] <= tin[low] && tin[low] < tout[u]))
                     return fail(MXS_E_INVALID, "dpop: not a pseudo-tree (the scope of constraint " + std::to_string(f) +
                                                    " does not lie on one root path)");
             }
             owner[f] = low;
         }
-        std::vector<int32_t> edge_factor(nE);
-        for (int f = 0; f < nF; ++f)
-            for (int e = h_frow[f]; e < h_frow[f + 1]; ++e) edge_factor[e] = f;
         std::vector<std::vector<int32_t>> cons(nV);
         {
             std::vector<int32_t> taken(nF, 0);
             for (int v = 0; v < nV; ++v)
-                for (int k = G.var_rowptr[v]; k < G.var_rowptr[v + 1]; ++k) {
-                    const int e = G.var_edges[k];
-                    if (e < 0 || e >= nE || h_evar[e] != v) return fail(MXS_E_INVALID, "var_edges inconsistent with edge_var");
-                    const int f = edge_factor[e];
+                for (int k = hg.vrow[v]; k < hg.vrow[v + 1]; ++k) {
+                    const int e = hg.vedges[k];
+                    if (e < 0 || e >= nE || hg.evar[e] != v) return fail(MXS_E_INVALID, "var_edges inconsistent with edge_var");
+                    const int f = hg.efac[e];
                     if (owner[f] == v && !taken[f]++) cons[v].push_back(f);
                 }
             for (int f = 0; f < nF; ++f)
@@ -339,14 +316,14 @@ struct Engine : Base {
                 for (int u : sep[c]) add(u);
             }
             for (int f : cons[v])
-                for (int e = h_frow[f]; e < h_frow[f + 1]; ++e) add(h_evar[e]);
+                for (int e = hg.frow[f]; e < hg.frow[f + 1]; ++e) add(hg.evar[e]);
             max_depth = std::max<int64_t>(max_depth, depth[v]);
             if (h_parent[v] < 0) continue;  // (a root's separator is empty: every scope lies on a root path)
             double n = 1;
             int digits = 0;
             for (int u : sep[v]) {
-                n *= h_dom[u];
-                digits += h_dom[u] > 1;
+                n *= hg.dom[u];
+                digits += hg.dom[u] > 1;
             }
             widest_sep = std::max<int64_t>(widest_sep, (int64_t)sep[v].size());
             if (n > 9.0e18) {
@@ -365,11 +342,11 @@ struct Engine : Base {
         stats[ST_ENTRIES] = total;
         stats[ST_BYTES] = total > INT64_MAX / (int64_t)sizeof(T) ? INT64_MAX : total * (int64_t)sizeof(T);
         // ---- the budget, before anything is allocated
-        MGM_TRY(hipSetDevice(device));
+        MXS_TRY(hipSetDevice(device));
         int64_t budget = max_bytes;
         if (budget == 0) {
             size_t free_b = 0, total_b = 0;
-            MGM_TRY(hipMemGetInfo(&free_b, &total_b));
+            MXS_TRY(hipMemGetInfo(&free_b, &total_b));
             budget = (int64_t)(free_b / 10 * 8);  // 80 % of what is free: the graph, the plan and the runtime need the rest
         }
         if (stats[ST_BYTES] > budget)
@@ -381,7 +358,7 @@ struct Engine : Base {
             if (h_entries[v] < 0)
                 return fail(MXS_E_INVALID, "dpop: the UTIL table of variable " + std::to_string(v) + " has more than 2^31 - 1 entries");
         // ---- pool layout and the terms
-        const int64_t n_cost = h_coff[nV], n_tab = h_toff[nF];
+        const int64_t n_cost = hg.coff[nV], n_tab = hg.toff[nF];
         h_uoff.assign(nV, -1);
         int64_t at = n_cost + n_tab;
         for (int v = 0; v < nV; ++v)
@@ -396,10 +373,10 @@ struct Engine : Base {
         for (int v = 0; v < nV; ++v) {
             int S = 0;
             for (int u : sep[v])
-                if (h_dom[u] > 1) {
+                if (hg.dom[u] > 1) {
                     pos[u] = S++;
                     v_sep_var.push_back(u);
-                    v_sep_size.push_back(h_dom[u]);
+                    v_sep_size.push_back(hg.dom[u]);
                 }
             v_sep_ptr[v + 1] = (int32_t)v_sep_var.size();
             acc_stride.assign(S, 0);
@@ -411,8 +388,8 @@ struct Engine : Base {
                 for (int k = n - 1; k >= 0; --k) {
                     const int u = scope[k];
                     if (u == v) sv += (int32_t)stride;
-                    else if (h_dom[u] > 1) acc_stride[pos[u]] += (int32_t)stride;
-                    stride *= h_dom[u];
+                    else if (hg.dom[u] > 1) acc_stride[pos[u]] += (int32_t)stride;
+                    stride *= hg.dom[u];
                 }
                 v_term_off.push_back(off);
                 v_term_sv.push_back(sv);
@@ -424,9 +401,9 @@ struct Engine : Base {
                 v_dim_ptr.push_back((int32_t)v_dim_pos.size());
             };
             const int32_t self = v;
-            term(h_coff[v], &self, 1);
+            term(hg.coff[v], &self, 1);
             for (int k = crow[v]; k < crow[v + 1]; ++k) term(h_uoff[cidx[k]], sep[cidx[k]].data(), (int)sep[cidx[k]].size());
-            for (int f : cons[v]) term(n_cost + h_toff[f], h_evar.data() + h_frow[f], h_frow[f + 1] - h_frow[f]);
+            for (int f : cons[v]) term(n_cost + hg.toff[f], hg.evar.data() + hg.frow[f], hg.frow[f + 1] - hg.frow[f]);
             v_term_ptr[v + 1] = (int32_t)v_term_off.size();
             for (int u : sep[v]) pos[u] = -1;
         }
@@ -480,37 +457,37 @@ struct Engine : Base {
         stats[ST_LAUNCH_UTIL] = (int64_t)util_launches.size();
         stats[ST_LAUNCH_VALUE] = (int64_t)value_launches.size();
         // ---- upload
-        MGM_TRY(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
-        for (auto& e : ev) MGM_TRY(hipEventCreate(&e));
+        MXS_TRY(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
+        for (auto& e : ev) MXS_TRY(hipEventCreate(&e));
         {
             std::vector<T> head((size_t)(n_cost + n_tab));
-            for (int64_t i = 0; i < n_cost; ++i) head[(size_t)i] = (T)G.var_cost[i];
-            for (int64_t i = 0; i < n_tab; ++i) head[(size_t)(n_cost + i)] = (T)h_tables[(size_t)i];
-            MGM_TRY(pool.alloc((size_t)at));
+            for (int64_t i = 0; i < n_cost; ++i) head[(size_t)i] = (T)hg.var_cost[i];
+            for (int64_t i = 0; i < n_tab; ++i) head[(size_t)(n_cost + i)] = (T)hg.tables[(size_t)i];
+            MXS_TRY(pool.alloc((size_t)at));
             if (!head.empty()) {
-                MGM_TRY(hipMemcpyAsync(pool.p, head.data(), head.size() * sizeof(T), hipMemcpyHostToDevice, stream));
-                MGM_TRY(hipStreamSynchronize(stream));
+                MXS_TRY(hipMemcpyAsync(pool.p, head.data(), head.size() * sizeof(T), hipMemcpyHostToDevice, stream));
+                MXS_TRY(hipStreamSynchronize(stream));
             }
         }
-        MGM_TRY(dom.upload(h_dom, stream));
-        MGM_TRY(entries.upload(h_entries, stream));
-        MGM_TRY(util_off.upload(h_uoff, stream));
-        MGM_TRY(sep_ptr.upload(v_sep_ptr, stream));
-        MGM_TRY(sep_var.upload(v_sep_var, stream));
-        MGM_TRY(sep_size.upload(v_sep_size, stream));
-        MGM_TRY(term_ptr.upload(v_term_ptr, stream));
-        MGM_TRY(term_off.upload(v_term_off, stream));
-        MGM_TRY(term_sv.upload(v_term_sv, stream));
-        MGM_TRY(dim_ptr.upload(v_dim_ptr, stream));
-        MGM_TRY(dim_pos.upload(v_dim_pos, stream));
-        MGM_TRY(dim_stride.upload(v_dim_stride, stream));
-        MGM_TRY(ulevel_ptr.upload(v_ulevel, stream));
-        MGM_TRY(ublk_node.upload(v_ublk_node, stream));
-        MGM_TRY(ublk_first.upload(v_ublk_first, stream));
-        MGM_TRY(vlevel_ptr.upload(v_vlevel, stream));
-        MGM_TRY(vnode.upload(v_vnode, stream));
-        MGM_TRY(idx.alloc(nV));
-        MGM_TRY(cost.alloc(nV));
+        MXS_TRY(dom.upload(hg.dom, stream));
+        MXS_TRY(entries.upload(h_entries, stream));
+        MXS_TRY(util_off.upload(h_uoff, stream));
+        MXS_TRY(sep_ptr.upload(v_sep_ptr, stream));
+        MXS_TRY(sep_var.upload(v_sep_var, stream));
+        MXS_TRY(sep_size.upload(v_sep_size, stream));
+        MXS_TRY(term_ptr.upload(v_term_ptr, stream));
+        MXS_TRY(term_off.upload(v_term_off, stream));
+        MXS_TRY(term_sv.upload(v_term_sv, stream));
+        MXS_TRY(dim_ptr.upload(v_dim_ptr, stream));
+        MXS_TRY(dim_pos.upload(v_dim_pos, stream));
+        MXS_TRY(dim_stride.upload(v_dim_stride, stream));
+        MXS_TRY(ulevel_ptr.upload(v_ulevel, stream));
+        MXS_TRY(ublk_node.upload(v_ublk_node, stream));
+        MXS_TRY(ublk_first.upload(v_ublk_first, stream));
+        MXS_TRY(vlevel_ptr.upload(v_vlevel, stream));
+        MXS_TRY(vnode.upload(v_vnode, stream));
+        MXS_TRY(idx.alloc(nV));
+        MXS_TRY(cost.alloc(nV));
         g = Dev<T>{pool.p, dom.p, entries.p, util_off.p, sep_ptr.p, sep_var.p, sep_size.p, term_ptr.p, term_off.p, term_sv.p,
                    dim_ptr.p, dim_pos.p, dim_stride.p, ulevel_ptr.p, ublk_node.p, ublk_first.p, vlevel_ptr.p, vnode.p, idx.p, cost.p};
         return MXS_OK;
@@ -518,28 +495,28 @@ struct Engine : Base {
 
     template <bool IS_MAX>
     int launch_all() {
-        MGM_TRY(hipEventRecord(ev[0], stream));
+        MXS_TRY(hipEventRecord(ev[0], stream));
         for (const Launch& l : util_launches) {
             hipLaunchKernelGGL((k_dpop_util<T, IS_MAX>), dim3(l.grid), dim3(TPB), 0, stream, g, l.begin, l.end);
-            MGM_TRY(hipGetLastError());
+            MXS_TRY(hipGetLastError());
         }
-        MGM_TRY(hipEventRecord(ev[1], stream));
+        MXS_TRY(hipEventRecord(ev[1], stream));
         for (const Launch& l : value_launches) {
             hipLaunchKernelGGL((k_dpop_value<T, IS_MAX>), dim3(l.grid), dim3(TPB), 0, stream, g, l.begin, l.end);
-            MGM_TRY(hipGetLastError());
+            MXS_TRY(hipGetLastError());
         }
-        MGM_TRY(hipEventRecord(ev[2], stream));
-        MGM_TRY(hipStreamSynchronize(stream));
+        MXS_TRY(hipEventRecord(ev[2], stream));
+        MXS_TRY(hipStreamSynchronize(stream));
         float u_ms = 0, v_ms = 0;
-        MGM_TRY(hipEventElapsedTime(&u_ms, ev[0], ev[1]));
-        MGM_TRY(hipEventElapsedTime(&v_ms, ev[1], ev[2]));
+        MXS_TRY(hipEventElapsedTime(&u_ms, ev[0], ev[1]));
+        MXS_TRY(hipEventElapsedTime(&v_ms, ev[1], ev[2]));
         stats[ST_UTIL_NS] = (int64_t)((double)u_ms * 1e6);
         stats[ST_VALUE_NS] = (int64_t)((double)v_ms * 1e6);
         return MXS_OK;
     }
 
     int solve() override {
-        MGM_TRY(hipSetDevice(device));
+        MXS_TRY(hipSetDevice(device));
         int rc = is_max ? launch_all<true>() : launch_all<false>();
         if (rc) return rc;
         solved = true;
@@ -548,14 +525,14 @@ struct Engine : Base {
 
     int get_state(int32_t* out_idx, double* out_cost) override {
         if (!solved) return fail(MXS_E_STATE, "dpop: no solution yet (call mxs_dpop_solve first)");
-        MGM_TRY(hipSetDevice(device));
-        const int nV = (int)h_dom.size();
+        MXS_TRY(hipSetDevice(device));
+        const int nV = hg.nV;
         if (!nV) return MXS_OK;
         std::vector<T> hc(nV);
         std::vector<int32_t> hi(nV);
-        MGM_TRY(hipMemcpyAsync(hi.data(), idx.p, 4 * (size_t)nV, hipMemcpyDeviceToHost, stream));
-        MGM_TRY(hipMemcpyAsync(hc.data(), cost.p, sizeof(T) * nV, hipMemcpyDeviceToHost, stream));
-        MGM_TRY(hipStreamSynchronize(stream));
+        MXS_TRY(hipMemcpyAsync(hi.data(), idx.p, 4 * (size_t)nV, hipMemcpyDeviceToHost, stream));
+        MXS_TRY(hipMemcpyAsync(hc.data(), cost.p, sizeof(T) * nV, hipMemcpyDeviceToHost, stream));
+        MXS_TRY(hipStreamSynchronize(stream));
         for (int v = 0; v < nV; ++v) {
             if (out_idx) out_idx[v] = hi[v];
             if (out_cost) out_cost[v] = (double)hc[v];
@@ -565,13 +542,13 @@ struct Engine : Base {
 
     int get_util(int32_t var, double* buf, int64_t n) override {
         if (!solved) return fail(MXS_E_STATE, "dpop: no solution yet (call mxs_dpop_solve first)");
-        if (var < 0 || var >= (int)h_dom.size()) return fail(MXS_E_INVALID, "dpop: variable out of range");
+        if (var < 0 || var >= (int)hg.dom.size()) return fail(MXS_E_INVALID, "dpop: variable out of range");
         if (h_parent[var] < 0) return fail(MXS_E_INVALID, "dpop: a root sends no UTIL");
         if (!buf || n != h_entries[var]) return fail(MXS_E_INVALID, "dpop: the buffer must hold the UTIL's " + std::to_string(h_entries[var]) + " entries");
-        MGM_TRY(hipSetDevice(device));
+        MXS_TRY(hipSetDevice(device));
         std::vector<T> h((size_t)n);
-        MGM_TRY(hipMemcpyAsync(h.data(), pool.p + h_uoff[var], sizeof(T) * (size_t)n, hipMemcpyDeviceToHost, stream));
-        MGM_TRY(hipStreamSynchronize(stream));
+        MXS_TRY(hipMemcpyAsync(h.data(), pool.p + h_uoff[var], sizeof(T) * (size_t)n, hipMemcpyDeviceToHost, stream));
+        MXS_TRY(hipStreamSynchronize(stream));
         for (int64_t i = 0; i < n; ++i) buf[i] = (double)h[(size_t)i];
         return MXS_OK;
     }
@@ -579,31 +556,14 @@ struct Engine : Base {
     // DCOP.solution_cost of an assignment: every constraint and every variable's own cost
     int eval_cost(const int32_t* in_idx, double infinity, double* cst, int64_t* viol) override {
         std::vector<int32_t> c;
-        const int nV = (int)h_dom.size();
+        const int nV = hg.nV;
         if (!in_idx) {
             c.resize(nV);
             int rc = get_state(c.data(), nullptr);
             if (rc) return rc;
             in_idx = c.data();
         }
-        for (int v = 0; v < nV; ++v)
-            if (in_idx[v] < 0 || in_idx[v] >= h_dom[v]) return fail(MXS_E_INVALID, "assignment index out of the domain");
-        double soft = 0;
-        int64_t hard = 0;
-        const int nF = (int)h_frow.size() - 1;
-        for (int f = 0; f < nF; ++f) {
-            int64_t lin = 0;
-            for (int e = h_frow[f]; e < h_frow[f + 1]; ++e) lin = lin * h_dom[h_evar[e]] + in_idx[h_evar[e]];
-            const double r = h_tables[h_toff[f] + lin];
-            if (r != infinity) soft += r; else hard += 1;
-        }
-        for (int v = 0; v < nV; ++v) {
-            const double x = h_eval_cost[h_coff[v] + in_idx[v]];
-            if (x != infinity) soft += x; else hard += 1;
-        }
-        if (cst) *cst = soft;
-        if (viol) *viol = hard;
-        return MXS_OK;
+        return hg.eval_cost(in_idx, infinity, cst, viol);
     }
 };
 
@@ -617,48 +577,34 @@ extern "C" {
 
 int mxs_dpop_create(const mxs_graph* g, const mxs_params* p, const int32_t* parent, const int32_t* child_rowptr,
                     const int32_t* child_idx, int64_t max_bytes, int32_t fuse_entries, int32_t device, mxs_dpop** out) {
-    if (!g || !p || !out) return mgm::fail(MXS_E_INVALID, "null argument");
-    *out = nullptr;
-    try {
-        dpop::Base* impl = p->dtype == MXS_DTYPE_F32 ? (dpop::Base*)new dpop::Engine<float>()
-                                                     : (dpop::Base*)new dpop::Engine<double>();
-        int rc = impl->init(*g, *p, parent, child_rowptr, child_idx, max_bytes, fuse_entries, device);
-        if (rc) {
-            delete impl;
-            return rc;
-        }
-        *out = new mxs_dpop{impl};
-        return MXS_OK;
-    } catch (const std::exception& ex) {
-        return mgm::fail(MXS_E_NOMEM, ex.what());
-    }
+    return mxs_host::create<mxs_dpop, dpop::Engine>(g, p, out, parent, child_rowptr, child_idx, max_bytes, fuse_entries, device);
 }
-int mxs_dpop_solve(mxs_dpop* e) { return e ? e->impl->solve() : mgm::fail(MXS_E_INVALID, "null handle"); }
+int mxs_dpop_solve(mxs_dpop* e) { return e ? e->impl->solve() : mxs_host::fail(MXS_E_INVALID, "null handle"); }
 int mxs_dpop_get_state(mxs_dpop* e, int32_t* idx, double* cost) {
-    return e ? e->impl->get_state(idx, cost) : mgm::fail(MXS_E_INVALID, "null handle");
+    return e ? e->impl->get_state(idx, cost) : mxs_host::fail(MXS_E_INVALID, "null handle");
 }
 int mxs_dpop_eval_cost(mxs_dpop* e, const int32_t* idx, double infinity, double* cost, int64_t* violations) {
-    return e ? e->impl->eval_cost(idx, infinity, cost, violations) : mgm::fail(MXS_E_INVALID, "null handle");
+    return e ? e->impl->eval_cost(idx, infinity, cost, violations) : mxs_host::fail(MXS_E_INVALID, "null handle");
 }
 int mxs_dpop_stats(const mxs_dpop* e, int64_t* out, int32_t n) {
-    if (!e || !out || n < 0) return mgm::fail(MXS_E_INVALID, "null handle or buffer");
+    if (!e || !out || n < 0) return mxs_host::fail(MXS_E_INVALID, "null handle or buffer");
     for (int i = 0; i < n; ++i) out[i] = i < dpop::ST_COUNT ? e->impl->stats[i] : 0;
     return MXS_OK;
 }
 int mxs_dpop_util_dims(const mxs_dpop* e, int32_t var, int32_t* dims, int32_t* n) {
-    if (!e || !n) return mgm::fail(MXS_E_INVALID, "null handle or count");
-    if (var < 0 || var >= (int32_t)e->impl->sep.size()) return mgm::fail(MXS_E_INVALID, "dpop: variable out of range");
-    if (e->impl->h_parent[var] < 0) return mgm::fail(MXS_E_INVALID, "dpop: a root sends no UTIL");
+    if (!e || !n) return mxs_host::fail(MXS_E_INVALID, "null handle or count");
+    if (var < 0 || var >= (int32_t)e->impl->sep.size()) return mxs_host::fail(MXS_E_INVALID, "dpop: variable out of range");
+    if (e->impl->h_parent[var] < 0) return mxs_host::fail(MXS_E_INVALID, "dpop: a root sends no UTIL");
     const auto& s = e->impl->sep[var];
     if (dims) {
-        if (*n < (int32_t)s.size()) return mgm::fail(MXS_E_INVALID, "dpop: the dims buffer is too short");
+        if (*n < (int32_t)s.size()) return mxs_host::fail(MXS_E_INVALID, "dpop: the dims buffer is too short");
         for (size_t i = 0; i < s.size(); ++i) dims[i] = s[i];
     }
     *n = (int32_t)s.size();
     return MXS_OK;
 }
 int mxs_dpop_get_util(mxs_dpop* e, int32_t var, double* buf, int64_t n_entries) {
-    return e ? e->impl->get_util(var, buf, n_entries) : mgm::fail(MXS_E_INVALID, "null handle");
+    return e ? e->impl->get_util(var, buf, n_entries) : mxs_host::fail(MXS_E_INVALID, "null handle");
 }
 int mxs_dpop_destroy(mxs_dpop* e) {
     if (e) {

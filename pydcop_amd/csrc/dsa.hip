@@ -10,7 +10,7 @@
 //
 // The reference draws from Python's unseeded `random` module (initial value, move test, choice
 // among the best values).  Here every draw comes from a counter-based generator keyed on (seed,
-// variable, cycle, draw) -- dsa_uniform, the same function in oracle/dsa_oracle.c and, patched into
+// variable, cycle, draw) -- uniform() of engine_common.h, the same function in oracle/dsa_oracle.c and, patched into
 // the reference's `random` for the duration of a run, in oracle/ref_harness.py -- so that the
 // stochastic algorithm has a pinned parity: bit for bit the reference's own DsaComputation objects
 // under that generator (tests/test_dsa_oracle_vs_reference.py), independent of scheduling.  The
@@ -26,74 +26,18 @@
 #include <vector>
 
 #include "../../include/maxsum_gpu.h"
+#include "engine_common.h"
 #include "local_search.h"
-
-extern "C" __attribute__((visibility("hidden"))) void mxs_set_last_error(const char* msg);  // engine.hip
 
 namespace dsa {
 
+using mxs_host::Buf;
+using mxs_host::fail;
+using mxs_host::uniform;            // draws 0 (start value), 1 (move test), 2 (choice among the best values)
+using mxs_host::uniform_from_key;
+using mxs_host::uniform_key;
+
 constexpr int TPB = 64;  // one wave per block: 100k variables spread over every CU (latency-bound CSR walks)
-
-static int fail(int code, const std::string& msg) {
-    mxs_set_last_error(msg.c_str());
-    return code;
-}
-#define DSA_TRY(call)                                                                     \
-    do {                                                                                  \
-        hipError_t e__ = (call);                                                          \
-        if (e__ != hipSuccess) return fail(MXS_E_HIP, std::string(#call) + " failed");     \
-    } while (0)
-
-template <typename U>
-struct Buf {
-    U* p = nullptr;
-    size_t n = 0;
-    hipError_t upload(const std::vector<U>& h, hipStream_t st) {
-        release();
-        n = h.size();
-        hipError_t e = hipMalloc((void**)&p, (n ? n : 1) * sizeof(U));
-        if (e != hipSuccess || h.empty()) return e;
-        e = hipMemcpyAsync(p, h.data(), n * sizeof(U), hipMemcpyHostToDevice, st);
-        if (e != hipSuccess) return e;
-        return hipStreamSynchronize(st);
-    }
-    hipError_t alloc(size_t count) {
-        n = count;
-        return hipMalloc((void**)&p, (n ? n : 1) * sizeof(U));
-    }
-    void release() {
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        n = 0;
-    }
-    ~Buf() {
-        if (p) (void)hipFree(p);
-    }
-};
-
-// splitmix64 finaliser over a key of (seed, variable, cycle, draw): oracle/dsa_oracle.c, bit for bit
-__host__ __device__ inline uint64_t mix64(uint64_t z) {
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    return z ^ (z >> 31);
-}
-__host__ __device__ inline double uniform(uint64_t seed, int32_t variable, int64_t cycle, int32_t draw) {
-    uint64_t z = seed + 0x9E3779B97F4A7C15ull * ((uint64_t)(uint32_t)variable + 1);
-    z = mix64(z) + 0x9E3779B97F4A7C15ull * ((uint64_t)cycle + 1);
-    z = mix64(z) + (uint64_t)(uint32_t)draw;
-    return (double)(mix64(z) >> 11) * (1.0 / 9007199254740992.0);
-}
-
-// the same generator from its first stage, mix64(seed + G * (variable + 1)): a constant of the variable,
-// computed once on the host for the packed kernel (two 64-bit multiplies per draw fewer)
-__host__ __device__ inline uint64_t uniform_key(uint64_t seed, int32_t variable) {
-    return mix64(seed + 0x9E3779B97F4A7C15ull * ((uint64_t)(uint32_t)variable + 1));
-}
-__host__ __device__ inline double uniform_from_key(uint64_t key, int64_t cycle, int32_t draw) {
-    uint64_t z = key + 0x9E3779B97F4A7C15ull * ((uint64_t)cycle + 1);
-    z = mix64(z) + (uint64_t)(uint32_t)draw;
-    return (double)(mix64(z) >> 11) * (1.0 / 9007199254740992.0);
-}
 
 template <typename T>
 struct Dev {
@@ -377,28 +321,18 @@ struct Engine : Base {
     Dev<T> g{};
     int which = 0;
     uint64_t seed = 0;
-    std::vector<int32_t> h_dom, h_frow, h_evar, h_nn, h_q, h_vrank;
-    std::vector<int64_t> h_toff, h_coff;
-    std::vector<double> h_tables, h_eval_cost, h_var_cost;
-    Buf<int32_t> dom_size, factor_rowptr, edge_var, edge_factor, var_rowptr, var_edges, n_neigh;
+    mxs_host::HostGraph hg;
+    std::vector<int32_t> h_nn, h_q, h_vrank;
+    Buf<int32_t> dom_size, factor_rowptr, edge_var, edge_factor, var_rowptr, var_edges, n_neigh, qmap;
     Buf<int32_t> cur[2];
     Buf<int64_t> table_off;
     Buf<T> tables, f_opt, cost;
     Buf<double> prob;
-    Buf<int64_t> sl_base;
-    Buf<int32_t> sl_stride_v, sl_nb_rowptr, sl_nb_var, sl_nb_stride, sl_nb0_var, sl_nb0_stride, sl_conc_rowptr, sl_conc_var;
-    Buf<uint8_t> sl_rows;           // the row view of the variables the pack cannot take (local_search.h, Slots::rows)
-    Buf<int64_t> sl_row_base;
-    Buf<int32_t> sl_row_nb_stride, sl_row_nb0_stride;
-    bool have_rows = false;
-    Buf<lsearch::PackWave> pk_waves;
-    Buf<int32_t> pk_nb, pk_slot, pk_rest, pk_dom, qmap;
-    Buf<uint64_t> pk_key;
+    mxs_host::DevSlots sl;
+    mxs_host::DevPack<T> pk;
+    Buf<uint64_t> pk_key;   // what only DSA keeps per packed variable / lane (Dev::pack_key, pack_prob, pack_fopt)
     Buf<double> pk_prob;
-    Buf<int8_t> pk_rec8;
-    Buf<T> pk_recT, pk_fopt;
-    bool pack_int8 = false;
-    int n_rest = 0;
+    Buf<T> pk_fopt;
     int max_dom = 0;
 
     ~Engine() override {
@@ -409,162 +343,78 @@ struct Engine : Base {
              uint64_t sd, int dev) override {
         device = dev;
         seed = sd;
-        int count = 0;
-        if (hipGetDeviceCount(&count) != hipSuccess || count <= 0)
-            return fail(MXS_E_NODEVICE, "no HIP device visible: the engine has no CPU fallback");
-        if (dev < 0 || dev >= count) return fail(MXS_E_INVALID, "device index out of range");
+        if (int rc = mxs_host::open_device(dev, &stream)) return rc;
         if (variant < 0 || variant > 2) return fail(MXS_E_INVALID, "variant must be 0 (A), 1 (B) or 2 (C)");
-        if (p.mode != MXS_MODE_MIN && p.mode != MXS_MODE_MAX) return fail(MXS_E_INVALID, "invalid mode");
-        DSA_TRY(hipSetDevice(dev));
-        DSA_TRY(hipStreamCreateWithFlags(&stream, 0));
-        const int nV = G.n_vars, nF = G.n_factors, nE = G.n_edges;
-        if (nV < 0 || nF < 0 || nE < 0) return fail(MXS_E_INVALID, "negative size");
-        h_dom.assign(G.dom_size, G.dom_size + nV);
-        h_frow.assign(G.factor_rowptr, G.factor_rowptr + nF + 1);
-        h_evar.assign(G.edge_var, G.edge_var + nE);
-        h_toff.assign(G.table_off, G.table_off + nF + 1);
-        h_coff.assign(nV + 1, 0);
-        for (int v = 0; v < nV; ++v) {
-            if (h_dom[v] < 1) return fail(MXS_E_INVALID, "empty domain");
-            h_coff[v + 1] = h_coff[v] + h_dom[v];
-        }
-        std::vector<int32_t> efac(nE), vrow(G.var_rowptr, G.var_rowptr + nV + 1), vedges(G.var_edges, G.var_edges + nE);
-        for (int f = 0; f < nF; ++f) {
-            if (h_frow[f + 1] <= h_frow[f]) return fail(MXS_E_INVALID, "factor without variable");
-            for (int e = h_frow[f]; e < h_frow[f + 1]; ++e) {
-                if (h_evar[e] < 0 || h_evar[e] >= nV) return fail(MXS_E_INVALID, "edge_var out of range");
-                efac[e] = f;
-            }
-        }
+        if (int rc = hg.load(G, p)) return rc;  // (init_idx is not read: the reference's DSA ignores initial values)
+        const int nV = hg.nV, nF = hg.nF;
+        const std::vector<int32_t> &efac = hg.efac, &vrow = hg.vrow, &vedges = hg.vedges;
         h_nn.assign(nV, 0);
         std::vector<int64_t> n_count(nV, 0);
         for (int f = 0; f < nF; ++f) {
-            const int ar = h_frow[f + 1] - h_frow[f];
-            for (int e = h_frow[f]; e < h_frow[f + 1]; ++e) {
-                if (ar > 1) h_nn[h_evar[e]] = 1;
-                n_count[h_evar[e]] += ar - 1;
+            const int ar = hg.frow[f + 1] - hg.frow[f];
+            for (int e = hg.frow[f]; e < hg.frow[f + 1]; ++e) {
+                if (ar > 1) h_nn[hg.evar[e]] = 1;
+                n_count[hg.evar[e]] += ar - 1;
             }
         }
         std::vector<double> pr(nV);
         for (int v = 0; v < nV; ++v)  // p_mode arity: 1 / sum(arity - 1) * 1.2 (dsa.py:256-259)
             pr[v] = (arity_mode && n_count[v] > 0) ? 1.0 / (double)n_count[v] * 1.2 : probability;
-        h_tables.assign(G.tables, G.tables + h_toff[nF]);
-        h_var_cost.assign(G.var_cost, G.var_cost + h_coff[nV]);
-        const double* ev = G.eval_var_cost ? G.eval_var_cost : G.var_cost;
-        h_eval_cost.assign(ev, ev + h_coff[nV]);
-        std::vector<T> tt(h_tables.size()), fo(nF);
-        for (size_t i = 0; i < tt.size(); ++i) tt[i] = (T)h_tables[i];
+        const std::vector<T> tt = mxs_host::narrowed<T>(hg.tables);
+        std::vector<T> fo(nF);
         for (int f = 0; f < nF; ++f) {  // find_optimum (relations.py:1367-1401): variant B
-            T opt = tt[h_toff[f]];
-            for (int64_t k = h_toff[f] + 1; k < h_toff[f + 1]; ++k)
+            T opt = tt[hg.toff[f]];
+            for (int64_t k = hg.toff[f] + 1; k < hg.toff[f + 1]; ++k)
                 if (p.mode == MXS_MODE_MAX ? tt[k] > opt : tt[k] < opt) opt = tt[k];
             fo[f] = opt;
         }
         lsearch::HostSlots hs;
-        const std::string bad = hs.build(nV, nF, h_dom, h_frow, h_evar, h_toff, vrow, vedges);
+        const std::string bad = hs.build(nV, nF, hg.dom, hg.frow, hg.evar, hg.toff, vrow, vedges);
         if (!bad.empty()) return fail(MXS_E_INVALID, bad);
         max_dom = 0;
-        for (int v = 0; v < nV; ++v) max_dom = h_dom[v] > max_dom ? h_dom[v] : max_dom;
+        for (int v = 0; v < nV; ++v) max_dom = hg.dom[v] > max_dom ? hg.dom[v] : max_dom;
         {   // the packed view of the variables it can take (local_search.h); the others -- constraints of
             // arity > 2, larger domains, degrees above 64 -- stay on the thread-per-variable kernel
             lsearch::HostPack hp;
-            hp.build(nV, h_dom, vrow, h_nn, hs, h_tables);
+            hp.build(nV, hg.dom, vrow, h_nn, hs, hg.tables);
             std::vector<T> fopt_lane(hp.slot.size(), (T)0);
             for (size_t i = 0; i < hp.slot.size(); ++i)
                 if (hp.slot[i] >= 0) fopt_lane[i] = fo[efac[vedges[hp.slot[i]]]];
-            pack_int8 = hp.int8_exact;
-            if (pack_int8) {
-                std::vector<int8_t> r8(hp.rec.size());
-                for (size_t i = 0; i < r8.size(); ++i) r8[i] = (int8_t)hp.rec[i];
-                DSA_TRY(pk_rec8.upload(r8, stream));
-            } else {
-                std::vector<T> rt(hp.rec.size());
-                for (size_t i = 0; i < rt.size(); ++i) rt[i] = (T)hp.rec[i];
-                DSA_TRY(pk_recT.upload(rt, stream));
-            }
-            DSA_TRY(pk_waves.upload(hp.waves, stream));
-            // packed positions (Dev::q): the packed variables in wave order, then the others
-            h_q.assign(nV, -1);
-            int nq = 0;
-            for (int v : hp.vars) h_q[v] = nq++;
-            const int n_packed = nq;
-            for (int v = 0; v < nV; ++v)
-                if (h_q[v] < 0) h_q[v] = nq++;
-            auto to_q = [&](std::vector<int32_t> a) {
-                for (auto& x : a)
-                    if (x >= 0) x = h_q[x];
-                return a;
-            };
-            std::vector<int32_t> pdom(n_packed);
-            std::vector<uint64_t> pkey(n_packed);
-            std::vector<double> pprob(n_packed);
+            h_q = mxs_host::packed_order(hp, nV);
+            std::vector<uint64_t> pkey(hp.vars.size());
+            std::vector<double> pprob(hp.vars.size());
             for (int v : hp.vars) {
-                pdom[h_q[v]] = h_dom[v];
                 pkey[h_q[v]] = uniform_key(seed, v);
                 pprob[h_q[v]] = pr[v];
             }
-            DSA_TRY(qmap.upload(h_q, stream));
-            DSA_TRY(pk_dom.upload(pdom, stream));
-            DSA_TRY(pk_key.upload(pkey, stream));
-            DSA_TRY(pk_prob.upload(pprob, stream));
-            DSA_TRY(sl_nb_var.upload(to_q(hs.nb_var), stream));
-            DSA_TRY(sl_nb0_var.upload(to_q(hs.nb0_var), stream));
+            if (int rc = pk.upload(hp, h_q, hg.dom, stream)) return rc;
+            MXS_TRY(qmap.upload(h_q, stream));
+            MXS_TRY(pk_key.upload(pkey, stream));
+            MXS_TRY(pk_prob.upload(pprob, stream));
+            MXS_TRY(pk_fopt.upload(fopt_lane, stream));
+            if (int rc = sl.upload(hs, stream, &h_q, true)) return rc;
+            sl.upload_rows(hs, hp.rest, hg, max_dom, (int)sizeof(T), stream);
             g.q = qmap.p;
-            g.pack_dom = pk_dom.p;
+            g.pack = pk.view();
+            g.pack_dom = pk.dom.p;
             g.pack_key = pk_key.p;
             g.pack_prob = pk_prob.p;
-            DSA_TRY(pk_nb.upload(to_q(hp.nb), stream));
-            DSA_TRY(pk_slot.upload(hp.slot, stream));
-            DSA_TRY(pk_rest.upload(hp.rest, stream));
-            DSA_TRY(pk_fopt.upload(fopt_lane, stream));
-            n_rest = (int)hp.rest.size();
-            // the row view for them (domains of at most 32 values; $MAXSUM_LOCAL_SEARCH_ROWS=0 leaves it out, the
-            // budget in bytes can be set: A/B runs and tests)
-            {
-                const int64_t budget = lsearch::HostSlots::rows_budget();
-                have_rows = budget > 0 && max_dom <= 32 && hs.build_rows(hp.rest, h_dom, vrow, h_toff, h_tables, (int)sizeof(T), 32, budget);
-                if (have_rows) {
-                    // an upload that fails (device memory) leaves the strided path: free what was allocated and carry on
-                    const bool ok = sl_rows.upload(hs.rows, stream) == hipSuccess && sl_row_base.upload(hs.row_base, stream) == hipSuccess &&
-                                    sl_row_nb_stride.upload(hs.row_nb_stride, stream) == hipSuccess &&
-                                    sl_row_nb0_stride.upload(hs.row_nb0_stride, stream) == hipSuccess;
-                    if (!ok) {
-                        (void)hipGetLastError();
-                        sl_rows.release(), sl_row_base.release(), sl_row_nb_stride.release(), sl_row_nb0_stride.release();
-                        have_rows = false;
-                    }
-                    hs.rows.clear();
-                    hs.rows.shrink_to_fit();
-                }
-            }
-            g.pack = lsearch::Pack{pk_waves.p, pk_nb.p, pk_slot.p,
-                                   pack_int8 ? (const void*)pk_rec8.p : (const void*)pk_recT.p, (int32_t)hp.nb.size()};
             g.pack_fopt = pk_fopt.p;
         }
-        DSA_TRY(sl_base.upload(hs.base, stream));
-        DSA_TRY(sl_stride_v.upload(hs.stride_v, stream));
-        DSA_TRY(sl_nb_rowptr.upload(hs.nb_rowptr, stream));
-        DSA_TRY(sl_nb_stride.upload(hs.nb_stride, stream));
-        DSA_TRY(sl_nb0_stride.upload(hs.nb0_stride, stream));
-        DSA_TRY(sl_conc_rowptr.upload(hs.conc_rowptr, stream));
-        DSA_TRY(sl_conc_var.upload(hs.conc_var, stream));
-        g.slots = lsearch::Slots{sl_base.p, sl_stride_v.p, sl_nb_rowptr.p, sl_nb_var.p, sl_nb_stride.p,
-                                 sl_nb0_var.p, sl_nb0_stride.p, sl_conc_rowptr.p, sl_conc_var.p,
-                                 have_rows ? sl_rows.p : nullptr, sl_row_base.p, sl_row_nb_stride.p, sl_row_nb0_stride.p,
-                                 hs.rows_int8 ? 1 : 0};
-        DSA_TRY(dom_size.upload(h_dom, stream));
-        DSA_TRY(factor_rowptr.upload(h_frow, stream));
-        DSA_TRY(edge_var.upload(h_evar, stream));
-        DSA_TRY(edge_factor.upload(efac, stream));
-        DSA_TRY(var_rowptr.upload(vrow, stream));
-        DSA_TRY(var_edges.upload(vedges, stream));
-        DSA_TRY(n_neigh.upload(h_nn, stream));
-        DSA_TRY(table_off.upload(h_toff, stream));
-        DSA_TRY(tables.upload(tt, stream));
-        DSA_TRY(f_opt.upload(fo, stream));
-        DSA_TRY(prob.upload(pr, stream));
-        for (int b = 0; b < 2; ++b) DSA_TRY(cur[b].alloc(nV));
-        DSA_TRY(cost.alloc(nV));
+        g.slots = sl.view();
+        MXS_TRY(dom_size.upload(hg.dom, stream));
+        MXS_TRY(factor_rowptr.upload(hg.frow, stream));
+        MXS_TRY(edge_var.upload(hg.evar, stream));
+        MXS_TRY(edge_factor.upload(efac, stream));
+        MXS_TRY(var_rowptr.upload(vrow, stream));
+        MXS_TRY(var_edges.upload(vedges, stream));
+        MXS_TRY(n_neigh.upload(h_nn, stream));
+        MXS_TRY(table_off.upload(hg.toff, stream));
+        MXS_TRY(tables.upload(tt, stream));
+        MXS_TRY(f_opt.upload(fo, stream));
+        MXS_TRY(prob.upload(pr, stream));
+        for (int b = 0; b < 2; ++b) MXS_TRY(cur[b].alloc(nV));
+        MXS_TRY(cost.alloc(nV));
         g.n_vars = nV;
         g.is_max = p.mode == MXS_MODE_MAX;
         g.variant = variant;
@@ -579,45 +429,39 @@ struct Engine : Base {
     // the order of every variable's domain values (include/maxsum_gpu.h): cost ties of a variable without
     // neighbours break on the value, as the reference's optimal_cost_value does
     int set_value_rank(const int32_t* rank) override {
-        if (rank) h_vrank.assign(rank, rank + h_coff[g.n_vars]);
+        if (rank) h_vrank.assign(rank, rank + hg.coff[g.n_vars]);
         else h_vrank.clear();
         return reset();
     }
 
     int reset() override {
-        DSA_TRY(hipSetDevice(device));
+        MXS_TRY(hipSetDevice(device));
         const int nV = g.n_vars;
         std::vector<int32_t> c0(nV);
         std::vector<T> k0(nV, (T)0);
         for (int v = 0; v < nV; ++v) {
             if (h_nn[v] == 0) {  // optimal_cost_value (dsa.py:278-289)
-                const int32_t* rk = h_vrank.empty() ? nullptr : h_vrank.data() + h_coff[v];
-                int best = 0;
-                for (int d = 1; d < h_dom[v]; ++d) {  // min / max over (cost, value) tuples, relations.py:1661-1665
-                    const T a = (T)h_var_cost[h_coff[v] + d], b = (T)h_var_cost[h_coff[v] + best];
-                    const int rd = rk ? rk[d] : d, rb = rk ? rk[best] : best;
-                    if (g.is_max ? (a > b || (a == b && rd > rb)) : (a < b || (a == b && rd < rb))) best = d;
-                }
+                const int best = hg.optimal_cost_value<T>(v, g.is_max, h_vrank);
                 c0[h_q[v]] = best;  // (the state lives in packed order, Dev::q)
-                k0[h_q[v]] = (T)h_var_cost[h_coff[v] + best];
+                k0[h_q[v]] = (T)hg.var_cost[hg.coff[v] + best];
             } else {  // random_value_selection (dsa.py:291): draw 0 of cycle 0
-                c0[h_q[v]] = (int32_t)(uniform(seed, v, 0, 0) * h_dom[v]);
+                c0[h_q[v]] = (int32_t)(uniform(seed, v, 0, 0) * hg.dom[v]);
             }
         }
         which = 0;
         if (nV) {
-            DSA_TRY(hipMemcpyAsync(cur[0].p, c0.data(), 4 * nV, hipMemcpyHostToDevice, stream));
+            MXS_TRY(hipMemcpyAsync(cur[0].p, c0.data(), 4 * nV, hipMemcpyHostToDevice, stream));
             // (both buffers: the packed launch writes only the variables that have neighbours)
-            DSA_TRY(hipMemcpyAsync(cur[1].p, c0.data(), 4 * nV, hipMemcpyHostToDevice, stream));
-            DSA_TRY(hipMemcpyAsync(cost.p, k0.data(), sizeof(T) * nV, hipMemcpyHostToDevice, stream));
-            DSA_TRY(hipStreamSynchronize(stream));
+            MXS_TRY(hipMemcpyAsync(cur[1].p, c0.data(), 4 * nV, hipMemcpyHostToDevice, stream));
+            MXS_TRY(hipMemcpyAsync(cost.p, k0.data(), sizeof(T) * nV, hipMemcpyHostToDevice, stream));
+            MXS_TRY(hipStreamSynchronize(stream));
         }
         cycles = 0;
         return MXS_OK;
     }
 
     int run(int32_t n) override {
-        DSA_TRY(hipSetDevice(device));
+        MXS_TRY(hipSetDevice(device));
         const int nV = g.n_vars;
         if (nV == 0) {
             cycles += n > 0 ? n : 0;
@@ -634,11 +478,11 @@ struct Engine : Base {
             g.n_list = nV;
             if (packed) {
                 const dim3 pgrid((unsigned)((g.pack.n_lanes + PACK_TPB - 1) / PACK_TPB)), pblock(PACK_TPB);
-                if (pack_int8) hipLaunchKernelGGL((k_dsa_cycle_pack<T, int8_t>), pgrid, pblock, 0, stream, g);
+                if (pk.int8) hipLaunchKernelGGL((k_dsa_cycle_pack<T, int8_t>), pgrid, pblock, 0, stream, g);
                 else hipLaunchKernelGGL((k_dsa_cycle_pack<T, T>), pgrid, pblock, 0, stream, g);
-                DSA_TRY(hipGetLastError());
-                g.var_list = pk_rest.p;
-                g.n_list = n_rest;
+                MXS_TRY(hipGetLastError());
+                g.var_list = pk.rest.p;
+                g.n_list = pk.n_rest;
             }
             if (g.n_list > 0) {
                 const dim3 grid((unsigned)((g.n_list + TPB - 1) / TPB)), block(TPB);
@@ -647,24 +491,24 @@ struct Engine : Base {
                 else if (max_dom <= 8) hipLaunchKernelGGL((k_dsa_cycle_slots<T, 8>), grid, block, 0, stream, g);
                 else if (max_dom <= 16) hipLaunchKernelGGL((k_dsa_cycle_slots<T, 16>), grid, block, 0, stream, g);
                 else hipLaunchKernelGGL((k_dsa_cycle_slots<T, 32>), grid, block, 0, stream, g);
-                DSA_TRY(hipGetLastError());
+                MXS_TRY(hipGetLastError());
             }
             which ^= 1;
             cycles += 1;
         }
-        DSA_TRY(hipStreamSynchronize(stream));
+        MXS_TRY(hipStreamSynchronize(stream));
         return MXS_OK;
     }
 
     int get_state(int32_t* idx, double* cst) override {
-        DSA_TRY(hipSetDevice(device));
+        MXS_TRY(hipSetDevice(device));
         const int nV = g.n_vars;
         if (!nV) return MXS_OK;
         std::vector<T> hc(nV);
         std::vector<int32_t> hi(nV);
-        DSA_TRY(hipMemcpyAsync(hi.data(), cur[which].p, 4 * nV, hipMemcpyDeviceToHost, stream));
-        DSA_TRY(hipMemcpyAsync(hc.data(), cost.p, sizeof(T) * nV, hipMemcpyDeviceToHost, stream));
-        DSA_TRY(hipStreamSynchronize(stream));
+        MXS_TRY(hipMemcpyAsync(hi.data(), cur[which].p, 4 * nV, hipMemcpyDeviceToHost, stream));
+        MXS_TRY(hipMemcpyAsync(hc.data(), cost.p, sizeof(T) * nV, hipMemcpyDeviceToHost, stream));
+        MXS_TRY(hipStreamSynchronize(stream));
         for (int v = 0; v < nV; ++v) {  // the state lives in packed order (Dev::q)
             if (idx) idx[v] = hi[h_q[v]];
             if (cst) cst[v] = (double)hc[h_q[v]];
@@ -680,26 +524,7 @@ struct Engine : Base {
             if (rc) return rc;
             idx = c.data();
         }
-        double soft = 0;
-        int64_t hard = 0;
-        const int nF = (int)h_frow.size() - 1;
-        for (int f = 0; f < nF; ++f) {
-            int64_t lin = 0;
-            for (int e = h_frow[f]; e < h_frow[f + 1]; ++e) {
-                const int v = h_evar[e];
-                if (idx[v] < 0 || idx[v] >= h_dom[v]) return fail(MXS_E_INVALID, "assignment index out of the domain");
-                lin = lin * h_dom[v] + idx[v];
-            }
-            const double r = h_tables[h_toff[f] + lin];
-            if (r != infinity) soft += r; else hard += 1;
-        }
-        for (int v = 0; v < g.n_vars; ++v) {
-            const double x = h_eval_cost[h_coff[v] + idx[v]];
-            if (x != infinity) soft += x; else hard += 1;
-        }
-        if (cst) *cst = soft;
-        if (viol) *viol = hard;
-        return MXS_OK;
+        return hg.eval_cost(idx, infinity, cst, viol);
     }
 };
 
@@ -713,40 +538,27 @@ extern "C" {
 
 int mxs_dsa_create(const mxs_graph* g, const mxs_params* p, int32_t variant, double probability, int32_t arity_mode,
                    uint64_t seed, int32_t device, mxs_dsa** out) {
-    if (!g || !p || !out) return dsa::fail(MXS_E_INVALID, "null argument");
-    *out = nullptr;
-    try {
-        dsa::Base* impl = p->dtype == MXS_DTYPE_F32 ? (dsa::Base*)new dsa::Engine<float>() : (dsa::Base*)new dsa::Engine<double>();
-        int rc = impl->init(*g, *p, variant, probability, arity_mode, seed, device);
-        if (rc) {
-            delete impl;
-            return rc;
-        }
-        *out = new mxs_dsa{impl};
-        return MXS_OK;
-    } catch (const std::exception& ex) {
-        return dsa::fail(MXS_E_NOMEM, ex.what());
-    }
+    return mxs_host::create<mxs_dsa, dsa::Engine>(g, p, out, variant, probability, arity_mode, seed, device);
 }
-int mxs_dsa_reset(mxs_dsa* e) { return e ? e->impl->reset() : dsa::fail(MXS_E_INVALID, "null handle"); }
+int mxs_dsa_reset(mxs_dsa* e) { return e ? e->impl->reset() : mxs_host::fail(MXS_E_INVALID, "null handle"); }
 int mxs_dsa_set_value_rank(mxs_dsa* e, const int32_t* value_rank) {
-    return e ? e->impl->set_value_rank(value_rank) : dsa::fail(MXS_E_INVALID, "null handle");
+    return e ? e->impl->set_value_rank(value_rank) : mxs_host::fail(MXS_E_INVALID, "null handle");
 }
 int mxs_dsa_run(mxs_dsa* e, int32_t n_cycles) {
-    if (!e) return dsa::fail(MXS_E_INVALID, "null handle");
-    if (n_cycles < 0) return dsa::fail(MXS_E_INVALID, "negative cycle count");
+    if (!e) return mxs_host::fail(MXS_E_INVALID, "null handle");
+    if (n_cycles < 0) return mxs_host::fail(MXS_E_INVALID, "negative cycle count");
     return e->impl->run(n_cycles);
 }
 int mxs_dsa_cycles(const mxs_dsa* e, int64_t* cycles) {
-    if (!e) return dsa::fail(MXS_E_INVALID, "null handle");
+    if (!e) return mxs_host::fail(MXS_E_INVALID, "null handle");
     if (cycles) *cycles = e->impl->cycles;
     return MXS_OK;
 }
 int mxs_dsa_get_state(mxs_dsa* e, int32_t* idx, double* cost) {
-    return e ? e->impl->get_state(idx, cost) : dsa::fail(MXS_E_INVALID, "null handle");
+    return e ? e->impl->get_state(idx, cost) : mxs_host::fail(MXS_E_INVALID, "null handle");
 }
 int mxs_dsa_eval_cost(mxs_dsa* e, const int32_t* idx, double infinity, double* cost, int64_t* violations) {
-    return e ? e->impl->eval_cost(idx, infinity, cost, violations) : dsa::fail(MXS_E_INVALID, "null handle");
+    return e ? e->impl->eval_cost(idx, infinity, cost, violations) : mxs_host::fail(MXS_E_INVALID, "null handle");
 }
 int mxs_dsa_destroy(mxs_dsa* e) {
     if (e) {

@@ -22,14 +22,14 @@
 
 namespace gdba {
 
-using mgm::Buf;
-using mgm::fail;
-using mgm2::uniform;
+using mxs_host::Buf;
+using mxs_host::fail;
+using mxs_host::uniform;
 
 constexpr int TPB = 64;  // one wave per block, as mgm2.h: 100k variables spread over every CU
 constexpr int64_t MAX_ROUNDS = 65535;
 constexpr int64_t DEFAULT_POOL_BUDGET = (int64_t)4 << 30;
-// draw ids, after those of DSA (0..2) and MGM-2 (0..5): 6 start value (cycle 0), 7 one of the best values
+// draw ids (the table in engine_common.h): 6 start value (cycle 0), 7 one of the best values
 enum { D_START = 6, D_BEST = 7 };
 enum { MOD_A = 0, MOD_M = 1 };
 enum { VIO_NZ = 0, VIO_NM = 1, VIO_MX = 2 };
@@ -283,13 +283,12 @@ struct Engine : Base {
     hipStream_t stream = nullptr;
     Dev<T> g{};
     Plan plan;
-    std::vector<int32_t> h_dom, h_frow, h_evar, h_init, h_nb, h_vrow, h_vrank;
-    std::vector<int64_t> h_toff, h_coff;
-    std::vector<double> h_tables, h_eval_cost, h_var_cost;
+    mxs_host::HostGraph hg;
+    std::vector<int32_t> h_nb, h_vrank;
     lsearch::HostSlots hs;
     Buf<int32_t> dom, var_rowptr, has_nb, rank, conc_first, cur;
-    Buf<int64_t> sl_base, mod_off, cost_off;
-    Buf<int32_t> sl_stride_v, sl_nb_rowptr, sl_nb_var, sl_nb_stride, sl_conc_rowptr, sl_conc_var;
+    Buf<int64_t> mod_off, cost_off;
+    mxs_host::DevSlots sl;
     Buf<T> tables, vref, var_cost, cost, slot_vc;
     Buf<counter_t> pool;
     Buf<uint8_t> has_cost, viol;
@@ -302,58 +301,28 @@ struct Engine : Base {
     int init(const mxs_graph& G, const mxs_params& p, const int32_t* rk, const int32_t* vrk, int32_t modifier,
              int32_t violation, int32_t increase_mode, uint64_t seed, int64_t budget, int dev) override {
         device = dev;
-        int count = 0;
-        if (hipGetDeviceCount(&count) != hipSuccess || count <= 0)
-            return fail(MXS_E_NODEVICE, "no HIP device visible: the engine has no CPU fallback");
-        if (dev < 0 || dev >= count) return fail(MXS_E_INVALID, "device index out of range");
+        if (int rc = mxs_host::open_device(dev, &stream)) return rc;
         if (modifier < 0 || modifier > 1) return fail(MXS_E_INVALID, "gdba: modifier must be 0 (A) or 1 (M)");
         if (violation < 0 || violation > 2) return fail(MXS_E_INVALID, "gdba: violation must be 0 (NZ), 1 (NM) or 2 (MX)");
         if (increase_mode < 0 || increase_mode > 3)
             return fail(MXS_E_INVALID, "gdba: increase_mode must be 0 (E), 1 (R), 2 (C) or 3 (T)");
         if (budget < 0) return fail(MXS_E_INVALID, "gdba: negative pool budget");
         if (budget == 0) budget = DEFAULT_POOL_BUDGET;
-        MGM_TRY(hipSetDevice(dev));
-        MGM_TRY(hipStreamCreateWithFlags(&stream, 0));
-        const int nV = G.n_vars, nF = G.n_factors, nE = G.n_edges;
-        if (nV < 0 || nF < 0 || nE < 0) return fail(MXS_E_INVALID, "negative size");
-        if (p.mode != MXS_MODE_MIN && p.mode != MXS_MODE_MAX) return fail(MXS_E_INVALID, "invalid mode");
-        h_dom.assign(G.dom_size, G.dom_size + nV);
-        h_frow.assign(G.factor_rowptr, G.factor_rowptr + nF + 1);
-        h_evar.assign(G.edge_var, G.edge_var + nE);
-        h_toff.assign(G.table_off, G.table_off + nF + 1);
-        h_coff.assign(nV + 1, 0);
-        for (int v = 0; v < nV; ++v) {
-            if (h_dom[v] < 1) return fail(MXS_E_INVALID, "empty domain");
-            h_coff[v + 1] = h_coff[v] + h_dom[v];
-        }
-        for (int f = 0; f < nF; ++f) {
-            if (h_frow[f + 1] <= h_frow[f]) return fail(MXS_E_INVALID, "factor without variable");
-            if (h_toff[f + 1] <= h_toff[f]) return fail(MXS_E_INVALID, "empty table");
-            for (int e = h_frow[f]; e < h_frow[f + 1]; ++e)
-                if (h_evar[e] < 0 || h_evar[e] >= nV) return fail(MXS_E_INVALID, "edge_var out of range");
-        }
-        h_vrow.assign(G.var_rowptr, G.var_rowptr + nV + 1);
-        std::vector<int32_t> vedges(G.var_edges, G.var_edges + nE);
-        h_tables.assign(G.tables, G.tables + h_toff[nF]);
+        if (int rc = hg.load(G, p)) return rc;
+        const int nV = hg.nV, nF = hg.nF;
+        for (int f = 0; f < nF; ++f)
+            if (hg.toff[f + 1] <= hg.toff[f]) return fail(MXS_E_INVALID, "empty table");
         // maxi over NaN improvements depends on message arrival in the reference: no defined result
-        for (double t : h_tables)
+        for (double t : hg.tables)
             if (!std::isfinite(t)) return fail(MXS_E_INVALID, "gdba: constraint tables must be finite (no inf / NaN entries)");
-        h_var_cost.assign(G.var_cost, G.var_cost + h_coff[nV]);
         bool any_vc = false;
-        for (double c : h_var_cost) {
+        for (double c : hg.var_cost) {
             if (!std::isfinite(c)) return fail(MXS_E_INVALID, "gdba: variable costs must be finite (no inf / NaN entries)");
             any_vc |= c != 0.0;
         }
-        const double* ev = G.eval_var_cost ? G.eval_var_cost : G.var_cost;
-        h_eval_cost.assign(ev, ev + h_coff[nV]);
-        if (vrk) h_vrank.assign(vrk, vrk + h_coff[nV]);
-        h_init.assign(nV, -1);
-        if (G.init_idx)
-            for (int v = 0; v < nV; ++v) {
-                if (G.init_idx[v] >= h_dom[v]) return fail(MXS_E_INVALID, "init_idx out of the domain");
-                h_init[v] = G.init_idx[v];
-            }
-        const std::string bad = hs.build(nV, nF, h_dom, h_frow, h_evar, h_toff, h_vrow, vedges);
+        if (vrk) h_vrank.assign(vrk, vrk + hg.coff[nV]);
+        if (int rc = hg.load_init(G)) return rc;
+        const std::string bad = hs.build(nV, nF, hg.dom, hg.frow, hg.evar, hg.toff, hg.vrow, hg.vedges);
         if (!bad.empty()) return fail(MXS_E_INVALID, bad);
         // neighbours: the other variables of v's constraints (the concerned list holds v itself once); the
         // first slot of v's list that holds each concerned variable (v itself: slot 0, every scope holds it)
@@ -366,11 +335,11 @@ struct Engine : Base {
                 const int u = hs.conc_var[k];
                 int first = 0;
                 if (u != v)
-                    for (int s = h_vrow[v]; s < h_vrow[v + 1]; ++s) {
+                    for (int s = hg.vrow[v]; s < hg.vrow[v + 1]; ++s) {
                         bool in = false;
                         for (int q = hs.nb_rowptr[s]; q < hs.nb_rowptr[s + 1]; ++q) in |= hs.nb_var[q] == u;
                         if (in) {
-                            first = s - h_vrow[v];
+                            first = s - hg.vrow[v];
                             break;
                         }
                     }
@@ -378,7 +347,7 @@ struct Engine : Base {
             }
         }
         // the plan of the modifier pool, checked against the budget before anything is allocated
-        plan.build(increase_mode, h_dom, h_vrow, h_nb, hs);
+        plan.build(increase_mode, hg.dom, hg.vrow, h_nb, hs);
         if (plan.entries > budget / (int64_t)sizeof(counter_t))
             return fail(MXS_E_INVALID, "gdba: the modifier tables take " + std::to_string(plan.entries * (int64_t)sizeof(counter_t)) +
                                            " bytes, more than the budget of " + std::to_string(budget));
@@ -387,49 +356,36 @@ struct Engine : Base {
         if (violation != VIO_NZ) {
             std::vector<T> fref(nF);
             for (int f = 0; f < nF; ++f) {
-                T r = (T)h_tables[h_toff[f]];
-                for (int64_t i = h_toff[f]; i < h_toff[f + 1]; ++i) {
-                    const T t = (T)h_tables[i];
+                T r = (T)hg.tables[hg.toff[f]];
+                for (int64_t i = hg.toff[f]; i < hg.toff[f + 1]; ++i) {
+                    const T t = (T)hg.tables[i];
                     if (violation == VIO_NM ? t < r : t > r) r = t;
                 }
                 fref[f] = r;
             }
-            std::vector<int32_t> efac(nE);
-            for (int f = 0; f < nF; ++f)
-                for (int e = h_frow[f]; e < h_frow[f + 1]; ++e) efac[e] = f;
-            for (size_t s = 0; s < h_vref.size(); ++s) h_vref[s] = fref[efac[vedges[s]]];
+            for (size_t s = 0; s < h_vref.size(); ++s) h_vref[s] = fref[hg.efac[hg.vedges[s]]];
         }
         std::vector<int32_t> h_rank(nV);
         for (int v = 0; v < nV; ++v) h_rank[v] = rk ? rk[v] : v;
-        std::vector<T> tt(h_tables.size()), vc(h_var_cost.size());
-        for (size_t i = 0; i < tt.size(); ++i) tt[i] = (T)h_tables[i];
-        for (size_t i = 0; i < vc.size(); ++i) vc[i] = (T)h_var_cost[i];
-        MGM_TRY(sl_base.upload(hs.base, stream));
-        MGM_TRY(sl_stride_v.upload(hs.stride_v, stream));
-        MGM_TRY(sl_nb_rowptr.upload(hs.nb_rowptr, stream));
-        MGM_TRY(sl_nb_var.upload(hs.nb_var, stream));
-        MGM_TRY(sl_nb_stride.upload(hs.nb_stride, stream));
-        MGM_TRY(sl_conc_rowptr.upload(hs.conc_rowptr, stream));
-        MGM_TRY(sl_conc_var.upload(hs.conc_var, stream));
-        MGM_TRY(conc_first.upload(h_first, stream));
-        MGM_TRY(dom.upload(h_dom, stream));
-        MGM_TRY(var_rowptr.upload(h_vrow, stream));
-        MGM_TRY(has_nb.upload(h_nb, stream));
-        MGM_TRY(rank.upload(h_rank, stream));
-        MGM_TRY(tables.upload(tt, stream));
-        MGM_TRY(vref.upload(h_vref, stream));
-        MGM_TRY(var_cost.upload(vc, stream));
-        MGM_TRY(cost_off.upload(h_coff, stream));
-        MGM_TRY(mod_off.upload(plan.mod_off, stream));
-        MGM_TRY(pool.alloc((size_t)plan.entries));
-        MGM_TRY(cur.alloc(nV));
-        MGM_TRY(cost.alloc(nV));
-        MGM_TRY(has_cost.alloc(nV));
-        MGM_TRY(rec.alloc(nV));
-        MGM_TRY(viol.alloc(hs.base.size()));
-        MGM_TRY(slot_vc.alloc(any_vc ? hs.base.size() : 0));
-        g.slots = lsearch::Slots{sl_base.p, sl_stride_v.p, sl_nb_rowptr.p, sl_nb_var.p, sl_nb_stride.p, nullptr, nullptr,
-                                 sl_conc_rowptr.p, sl_conc_var.p, nullptr, nullptr, nullptr, nullptr, 0};
+        if (int rc = sl.upload(hs, stream, nullptr, false)) return rc;  // no first-neighbour arrays, no rows
+        MXS_TRY(conc_first.upload(h_first, stream));
+        MXS_TRY(dom.upload(hg.dom, stream));
+        MXS_TRY(var_rowptr.upload(hg.vrow, stream));
+        MXS_TRY(has_nb.upload(h_nb, stream));
+        MXS_TRY(rank.upload(h_rank, stream));
+        MXS_TRY(tables.upload(mxs_host::narrowed<T>(hg.tables), stream));
+        MXS_TRY(vref.upload(h_vref, stream));
+        MXS_TRY(var_cost.upload(mxs_host::narrowed<T>(hg.var_cost), stream));
+        MXS_TRY(cost_off.upload(hg.coff, stream));
+        MXS_TRY(mod_off.upload(plan.mod_off, stream));
+        MXS_TRY(pool.alloc((size_t)plan.entries));
+        MXS_TRY(cur.alloc(nV));
+        MXS_TRY(cost.alloc(nV));
+        MXS_TRY(has_cost.alloc(nV));
+        MXS_TRY(rec.alloc(nV));
+        MXS_TRY(viol.alloc(hs.base.size()));
+        MXS_TRY(slot_vc.alloc(any_vc ? hs.base.size() : 0));
+        g.slots = sl.view();
         g.n_vars = nV;
         g.is_max = p.mode == MXS_MODE_MAX;
         g.modifier = modifier;
@@ -460,7 +416,7 @@ struct Engine : Base {
     // on_start (:302-333): a variable with neighbours takes its initial value or a random one (held cost None);
     // one without takes optimal_cost_value (min / max over (cost, value) tuples, relations.py:1661-1665)
     int reset() override {
-        MGM_TRY(hipSetDevice(device));
+        MXS_TRY(hipSetDevice(device));
         const int nV = g.n_vars;
         std::vector<int32_t> c0(nV);
         std::vector<T> k0(nV, (T)0);
@@ -468,37 +424,31 @@ struct Engine : Base {
         std::vector<Rec<T>> r0(nV);
         for (int v = 0; v < nV; ++v) {
             if (h_nb[v]) {
-                c0[v] = h_init[v] >= 0 ? h_init[v] : (int)(uniform(g.seed, v, 0, D_START) * h_dom[v]);
+                c0[v] = hg.init[v] >= 0 ? hg.init[v] : (int)(uniform(g.seed, v, 0, D_START) * hg.dom[v]);
             } else {
-                const int32_t* rk = h_vrank.empty() ? nullptr : h_vrank.data() + h_coff[v];
-                int best = 0;
-                for (int d = 1; d < h_dom[v]; ++d) {
-                    const T a = (T)h_var_cost[h_coff[v] + d], b = (T)h_var_cost[h_coff[v] + best];
-                    const int rd = rk ? rk[d] : d, rb = rk ? rk[best] : best;
-                    if (g.is_max ? (a > b || (a == b && rd > rb)) : (a < b || (a == b && rd < rb))) best = d;
-                }
+                const int best = hg.optimal_cost_value<T>(v, g.is_max, h_vrank);
                 c0[v] = best;
-                k0[v] = (T)h_var_cost[h_coff[v] + best];
+                k0[v] = (T)hg.var_cost[hg.coff[v] + best];
                 h0[v] = 1;
             }
             r0[v].improve = (T)0;
             r0[v].newv = c0[v];
         }
         if (nV) {
-            MGM_TRY(hipMemcpyAsync(cur.p, c0.data(), 4 * (size_t)nV, hipMemcpyHostToDevice, stream));
-            MGM_TRY(hipMemcpyAsync(cost.p, k0.data(), sizeof(T) * nV, hipMemcpyHostToDevice, stream));
-            MGM_TRY(hipMemcpyAsync(has_cost.p, h0.data(), nV, hipMemcpyHostToDevice, stream));
-            MGM_TRY(hipMemcpyAsync(rec.p, r0.data(), sizeof(Rec<T>) * nV, hipMemcpyHostToDevice, stream));
+            MXS_TRY(hipMemcpyAsync(cur.p, c0.data(), 4 * (size_t)nV, hipMemcpyHostToDevice, stream));
+            MXS_TRY(hipMemcpyAsync(cost.p, k0.data(), sizeof(T) * nV, hipMemcpyHostToDevice, stream));
+            MXS_TRY(hipMemcpyAsync(has_cost.p, h0.data(), nV, hipMemcpyHostToDevice, stream));
+            MXS_TRY(hipMemcpyAsync(rec.p, r0.data(), sizeof(Rec<T>) * nV, hipMemcpyHostToDevice, stream));
         }
-        if (plan.entries) MGM_TRY(hipMemsetAsync(pool.p, 0, sizeof(counter_t) * (size_t)plan.entries, stream));
-        if (!hs.base.empty()) MGM_TRY(hipMemsetAsync(viol.p, 0, hs.base.size(), stream));
-        MGM_TRY(hipStreamSynchronize(stream));
+        if (plan.entries) MXS_TRY(hipMemsetAsync(pool.p, 0, sizeof(counter_t) * (size_t)plan.entries, stream));
+        if (!hs.base.empty()) MXS_TRY(hipMemsetAsync(viol.p, 0, hs.base.size(), stream));
+        MXS_TRY(hipStreamSynchronize(stream));
         rounds = 0;
         return MXS_OK;
     }
 
     int run(int32_t n) override {
-        MGM_TRY(hipSetDevice(device));
+        MXS_TRY(hipSetDevice(device));
         if (rounds + (int64_t)n > MAX_ROUNDS)
             return fail(MXS_E_INVALID, "gdba: the modifier counters are 16 bits wide, at most 65535 rounds");
         const int nV = g.n_vars;
@@ -510,28 +460,28 @@ struct Engine : Base {
         for (int32_t r = 0; r < n; ++r) {
             g.round = rounds + 1;
             hipLaunchKernelGGL((k_gdba_eval<T>), grid, block, 0, stream, g);
-            MGM_TRY(hipGetLastError());
+            MXS_TRY(hipGetLastError());
             hipLaunchKernelGGL((k_gdba_decide<T>), grid, block, 0, stream, g);
-            MGM_TRY(hipGetLastError());
+            MXS_TRY(hipGetLastError());
             rounds += 1;
         }
-        MGM_TRY(hipStreamSynchronize(stream));
+        MXS_TRY(hipStreamSynchronize(stream));
         return MXS_OK;
     }
 
     int get_state(int32_t* idx, double* cst, uint8_t* has, double* imp, int32_t* nv) override {
-        MGM_TRY(hipSetDevice(device));
+        MXS_TRY(hipSetDevice(device));
         const int nV = g.n_vars;
         if (!nV) return MXS_OK;
         std::vector<T> hc(nV);
         std::vector<int32_t> hi(nV);
         std::vector<uint8_t> hh(nV);
         std::vector<Rec<T>> hr(nV);
-        MGM_TRY(hipMemcpyAsync(hi.data(), cur.p, 4 * (size_t)nV, hipMemcpyDeviceToHost, stream));
-        MGM_TRY(hipMemcpyAsync(hh.data(), has_cost.p, nV, hipMemcpyDeviceToHost, stream));
-        MGM_TRY(hipMemcpyAsync(hc.data(), cost.p, sizeof(T) * nV, hipMemcpyDeviceToHost, stream));
-        MGM_TRY(hipMemcpyAsync(hr.data(), rec.p, sizeof(Rec<T>) * nV, hipMemcpyDeviceToHost, stream));
-        MGM_TRY(hipStreamSynchronize(stream));
+        MXS_TRY(hipMemcpyAsync(hi.data(), cur.p, 4 * (size_t)nV, hipMemcpyDeviceToHost, stream));
+        MXS_TRY(hipMemcpyAsync(hh.data(), has_cost.p, nV, hipMemcpyDeviceToHost, stream));
+        MXS_TRY(hipMemcpyAsync(hc.data(), cost.p, sizeof(T) * nV, hipMemcpyDeviceToHost, stream));
+        MXS_TRY(hipMemcpyAsync(hr.data(), rec.p, sizeof(Rec<T>) * nV, hipMemcpyDeviceToHost, stream));
+        MXS_TRY(hipStreamSynchronize(stream));
         for (int v = 0; v < nV; ++v) {
             if (idx) idx[v] = hi[v];
             if (has) has[v] = hh[v];
@@ -554,10 +504,10 @@ struct Engine : Base {
         if (n) *n = cnt;
         if (!out || cnt == 0) return MXS_OK;
         if (capacity < cnt) return fail(MXS_E_INVALID, "gdba: buffer too small for the slot's modifiers");
-        MGM_TRY(hipSetDevice(device));
+        MXS_TRY(hipSetDevice(device));
         std::vector<counter_t> h((size_t)cnt);
-        MGM_TRY(hipMemcpyAsync(h.data(), pool.p + plan.mod_off[slot], sizeof(counter_t) * (size_t)cnt, hipMemcpyDeviceToHost, stream));
-        MGM_TRY(hipStreamSynchronize(stream));
+        MXS_TRY(hipMemcpyAsync(h.data(), pool.p + plan.mod_off[slot], sizeof(counter_t) * (size_t)cnt, hipMemcpyDeviceToHost, stream));
+        MXS_TRY(hipStreamSynchronize(stream));
         for (int64_t i = 0; i < cnt; ++i) out[i] = g.modifier + (int32_t)h[(size_t)i];
         return MXS_OK;
     }
@@ -571,26 +521,7 @@ struct Engine : Base {
             if (rc) return rc;
             idx = c.data();
         }
-        double soft = 0;
-        int64_t hard = 0;
-        const int nF = (int)h_frow.size() - 1;
-        for (int f = 0; f < nF; ++f) {
-            int64_t lin = 0;
-            for (int e = h_frow[f]; e < h_frow[f + 1]; ++e) {
-                const int v = h_evar[e];
-                if (idx[v] < 0 || idx[v] >= h_dom[v]) return fail(MXS_E_INVALID, "assignment index out of the domain");
-                lin = lin * h_dom[v] + idx[v];
-            }
-            const double r = h_tables[h_toff[f] + lin];
-            if (r != infinity) soft += r; else hard += 1;
-        }
-        for (int v = 0; v < g.n_vars; ++v) {
-            const double x = h_eval_cost[h_coff[v] + idx[v]];
-            if (x != infinity) soft += x; else hard += 1;
-        }
-        if (cst) *cst = soft;
-        if (viol_out) *viol_out = hard;
-        return MXS_OK;
+        return hg.eval_cost(idx, infinity, cst, viol_out);
     }
 };
 
@@ -605,41 +536,28 @@ extern "C" {
 int mxs_gdba_create(const mxs_graph* g, const mxs_params* p, const int32_t* name_rank, const int32_t* value_rank,
                     int32_t modifier, int32_t violation, int32_t increase_mode, uint64_t seed, int64_t pool_budget_bytes,
                     int32_t device, mxs_gdba** out) {
-    if (!g || !p || !out) return mgm::fail(MXS_E_INVALID, "null argument");
-    *out = nullptr;
-    try {
-        gdba::Base* impl = p->dtype == MXS_DTYPE_F32 ? (gdba::Base*)new gdba::Engine<float>()
-                                                     : (gdba::Base*)new gdba::Engine<double>();
-        int rc = impl->init(*g, *p, name_rank, value_rank, modifier, violation, increase_mode, seed, pool_budget_bytes, device);
-        if (rc) {
-            delete impl;
-            return rc;
-        }
-        *out = new mxs_gdba{impl};
-        return MXS_OK;
-    } catch (const std::exception& ex) {
-        return mgm::fail(MXS_E_NOMEM, ex.what());
-    }
+    return mxs_host::create<mxs_gdba, gdba::Engine>(g, p, out, name_rank, value_rank, modifier, violation, increase_mode, seed,
+                                                    pool_budget_bytes, device);
 }
-int mxs_gdba_reset(mxs_gdba* e) { return e ? e->impl->reset() : mgm::fail(MXS_E_INVALID, "null handle"); }
+int mxs_gdba_reset(mxs_gdba* e) { return e ? e->impl->reset() : mxs_host::fail(MXS_E_INVALID, "null handle"); }
 int mxs_gdba_run(mxs_gdba* e, int32_t n_rounds) {
-    if (!e) return mgm::fail(MXS_E_INVALID, "null handle");
-    if (n_rounds < 0) return mgm::fail(MXS_E_INVALID, "negative round count");
+    if (!e) return mxs_host::fail(MXS_E_INVALID, "null handle");
+    if (n_rounds < 0) return mxs_host::fail(MXS_E_INVALID, "negative round count");
     return e->impl->run(n_rounds);
 }
 int mxs_gdba_rounds(const mxs_gdba* e, int64_t* rounds) {
-    if (!e) return mgm::fail(MXS_E_INVALID, "null handle");
+    if (!e) return mxs_host::fail(MXS_E_INVALID, "null handle");
     if (rounds) *rounds = e->impl->rounds;
     return MXS_OK;
 }
 int mxs_gdba_get_state(mxs_gdba* e, int32_t* idx, double* cost, uint8_t* has_cost, double* improve, int32_t* new_value) {
-    return e ? e->impl->get_state(idx, cost, has_cost, improve, new_value) : mgm::fail(MXS_E_INVALID, "null handle");
+    return e ? e->impl->get_state(idx, cost, has_cost, improve, new_value) : mxs_host::fail(MXS_E_INVALID, "null handle");
 }
 int mxs_gdba_get_modifiers(mxs_gdba* e, int32_t slot, int32_t* out, int64_t capacity, int64_t* n_entries) {
-    return e ? e->impl->get_modifiers(slot, out, capacity, n_entries) : mgm::fail(MXS_E_INVALID, "null handle");
+    return e ? e->impl->get_modifiers(slot, out, capacity, n_entries) : mxs_host::fail(MXS_E_INVALID, "null handle");
 }
 int mxs_gdba_eval_cost(mxs_gdba* e, const int32_t* idx, double infinity, double* cost, int64_t* violations) {
-    return e ? e->impl->eval_cost(idx, infinity, cost, violations) : mgm::fail(MXS_E_INVALID, "null handle");
+    return e ? e->impl->eval_cost(idx, infinity, cost, violations) : mxs_host::fail(MXS_E_INVALID, "null handle");
 }
 int mxs_gdba_destroy(mxs_gdba* e) {
     if (e) {

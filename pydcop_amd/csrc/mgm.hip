@@ -26,50 +26,15 @@
 #include <vector>
 
 #include "../../include/maxsum_gpu.h"
+#include "engine_common.h"
 #include "local_search.h"
-
-extern "C" __attribute__((visibility("hidden"))) void mxs_set_last_error(const char* msg);  // engine.hip
 
 namespace mgm {
 
+using mxs_host::Buf;
+using mxs_host::fail;
+
 constexpr int TPB = 64;  // one wave per block: 100k variables spread over every CU (latency-bound CSR walks)
-
-static int fail(int code, const std::string& msg) {
-    mxs_set_last_error(msg.c_str());
-    return code;
-}
-#define MGM_TRY(call)                                                                     \
-    do {                                                                                  \
-        hipError_t e__ = (call);                                                          \
-        if (e__ != hipSuccess) return fail(MXS_E_HIP, std::string(#call) + " failed");     \
-    } while (0)
-
-template <typename U>
-struct Buf {
-    U* p = nullptr;
-    size_t n = 0;
-    hipError_t upload(const std::vector<U>& h, hipStream_t st) {
-        release();
-        n = h.size();
-        hipError_t e = hipMalloc((void**)&p, (n ? n : 1) * sizeof(U));
-        if (e != hipSuccess || h.empty()) return e;
-        e = hipMemcpyAsync(p, h.data(), n * sizeof(U), hipMemcpyHostToDevice, st);
-        if (e != hipSuccess) return e;
-        return hipStreamSynchronize(st);
-    }
-    hipError_t alloc(size_t count) {
-        n = count;
-        return hipMalloc((void**)&p, (n ? n : 1) * sizeof(U));
-    }
-    void release() {
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        n = 0;
-    }
-    ~Buf() {
-        if (p) (void)hipFree(p);
-    }
-};
 
 template <typename T>
 struct alignas(16) GainRec {
@@ -469,29 +434,18 @@ struct Engine : Base {
     hipStream_t stream = nullptr;
     Dev<T> g{};
     int which = 0;
-    std::vector<int32_t> h_dom, h_frow, h_evar, h_init, h_nn, h_rank, h_q, h_vrank;
-    std::vector<int64_t> h_toff, h_coff;
-    std::vector<double> h_tables, h_eval_cost, h_var_cost;
-    bool has_init = false;
-    Buf<int32_t> dom_size, factor_rowptr, edge_var, edge_factor, var_rowptr, var_edges, init_idx, name_rank, n_neigh;
+    mxs_host::HostGraph hg;
+    std::vector<int32_t> h_nn, h_rank, h_q, h_vrank;
+    Buf<int32_t> dom_size, factor_rowptr, edge_var, edge_factor, var_rowptr, var_edges, name_rank, n_neigh, qmap;
     Buf<int32_t> cur[2];
     Buf<int64_t> table_off, cost_off;
     Buf<T> tables, var_cost;
     Buf<T> cost[2], vcc[2], vc4;
     Buf<GainRec<T>> grec;
     Buf<uint8_t> has_cost;
-    Buf<int64_t> sl_base;
-    Buf<int32_t> sl_stride_v, sl_nb_rowptr, sl_nb_var, sl_nb_stride, sl_nb0_var, sl_nb0_stride, sl_conc_rowptr, sl_conc_var;
-    Buf<uint8_t> sl_rows;           // the row view of the variables the pack cannot take (local_search.h, Slots::rows)
-    Buf<int64_t> sl_row_base;
-    Buf<int32_t> sl_row_nb_stride, sl_row_nb0_stride;
-    bool have_rows = false;
-    Buf<lsearch::PackWave> pk_waves;
-    Buf<int32_t> pk_nb, pk_slot, pk_rest, pk_conc, pk_conc_x, pk_dom, qmap;
-    Buf<int8_t> pk_rec8;
-    Buf<T> pk_recT;
-    bool pack_int8 = false;
-    int n_rest = 0;
+    mxs_host::DevSlots sl;
+    mxs_host::DevPack<T> pk;
+    Buf<int32_t> pk_conc, pk_conc_x;  // what only MGM keeps per lane (Dev::pack_conc, pack_conc_x)
     int max_dom = 0;
 
     ~Engine() override {
@@ -500,91 +454,34 @@ struct Engine : Base {
 
     int init(const mxs_graph& G, const mxs_params& p, const int32_t* rank, int dev) override {
         device = dev;
-        int count = 0;
-        if (hipGetDeviceCount(&count) != hipSuccess || count <= 0)
-            return fail(MXS_E_NODEVICE, "no HIP device visible: the engine has no CPU fallback");
-        if (dev < 0 || dev >= count) return fail(MXS_E_INVALID, "device index out of range");
-        MGM_TRY(hipSetDevice(dev));
-        MGM_TRY(hipStreamCreateWithFlags(&stream, 0));
-        const int nV = G.n_vars, nF = G.n_factors, nE = G.n_edges;
-        if (nV < 0 || nF < 0 || nE < 0) return fail(MXS_E_INVALID, "negative size");
-        if (p.mode != MXS_MODE_MIN && p.mode != MXS_MODE_MAX) return fail(MXS_E_INVALID, "invalid mode");
-        h_dom.assign(G.dom_size, G.dom_size + nV);
-        h_frow.assign(G.factor_rowptr, G.factor_rowptr + nF + 1);
-        h_evar.assign(G.edge_var, G.edge_var + nE);
-        h_toff.assign(G.table_off, G.table_off + nF + 1);
-        h_coff.assign(nV + 1, 0);
-        for (int v = 0; v < nV; ++v) {
-            if (h_dom[v] < 1) return fail(MXS_E_INVALID, "empty domain");
-            h_coff[v + 1] = h_coff[v] + h_dom[v];
-        }
-        std::vector<int32_t> efac(nE), vrow(G.var_rowptr, G.var_rowptr + nV + 1), vedges(G.var_edges, G.var_edges + nE);
-        for (int f = 0; f < nF; ++f) {
-            if (h_frow[f + 1] <= h_frow[f]) return fail(MXS_E_INVALID, "factor without variable");
-            for (int e = h_frow[f]; e < h_frow[f + 1]; ++e) {
-                if (h_evar[e] < 0 || h_evar[e] >= nV) return fail(MXS_E_INVALID, "edge_var out of range");
-                efac[e] = f;
-            }
-        }
+        if (int rc = mxs_host::open_device(dev, &stream)) return rc;
+        if (int rc = hg.load(G, p)) return rc;
+        const int nV = hg.nV, nF = hg.nF;
+        const std::vector<int32_t> &efac = hg.efac, &vrow = hg.vrow, &vedges = hg.vedges;
         h_nn.assign(nV, 0);
         for (int f = 0; f < nF; ++f)
-            if (h_frow[f + 1] - h_frow[f] > 1)
-                for (int e = h_frow[f]; e < h_frow[f + 1]; ++e) h_nn[h_evar[e]] = 1;
+            if (hg.frow[f + 1] - hg.frow[f] > 1)
+                for (int e = hg.frow[f]; e < hg.frow[f + 1]; ++e) h_nn[hg.evar[e]] = 1;
         std::vector<int32_t> rk(nV);
         for (int v = 0; v < nV; ++v) rk[v] = rank ? rank[v] : v;
-        has_init = G.init_idx != nullptr;
-        h_init.assign(nV, -1);
-        if (has_init)
-            for (int v = 0; v < nV; ++v) {
-                if (G.init_idx[v] >= h_dom[v]) return fail(MXS_E_INVALID, "init_idx out of the domain");
-                h_init[v] = G.init_idx[v];
-            }
-        h_tables.assign(G.tables, G.tables + h_toff[nF]);
-        h_var_cost.assign(G.var_cost, G.var_cost + h_coff[nV]);
-        const double* ev = G.eval_var_cost ? G.eval_var_cost : G.var_cost;
-        h_eval_cost.assign(ev, ev + h_coff[nV]);
-        std::vector<T> tt(h_tables.size()), vc(h_var_cost.size());
-        for (size_t i = 0; i < tt.size(); ++i) tt[i] = (T)h_tables[i];
-        for (size_t i = 0; i < vc.size(); ++i) vc[i] = (T)h_var_cost[i];
+        if (int rc = hg.load_init(G)) return rc;
+        const std::vector<T> tt = mxs_host::narrowed<T>(hg.tables), vc = mxs_host::narrowed<T>(hg.var_cost);
         lsearch::HostSlots hs;
-        const std::string bad = hs.build(nV, nF, h_dom, h_frow, h_evar, h_toff, vrow, vedges);
+        const std::string bad = hs.build(nV, nF, hg.dom, hg.frow, hg.evar, hg.toff, vrow, vedges);
         if (!bad.empty()) return fail(MXS_E_INVALID, bad);
         max_dom = 0;
-        for (int v = 0; v < nV; ++v) max_dom = h_dom[v] > max_dom ? h_dom[v] : max_dom;
-        MGM_TRY(sl_base.upload(hs.base, stream));
-        MGM_TRY(sl_stride_v.upload(hs.stride_v, stream));
-        MGM_TRY(sl_nb_rowptr.upload(hs.nb_rowptr, stream));
-        MGM_TRY(sl_nb_stride.upload(hs.nb_stride, stream));
-        MGM_TRY(sl_nb0_stride.upload(hs.nb0_stride, stream));
+        for (int v = 0; v < nV; ++v) max_dom = hg.dom[v] > max_dom ? hg.dom[v] : max_dom;
         {   // the packed view of the variables it can take (local_search.h)
             lsearch::HostPack hp;
-            hp.build(nV, h_dom, vrow, h_nn, hs, h_tables);
-            // packed positions (Dev::q): the packed variables in wave order, then the others
-            h_q.assign(nV, -1);
-            int nq = 0;
-            for (int v : hp.vars) h_q[v] = nq++;
-            const int n_packed = nq;
-            for (int v = 0; v < nV; ++v)
-                if (h_q[v] < 0) h_q[v] = nq++;
-            auto to_q = [&](std::vector<int32_t> a) {
-                for (auto& x : a)
-                    if (x >= 0) x = h_q[x];
-                return a;
-            };
-            MGM_TRY(qmap.upload(h_q, stream));
-            MGM_TRY(sl_nb_var.upload(to_q(hs.nb_var), stream));
-            MGM_TRY(sl_nb0_var.upload(to_q(hs.nb0_var), stream));
-            MGM_TRY(sl_conc_var.upload(to_q(hs.conc_var), stream));
-            std::vector<int32_t> pdom(n_packed);
-            std::vector<T> v4((size_t)n_packed * lsearch::PACK_D, (T)0);
-            for (int v : hp.vars) {
-                pdom[h_q[v]] = h_dom[v];
-                for (int x = 0; x < h_dom[v]; ++x) v4[(size_t)h_q[v] * lsearch::PACK_D + x] = vc[h_coff[v] + x];
-            }
-            MGM_TRY(pk_dom.upload(pdom, stream));
-            MGM_TRY(vc4.upload(v4, stream));
+            hp.build(nV, hg.dom, vrow, h_nn, hs, hg.tables);
+            h_q = mxs_host::packed_order(hp, nV);
+            MXS_TRY(qmap.upload(h_q, stream));
+            if (int rc = sl.upload(hs, stream, &h_q, true)) return rc;
+            std::vector<T> v4(hp.vars.size() * lsearch::PACK_D, (T)0);
+            for (int v : hp.vars)
+                for (int x = 0; x < hg.dom[v]; ++x) v4[(size_t)h_q[v] * lsearch::PACK_D + x] = vc[hg.coff[v] + x];
+            MXS_TRY(vc4.upload(v4, stream));
             g.q = qmap.p;
-            g.pack_dom = pk_dom.p;
             g.vc4 = vc4.p;
             std::vector<int32_t> conc(hp.nb.size(), -1), conc_x(hp.nb.size(), -1);
             for (size_t i = 0; i < hp.nb.size(); ++i) {
@@ -595,72 +492,36 @@ struct Engine : Base {
                 if (k < n_conc) conc[i] = hs.conc_var[c0 + k];
                 if (k == 0 && n_conc > deg) conc_x[i] = hs.conc_var[c0 + deg];
             }
-            pack_int8 = hp.int8_exact;
-            if (pack_int8) {
-                std::vector<int8_t> r8(hp.rec.size());
-                for (size_t i = 0; i < r8.size(); ++i) r8[i] = (int8_t)hp.rec[i];
-                MGM_TRY(pk_rec8.upload(r8, stream));
-            } else {
-                std::vector<T> rt(hp.rec.size());
-                for (size_t i = 0; i < rt.size(); ++i) rt[i] = (T)hp.rec[i];
-                MGM_TRY(pk_recT.upload(rt, stream));
-            }
-            MGM_TRY(pk_waves.upload(hp.waves, stream));
-            MGM_TRY(pk_nb.upload(to_q(hp.nb), stream));
-            MGM_TRY(pk_slot.upload(hp.slot, stream));
-            MGM_TRY(pk_rest.upload(hp.rest, stream));
-            MGM_TRY(pk_conc.upload(to_q(conc), stream));
-            MGM_TRY(pk_conc_x.upload(to_q(conc_x), stream));
-            n_rest = (int)hp.rest.size();
-            // the row view for them (domains of at most 32 values; $MAXSUM_LOCAL_SEARCH_ROWS=0 leaves it out, the
-            // budget in bytes can be set: A/B runs and tests)
-            {
-                const int64_t budget = lsearch::HostSlots::rows_budget();
-                have_rows = budget > 0 && max_dom <= 32 && hs.build_rows(hp.rest, h_dom, vrow, h_toff, h_tables, (int)sizeof(T), 32, budget);
-                if (have_rows) {
-                    // an upload that fails (device memory) leaves the strided path: free what was allocated and carry on
-                    const bool ok = sl_rows.upload(hs.rows, stream) == hipSuccess && sl_row_base.upload(hs.row_base, stream) == hipSuccess &&
-                                    sl_row_nb_stride.upload(hs.row_nb_stride, stream) == hipSuccess &&
-                                    sl_row_nb0_stride.upload(hs.row_nb0_stride, stream) == hipSuccess;
-                    if (!ok) {
-                        (void)hipGetLastError();
-                        sl_rows.release(), sl_row_base.release(), sl_row_nb_stride.release(), sl_row_nb0_stride.release();
-                        have_rows = false;
-                    }
-                    hs.rows.clear();
-                    hs.rows.shrink_to_fit();
-                }
-            }
-            g.pack = lsearch::Pack{pk_waves.p, pk_nb.p, pk_slot.p,
-                                   pack_int8 ? (const void*)pk_rec8.p : (const void*)pk_recT.p, (int32_t)hp.nb.size()};
+            if (int rc = pk.upload(hp, h_q, hg.dom, stream)) return rc;
+            MXS_TRY(pk_conc.upload(mxs_host::remap(conc, h_q), stream));
+            MXS_TRY(pk_conc_x.upload(mxs_host::remap(conc_x, h_q), stream));
+            sl.upload_rows(hs, hp.rest, hg, max_dom, (int)sizeof(T), stream);
+            g.pack = pk.view();
+            g.pack_dom = pk.dom.p;
             g.pack_conc = pk_conc.p;
             g.pack_conc_x = pk_conc_x.p;
         }
-        MGM_TRY(sl_conc_rowptr.upload(hs.conc_rowptr, stream));
-        g.slots = lsearch::Slots{sl_base.p, sl_stride_v.p, sl_nb_rowptr.p, sl_nb_var.p, sl_nb_stride.p,
-                                 sl_nb0_var.p, sl_nb0_stride.p, sl_conc_rowptr.p, sl_conc_var.p,
-                                 have_rows ? sl_rows.p : nullptr, sl_row_base.p, sl_row_nb_stride.p, sl_row_nb0_stride.p,
-                                 hs.rows_int8 ? 1 : 0};
-        MGM_TRY(dom_size.upload(h_dom, stream));
-        MGM_TRY(factor_rowptr.upload(h_frow, stream));
-        MGM_TRY(edge_var.upload(h_evar, stream));
-        MGM_TRY(edge_factor.upload(efac, stream));
-        MGM_TRY(var_rowptr.upload(vrow, stream));
-        MGM_TRY(var_edges.upload(vedges, stream));
-        MGM_TRY(name_rank.upload(rk, stream));
-        MGM_TRY(n_neigh.upload(h_nn, stream));
-        MGM_TRY(table_off.upload(h_toff, stream));
-        MGM_TRY(cost_off.upload(h_coff, stream));
-        MGM_TRY(tables.upload(tt, stream));
-        MGM_TRY(var_cost.upload(vc, stream));
+        g.slots = sl.view();
+        MXS_TRY(dom_size.upload(hg.dom, stream));
+        MXS_TRY(factor_rowptr.upload(hg.frow, stream));
+        MXS_TRY(edge_var.upload(hg.evar, stream));
+        MXS_TRY(edge_factor.upload(efac, stream));
+        MXS_TRY(var_rowptr.upload(vrow, stream));
+        MXS_TRY(var_edges.upload(vedges, stream));
+        MXS_TRY(name_rank.upload(rk, stream));
+        MXS_TRY(n_neigh.upload(h_nn, stream));
+        MXS_TRY(table_off.upload(hg.toff, stream));
+        MXS_TRY(cost_off.upload(hg.coff, stream));
+        MXS_TRY(tables.upload(tt, stream));
+        MXS_TRY(var_cost.upload(vc, stream));
         for (int b = 0; b < 2; ++b) {
-            MGM_TRY(cur[b].alloc(nV));
-            MGM_TRY(cost[b].alloc(nV));
-            MGM_TRY(vcc[b].alloc(nV));
+            MXS_TRY(cur[b].alloc(nV));
+            MXS_TRY(cost[b].alloc(nV));
+            MXS_TRY(vcc[b].alloc(nV));
         }
         h_rank = rk;
-        MGM_TRY(grec.alloc(nV));
-        MGM_TRY(has_cost.alloc(nV));
+        MXS_TRY(grec.alloc(nV));
+        MXS_TRY(has_cost.alloc(nV));
         g.n_vars = nV;
         g.is_max = p.mode == MXS_MODE_MAX;
         g.dom_size = dom_size.p; g.factor_rowptr = factor_rowptr.p; g.edge_var = edge_var.p;
@@ -674,13 +535,13 @@ struct Engine : Base {
     // the order of every variable's domain values (include/maxsum_gpu.h): cost ties of a variable without
     // neighbours break on the value, as the reference's optimal_cost_value does
     int set_value_rank(const int32_t* rank) override {
-        if (rank) h_vrank.assign(rank, rank + h_coff[g.n_vars]);
+        if (rank) h_vrank.assign(rank, rank + hg.coff[g.n_vars]);
         else h_vrank.clear();
         return reset();
     }
 
     int reset() override {
-        MGM_TRY(hipSetDevice(device));
+        MXS_TRY(hipSetDevice(device));
         const int nV = g.n_vars;
         std::vector<int32_t> c0(nV);  // (all in packed order, Dev::q)
         std::vector<T> k0(nV, (T)0), v0(nV, (T)0);
@@ -689,39 +550,33 @@ struct Engine : Base {
         for (int v = 0; v < nV; ++v) {
             const int qv = h_q[v];
             if (h_nn[v] == 0) {  // on_start without neighbours: optimal_cost_value (mgm.py:279-290)
-                const int32_t* rk = h_vrank.empty() ? nullptr : h_vrank.data() + h_coff[v];
-                int best = 0;
-                for (int d = 1; d < h_dom[v]; ++d) {  // min / max over (cost, value) tuples, relations.py:1661-1665
-                    const T a = (T)h_var_cost[h_coff[v] + d], b = (T)h_var_cost[h_coff[v] + best];
-                    const int rd = rk ? rk[d] : d, rb = rk ? rk[best] : best;
-                    if (g.is_max ? (a > b || (a == b && rd > rb)) : (a < b || (a == b && rd < rb))) best = d;
-                }
+                const int best = hg.optimal_cost_value<T>(v, g.is_max, h_vrank);
                 c0[qv] = best;
-                k0[qv] = (T)h_var_cost[h_coff[v] + best];
+                k0[qv] = (T)hg.var_cost[hg.coff[v] + best];
                 h0[qv] = 1;
             } else {  // the initial value, else the first of the domain (random.choice fixed)
-                c0[qv] = h_init[v] >= 0 ? h_init[v] : 0;
+                c0[qv] = hg.init[v] >= 0 ? hg.init[v] : 0;
             }
-            v0[qv] = (T)h_var_cost[h_coff[v] + c0[qv]];
+            v0[qv] = (T)hg.var_cost[hg.coff[v] + c0[qv]];
             gr[qv] = GainRec<T>{(T)0, c0[qv], h_rank[v]};
         }
         which = 0;
         if (nV) {
             for (int b = 0; b < 2; ++b) {  // both buffers: the packed launches write only the variables with neighbours
-                MGM_TRY(hipMemcpyAsync(cur[b].p, c0.data(), 4 * nV, hipMemcpyHostToDevice, stream));
-                MGM_TRY(hipMemcpyAsync(cost[b].p, k0.data(), sizeof(T) * nV, hipMemcpyHostToDevice, stream));
-                MGM_TRY(hipMemcpyAsync(vcc[b].p, v0.data(), sizeof(T) * nV, hipMemcpyHostToDevice, stream));
+                MXS_TRY(hipMemcpyAsync(cur[b].p, c0.data(), 4 * nV, hipMemcpyHostToDevice, stream));
+                MXS_TRY(hipMemcpyAsync(cost[b].p, k0.data(), sizeof(T) * nV, hipMemcpyHostToDevice, stream));
+                MXS_TRY(hipMemcpyAsync(vcc[b].p, v0.data(), sizeof(T) * nV, hipMemcpyHostToDevice, stream));
             }
-            MGM_TRY(hipMemcpyAsync(has_cost.p, h0.data(), nV, hipMemcpyHostToDevice, stream));
-            MGM_TRY(hipMemcpyAsync(grec.p, gr.data(), sizeof(GainRec<T>) * nV, hipMemcpyHostToDevice, stream));
-            MGM_TRY(hipStreamSynchronize(stream));
+            MXS_TRY(hipMemcpyAsync(has_cost.p, h0.data(), nV, hipMemcpyHostToDevice, stream));
+            MXS_TRY(hipMemcpyAsync(grec.p, gr.data(), sizeof(GainRec<T>) * nV, hipMemcpyHostToDevice, stream));
+            MXS_TRY(hipStreamSynchronize(stream));
         }
         rounds = 0;
         return MXS_OK;
     }
 
     int run(int32_t n) override {
-        MGM_TRY(hipSetDevice(device));
+        MXS_TRY(hipSetDevice(device));
         const int nV = g.n_vars;
         if (nV == 0) {
             rounds += n > 0 ? n : 0;
@@ -739,13 +594,13 @@ struct Engine : Base {
             g.vcc = vcc[which].p;
             g.vcc_out = vcc[which ^ 1].p;
             T* const cw = cost[which].p;
-            g.var_list = packed ? pk_rest.p : nullptr;
-            g.n_list = packed ? n_rest : nV;
+            g.var_list = packed ? pk.rest.p : nullptr;
+            g.n_list = packed ? pk.n_rest : nV;
             const dim3 grid((unsigned)((g.n_list + TPB - 1) / TPB)), block(TPB);
             if (packed) {
-                if (pack_int8) hipLaunchKernelGGL((k_mgm_gain_pack<T, int8_t>), pgrid, pblock, 0, stream, g, cw);
+                if (pk.int8) hipLaunchKernelGGL((k_mgm_gain_pack<T, int8_t>), pgrid, pblock, 0, stream, g, cw);
                 else hipLaunchKernelGGL((k_mgm_gain_pack<T, T>), pgrid, pblock, 0, stream, g, cw);
-                MGM_TRY(hipGetLastError());
+                MXS_TRY(hipGetLastError());
             }
             if (g.n_list > 0) {
                 if (generic || max_dom > 32) hipLaunchKernelGGL((k_mgm_gain<T>), grid, block, 0, stream, g, cw);
@@ -753,37 +608,37 @@ struct Engine : Base {
                 else if (max_dom <= 8) hipLaunchKernelGGL((k_mgm_gain_slots<T, 8>), grid, block, 0, stream, g, cw);
                 else if (max_dom <= 16) hipLaunchKernelGGL((k_mgm_gain_slots<T, 16>), grid, block, 0, stream, g, cw);
                 else hipLaunchKernelGGL((k_mgm_gain_slots<T, 32>), grid, block, 0, stream, g, cw);
-                MGM_TRY(hipGetLastError());
+                MXS_TRY(hipGetLastError());
             }
             if (packed) {
                 hipLaunchKernelGGL((k_mgm_move_pack<T>), pgrid, pblock, 0, stream, g);
-                MGM_TRY(hipGetLastError());
+                MXS_TRY(hipGetLastError());
             }
             if (g.n_list > 0) {
                 if (generic) hipLaunchKernelGGL((k_mgm_move<T>), grid, block, 0, stream, g);
                 else hipLaunchKernelGGL((k_mgm_move_listed<T>), grid, block, 0, stream, g);
-                MGM_TRY(hipGetLastError());
+                MXS_TRY(hipGetLastError());
             }
             which ^= 1;
             rounds += 1;
         }
-        MGM_TRY(hipStreamSynchronize(stream));
+        MXS_TRY(hipStreamSynchronize(stream));
         return MXS_OK;
     }
 
     int get_state(int32_t* idx, double* cst, uint8_t* has, double* gn, int32_t* nv) override {
-        MGM_TRY(hipSetDevice(device));
+        MXS_TRY(hipSetDevice(device));
         const int nV = g.n_vars;
         if (!nV) return MXS_OK;
         std::vector<T> hc(nV);
         std::vector<GainRec<T>> hg(nV);
         std::vector<int32_t> hi(nV);
         std::vector<uint8_t> hh(nV);
-        MGM_TRY(hipMemcpyAsync(hi.data(), cur[which].p, 4 * nV, hipMemcpyDeviceToHost, stream));
-        MGM_TRY(hipMemcpyAsync(hh.data(), has_cost.p, nV, hipMemcpyDeviceToHost, stream));
-        MGM_TRY(hipMemcpyAsync(hc.data(), cost[which].p, sizeof(T) * nV, hipMemcpyDeviceToHost, stream));
-        MGM_TRY(hipMemcpyAsync(hg.data(), grec.p, sizeof(GainRec<T>) * nV, hipMemcpyDeviceToHost, stream));
-        MGM_TRY(hipStreamSynchronize(stream));
+        MXS_TRY(hipMemcpyAsync(hi.data(), cur[which].p, 4 * nV, hipMemcpyDeviceToHost, stream));
+        MXS_TRY(hipMemcpyAsync(hh.data(), has_cost.p, nV, hipMemcpyDeviceToHost, stream));
+        MXS_TRY(hipMemcpyAsync(hc.data(), cost[which].p, sizeof(T) * nV, hipMemcpyDeviceToHost, stream));
+        MXS_TRY(hipMemcpyAsync(hg.data(), grec.p, sizeof(GainRec<T>) * nV, hipMemcpyDeviceToHost, stream));
+        MXS_TRY(hipStreamSynchronize(stream));
         for (int v = 0; v < nV; ++v) {  // the state lives in packed order (Dev::q)
             const int qv = h_q[v];
             if (idx) idx[v] = hi[qv];
@@ -803,26 +658,7 @@ struct Engine : Base {
             if (rc) return rc;
             idx = c.data();
         }
-        double soft = 0;
-        int64_t hard = 0;
-        const int nF = (int)h_frow.size() - 1;
-        for (int f = 0; f < nF; ++f) {
-            int64_t lin = 0;
-            for (int e = h_frow[f]; e < h_frow[f + 1]; ++e) {
-                const int v = h_evar[e];
-                if (idx[v] < 0 || idx[v] >= h_dom[v]) return fail(MXS_E_INVALID, "assignment index out of the domain");
-                lin = lin * h_dom[v] + idx[v];
-            }
-            const double r = h_tables[h_toff[f] + lin];
-            if (r != infinity) soft += r; else hard += 1;
-        }
-        for (int v = 0; v < g.n_vars; ++v) {
-            const double x = h_eval_cost[h_coff[v] + idx[v]];
-            if (x != infinity) soft += x; else hard += 1;
-        }
-        if (cst) *cst = soft;
-        if (viol) *viol = hard;
-        return MXS_OK;
+        return hg.eval_cost(idx, infinity, cst, viol);
     }
 };
 
@@ -835,40 +671,27 @@ struct mxs_mgm {
 extern "C" {
 
 int mxs_mgm_create(const mxs_graph* g, const mxs_params* p, const int32_t* name_rank, int32_t device, mxs_mgm** out) {
-    if (!g || !p || !out) return mgm::fail(MXS_E_INVALID, "null argument");
-    *out = nullptr;
-    try {
-        mgm::Base* impl = p->dtype == MXS_DTYPE_F32 ? (mgm::Base*)new mgm::Engine<float>() : (mgm::Base*)new mgm::Engine<double>();
-        int rc = impl->init(*g, *p, name_rank, device);
-        if (rc) {
-            delete impl;
-            return rc;
-        }
-        *out = new mxs_mgm{impl};
-        return MXS_OK;
-    } catch (const std::exception& ex) {
-        return mgm::fail(MXS_E_NOMEM, ex.what());
-    }
+    return mxs_host::create<mxs_mgm, mgm::Engine>(g, p, out, name_rank, device);
 }
-int mxs_mgm_reset(mxs_mgm* e) { return e ? e->impl->reset() : mgm::fail(MXS_E_INVALID, "null handle"); }
+int mxs_mgm_reset(mxs_mgm* e) { return e ? e->impl->reset() : mxs_host::fail(MXS_E_INVALID, "null handle"); }
 int mxs_mgm_set_value_rank(mxs_mgm* e, const int32_t* value_rank) {
-    return e ? e->impl->set_value_rank(value_rank) : mgm::fail(MXS_E_INVALID, "null handle");
+    return e ? e->impl->set_value_rank(value_rank) : mxs_host::fail(MXS_E_INVALID, "null handle");
 }
 int mxs_mgm_run(mxs_mgm* e, int32_t n_rounds) {
-    if (!e) return mgm::fail(MXS_E_INVALID, "null handle");
-    if (n_rounds < 0) return mgm::fail(MXS_E_INVALID, "negative round count");
+    if (!e) return mxs_host::fail(MXS_E_INVALID, "null handle");
+    if (n_rounds < 0) return mxs_host::fail(MXS_E_INVALID, "negative round count");
     return e->impl->run(n_rounds);
 }
 int mxs_mgm_rounds(const mxs_mgm* e, int64_t* rounds) {
-    if (!e) return mgm::fail(MXS_E_INVALID, "null handle");
+    if (!e) return mxs_host::fail(MXS_E_INVALID, "null handle");
     if (rounds) *rounds = e->impl->rounds;
     return MXS_OK;
 }
 int mxs_mgm_get_state(mxs_mgm* e, int32_t* idx, double* cost, uint8_t* has_cost, double* gain, int32_t* new_value) {
-    return e ? e->impl->get_state(idx, cost, has_cost, gain, new_value) : mgm::fail(MXS_E_INVALID, "null handle");
+    return e ? e->impl->get_state(idx, cost, has_cost, gain, new_value) : mxs_host::fail(MXS_E_INVALID, "null handle");
 }
 int mxs_mgm_eval_cost(mxs_mgm* e, const int32_t* idx, double infinity, double* cost, int64_t* violations) {
-    return e ? e->impl->eval_cost(idx, infinity, cost, violations) : mgm::fail(MXS_E_INVALID, "null handle");
+    return e ? e->impl->eval_cost(idx, infinity, cost, violations) : mxs_host::fail(MXS_E_INVALID, "null handle");
 }
 int mxs_mgm_destroy(mxs_mgm* e) {
     if (e) {

@@ -15,7 +15,7 @@
 //   k_mgm2_resolve  an offerer whose partner accepted takes the accepted value and gain (answer, :858-890)
 //   k_mgm2_decide   gain comparison over the neighbourhood (name ranks for ties) and, for a committed pair,
 //                   both go decisions computed on the fly                  (gain :892-972, go :974-1001)
-// Every draw of the reference's unseeded `random` comes from the counter-based generator of dsa.hip keyed on
+// Every draw of the reference's unseeded `random` comes from the counter-based generator of engine_common.h keyed on
 // (seed, variable, round, draw); the sequences a draw picks from are in canonical order (tests/mgm2_oracle.py).
 // All cost sums run over the variable's constraints in the reference's order, starting from 0
 // (assignment_cost, relations.py:1513-1531), through the slot view of local_search.h.
@@ -23,24 +23,13 @@
 
 namespace mgm2 {
 
-using mgm::Buf;
-using mgm::fail;
+using mxs_host::Buf;
+using mxs_host::fail;
+using mxs_host::uniform;
 
 constexpr int TPB = 64;    // thread-per-variable launches: one wave per block (latency-bound gathers)
 constexpr int OTPB = 256;  // the offer-entry launch
 
-// splitmix64 over (seed, variable, cycle, draw): the generator of dsa.hip / oracle/dsa_oracle.c, bit for bit
-__host__ __device__ inline uint64_t mix64(uint64_t z) {
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    return z ^ (z >> 31);
-}
-__host__ __device__ inline double uniform(uint64_t seed, int32_t variable, int64_t cycle, int32_t draw) {
-    uint64_t z = seed + 0x9E3779B97F4A7C15ull * ((uint64_t)(uint32_t)variable + 1);
-    z = mix64(z) + 0x9E3779B97F4A7C15ull * ((uint64_t)cycle + 1);
-    z = mix64(z) + (uint64_t)(uint32_t)draw;
-    return (double)(mix64(z) >> 11) * (1.0 / 9007199254740992.0);
-}
 // the draw ids (tests/mgm2_oracle.py): 0 start, 1 offerer test, 2 partner, 3 best unilateral value,
 // 4 the `favor: no` coin, 5 the accepted offer among the tied best ones
 enum { D_START = 0, D_OFFERER = 1, D_PARTNER = 2, D_BEST = 3, D_COIN = 4, D_OFFER = 5 };
@@ -330,13 +319,12 @@ struct Engine : Base {
     int device = 0;
     hipStream_t stream = nullptr;
     Dev<T> g{};
-    std::vector<int32_t> h_dom, h_frow, h_evar, h_init, h_nb, h_vrow;
-    std::vector<int64_t> h_toff, h_coff;
-    std::vector<double> h_tables, h_eval_cost;
+    mxs_host::HostGraph hg;
+    std::vector<int32_t> h_nb;
     lsearch::HostSlots hs;
     Buf<int32_t> dom, var_rowptr, has_nb, rank, off_w, ent_var, cur;
-    Buf<int64_t> off_off, sl_base;
-    Buf<int32_t> sl_stride_v, sl_nb_rowptr, sl_nb_var, sl_nb_stride, sl_conc_rowptr, sl_conc_var;
+    Buf<int64_t> off_off;
+    mxs_host::DevSlots sl;
     Buf<T> tables, cost, offer;
     Buf<uint8_t> has_cost, offer_ok;
     Buf<Rec<T>> uni, recv;
@@ -348,46 +336,16 @@ struct Engine : Base {
     int init(const mxs_graph& G, const mxs_params& p, const int32_t* rk, double threshold, int32_t favor, uint64_t seed,
              int dev) override {
         device = dev;
-        int count = 0;
-        if (hipGetDeviceCount(&count) != hipSuccess || count <= 0)
-            return fail(MXS_E_NODEVICE, "no HIP device visible: the engine has no CPU fallback");
-        if (dev < 0 || dev >= count) return fail(MXS_E_INVALID, "device index out of range");
+        if (int rc = mxs_host::open_device(dev, &stream)) return rc;
         if (!(threshold >= 0.0 && threshold <= 1.0)) return fail(MXS_E_INVALID, "threshold must be in [0, 1]");
         if (favor < 0 || favor > 2) return fail(MXS_E_INVALID, "favor must be 0 (unilateral), 1 (no) or 2 (coordinated)");
-        MGM_TRY(hipSetDevice(dev));
-        MGM_TRY(hipStreamCreateWithFlags(&stream, 0));
-        const int nV = G.n_vars, nF = G.n_factors, nE = G.n_edges;
-        if (nV < 0 || nF < 0 || nE < 0) return fail(MXS_E_INVALID, "negative size");
-        if (p.mode != MXS_MODE_MIN && p.mode != MXS_MODE_MAX) return fail(MXS_E_INVALID, "invalid mode");
-        h_dom.assign(G.dom_size, G.dom_size + nV);
-        h_frow.assign(G.factor_rowptr, G.factor_rowptr + nF + 1);
-        h_evar.assign(G.edge_var, G.edge_var + nE);
-        h_toff.assign(G.table_off, G.table_off + nF + 1);
-        h_coff.assign(nV + 1, 0);
-        for (int v = 0; v < nV; ++v) {
-            if (h_dom[v] < 1) return fail(MXS_E_INVALID, "empty domain");
-            h_coff[v + 1] = h_coff[v] + h_dom[v];
-        }
-        for (int f = 0; f < nF; ++f) {
-            if (h_frow[f + 1] <= h_frow[f]) return fail(MXS_E_INVALID, "factor without variable");
-            for (int e = h_frow[f]; e < h_frow[f + 1]; ++e)
-                if (h_evar[e] < 0 || h_evar[e] >= nV) return fail(MXS_E_INVALID, "edge_var out of range");
-        }
-        h_vrow.assign(G.var_rowptr, G.var_rowptr + nV + 1);
-        std::vector<int32_t> vedges(G.var_edges, G.var_edges + nE);
-        h_tables.assign(G.tables, G.tables + h_toff[nF]);
+        if (int rc = hg.load(G, p)) return rc;
+        const int nV = hg.nV, nF = hg.nF;
         // max() over NaN gains depends on message arrival in the reference: no defined result
-        for (double t : h_tables)
+        for (double t : hg.tables)
             if (!std::isfinite(t)) return fail(MXS_E_INVALID, "mgm2: constraint tables must be finite (no inf / NaN entries)");
-        const double* ev = G.eval_var_cost ? G.eval_var_cost : G.var_cost;
-        h_eval_cost.assign(ev, ev + h_coff[nV]);
-        h_init.assign(nV, -1);
-        if (G.init_idx)
-            for (int v = 0; v < nV; ++v) {
-                if (G.init_idx[v] >= h_dom[v]) return fail(MXS_E_INVALID, "init_idx out of the domain");
-                h_init[v] = G.init_idx[v];
-            }
-        const std::string bad = hs.build(nV, nF, h_dom, h_frow, h_evar, h_toff, h_vrow, vedges);
+        if (int rc = hg.load_init(G)) return rc;
+        const std::string bad = hs.build(nV, nF, hg.dom, hg.frow, hg.evar, hg.toff, hg.vrow, hg.vedges);
         if (!bad.empty()) return fail(MXS_E_INVALID, bad);
         // neighbours: the other variables of v's constraints (the concerned list holds v itself once)
         h_nb.assign(nV, 0);
@@ -396,10 +354,10 @@ struct Engine : Base {
         for (int v = 0; v < nV; ++v) {
             int P = 0;
             for (int k = hs.conc_rowptr[v]; k < hs.conc_rowptr[v + 1]; ++k)
-                if (hs.conc_var[k] != v) P = std::max(P, h_dom[hs.conc_var[k]]);
+                if (hs.conc_var[k] != v) P = std::max(P, hg.dom[hs.conc_var[k]]);
             h_nb[v] = P > 0;
             h_w[v] = P;
-            h_off[v + 1] = h_off[v] + (int64_t)h_dom[v] * P;
+            h_off[v + 1] = h_off[v] + (int64_t)hg.dom[v] * P;
         }
         if (h_off[nV] > INT32_MAX) return fail(MXS_E_INVALID, "mgm2: offer tables larger than 2^31 entries");
         h_ent.resize((size_t)h_off[nV]);
@@ -407,32 +365,23 @@ struct Engine : Base {
             for (int64_t i = h_off[v]; i < h_off[v + 1]; ++i) h_ent[(size_t)i] = v;
         std::vector<int32_t> h_rank(nV);
         for (int v = 0; v < nV; ++v) h_rank[v] = rk ? rk[v] : v;
-        std::vector<T> tt(h_tables.size());
-        for (size_t i = 0; i < tt.size(); ++i) tt[i] = (T)h_tables[i];
-        MGM_TRY(sl_base.upload(hs.base, stream));
-        MGM_TRY(sl_stride_v.upload(hs.stride_v, stream));
-        MGM_TRY(sl_nb_rowptr.upload(hs.nb_rowptr, stream));
-        MGM_TRY(sl_nb_var.upload(hs.nb_var, stream));
-        MGM_TRY(sl_nb_stride.upload(hs.nb_stride, stream));
-        MGM_TRY(sl_conc_rowptr.upload(hs.conc_rowptr, stream));
-        MGM_TRY(sl_conc_var.upload(hs.conc_var, stream));
-        MGM_TRY(dom.upload(h_dom, stream));
-        MGM_TRY(var_rowptr.upload(h_vrow, stream));
-        MGM_TRY(has_nb.upload(h_nb, stream));
-        MGM_TRY(rank.upload(h_rank, stream));
-        MGM_TRY(off_w.upload(h_w, stream));
-        MGM_TRY(off_off.upload(h_off, stream));
-        MGM_TRY(ent_var.upload(h_ent, stream));
-        MGM_TRY(tables.upload(tt, stream));
-        MGM_TRY(cur.alloc(nV));
-        MGM_TRY(cost.alloc(nV));
-        MGM_TRY(has_cost.alloc(nV));
-        MGM_TRY(uni.alloc(nV));
-        MGM_TRY(recv.alloc(nV));
-        MGM_TRY(offer.alloc((size_t)h_off[nV]));
-        MGM_TRY(offer_ok.alloc((size_t)h_off[nV]));
-        g.slots = lsearch::Slots{sl_base.p, sl_stride_v.p, sl_nb_rowptr.p, sl_nb_var.p, sl_nb_stride.p, nullptr, nullptr,
-                                 sl_conc_rowptr.p, sl_conc_var.p, nullptr, nullptr, nullptr, nullptr, 0};
+        if (int rc = sl.upload(hs, stream, nullptr, false)) return rc;  // no first-neighbour arrays, no rows
+        MXS_TRY(dom.upload(hg.dom, stream));
+        MXS_TRY(var_rowptr.upload(hg.vrow, stream));
+        MXS_TRY(has_nb.upload(h_nb, stream));
+        MXS_TRY(rank.upload(h_rank, stream));
+        MXS_TRY(off_w.upload(h_w, stream));
+        MXS_TRY(off_off.upload(h_off, stream));
+        MXS_TRY(ent_var.upload(h_ent, stream));
+        MXS_TRY(tables.upload(mxs_host::narrowed<T>(hg.tables), stream));
+        MXS_TRY(cur.alloc(nV));
+        MXS_TRY(cost.alloc(nV));
+        MXS_TRY(has_cost.alloc(nV));
+        MXS_TRY(uni.alloc(nV));
+        MXS_TRY(recv.alloc(nV));
+        MXS_TRY(offer.alloc((size_t)h_off[nV]));
+        MXS_TRY(offer_ok.alloc((size_t)h_off[nV]));
+        g.slots = sl.view();
         g.n_vars = nV;
         g.is_max = p.mode == MXS_MODE_MAX;
         g.favor = favor;
@@ -460,7 +409,7 @@ struct Engine : Base {
     // on_start (:460-495): a variable with neighbours takes its initial value or a random one (held cost None);
     // one without neighbours takes a random best value of its own constraints and is finished
     int reset() override {
-        MGM_TRY(hipSetDevice(device));
+        MXS_TRY(hipSetDevice(device));
         const int nV = g.n_vars;
         std::vector<int32_t> c0(nV);
         std::vector<T> k0(nV, (T)0);
@@ -468,15 +417,15 @@ struct Engine : Base {
         for (int v = 0; v < nV; ++v) {
             const double u = uniform(g.seed, v, 0, D_START);
             if (h_nb[v]) {
-                c0[v] = h_init[v] >= 0 ? h_init[v] : (int)(u * h_dom[v]);
+                c0[v] = hg.init[v] >= 0 ? hg.init[v] : (int)(u * hg.dom[v]);
                 continue;
             }
-            std::vector<T> c(h_dom[v]);
+            std::vector<T> c(hg.dom[v]);
             T best = (T)0;
             int n_best = 0;
-            for (int x = 0; x < h_dom[v]; ++x) {
+            for (int x = 0; x < hg.dom[v]; ++x) {
                 T acc = (T)0;
-                for (int s = h_vrow[v]; s < h_vrow[v + 1]; ++s) acc += (T)h_tables[hs.base[s] + (int64_t)x * hs.stride_v[s]];
+                for (int s = hg.vrow[v]; s < hg.vrow[v + 1]; ++s) acc += (T)hg.tables[hs.base[s] + (int64_t)x * hs.stride_v[s]];
                 c[x] = acc;
                 if (n_best == 0 || (g.is_max ? best < acc : best > acc)) {
                     best = acc;
@@ -486,7 +435,7 @@ struct Engine : Base {
                 }
             }
             int k = (int)(u * n_best);
-            for (int x = 0; x < h_dom[v]; ++x)
+            for (int x = 0; x < hg.dom[v]; ++x)
                 if (c[x] == best && k-- == 0) {
                     c0[v] = x;
                     break;
@@ -495,17 +444,17 @@ struct Engine : Base {
             h0[v] = 1;
         }
         if (nV) {
-            MGM_TRY(hipMemcpyAsync(cur.p, c0.data(), 4 * (size_t)nV, hipMemcpyHostToDevice, stream));
-            MGM_TRY(hipMemcpyAsync(cost.p, k0.data(), sizeof(T) * nV, hipMemcpyHostToDevice, stream));
-            MGM_TRY(hipMemcpyAsync(has_cost.p, h0.data(), nV, hipMemcpyHostToDevice, stream));
-            MGM_TRY(hipStreamSynchronize(stream));
+            MXS_TRY(hipMemcpyAsync(cur.p, c0.data(), 4 * (size_t)nV, hipMemcpyHostToDevice, stream));
+            MXS_TRY(hipMemcpyAsync(cost.p, k0.data(), sizeof(T) * nV, hipMemcpyHostToDevice, stream));
+            MXS_TRY(hipMemcpyAsync(has_cost.p, h0.data(), nV, hipMemcpyHostToDevice, stream));
+            MXS_TRY(hipStreamSynchronize(stream));
         }
         rounds = 0;
         return MXS_OK;
     }
 
     int run(int32_t n) override {
-        MGM_TRY(hipSetDevice(device));
+        MXS_TRY(hipSetDevice(device));
         const int nV = g.n_vars;
         if (nV == 0) {
             rounds += n > 0 ? n : 0;
@@ -516,34 +465,34 @@ struct Engine : Base {
         for (int32_t r = 0; r < n; ++r) {
             g.round = rounds + 1;
             hipLaunchKernelGGL((k_mgm2_value<T>), grid, block, 0, stream, g);
-            MGM_TRY(hipGetLastError());
+            MXS_TRY(hipGetLastError());
             if (g.n_entries > 0) {
                 hipLaunchKernelGGL((k_mgm2_offers<T>), ogrid, oblock, 0, stream, g);
-                MGM_TRY(hipGetLastError());
+                MXS_TRY(hipGetLastError());
             }
             hipLaunchKernelGGL((k_mgm2_receive<T>), grid, block, 0, stream, g);
-            MGM_TRY(hipGetLastError());
+            MXS_TRY(hipGetLastError());
             hipLaunchKernelGGL((k_mgm2_resolve<T>), grid, block, 0, stream, g);
-            MGM_TRY(hipGetLastError());
+            MXS_TRY(hipGetLastError());
             hipLaunchKernelGGL((k_mgm2_decide<T>), grid, block, 0, stream, g);
-            MGM_TRY(hipGetLastError());
+            MXS_TRY(hipGetLastError());
             rounds += 1;
         }
-        MGM_TRY(hipStreamSynchronize(stream));
+        MXS_TRY(hipStreamSynchronize(stream));
         return MXS_OK;
     }
 
     int get_state(int32_t* idx, double* cst, uint8_t* has) override {
-        MGM_TRY(hipSetDevice(device));
+        MXS_TRY(hipSetDevice(device));
         const int nV = g.n_vars;
         if (!nV) return MXS_OK;
         std::vector<T> hc(nV);
         std::vector<int32_t> hi(nV);
         std::vector<uint8_t> hh(nV);
-        MGM_TRY(hipMemcpyAsync(hi.data(), cur.p, 4 * (size_t)nV, hipMemcpyDeviceToHost, stream));
-        MGM_TRY(hipMemcpyAsync(hh.data(), has_cost.p, nV, hipMemcpyDeviceToHost, stream));
-        MGM_TRY(hipMemcpyAsync(hc.data(), cost.p, sizeof(T) * nV, hipMemcpyDeviceToHost, stream));
-        MGM_TRY(hipStreamSynchronize(stream));
+        MXS_TRY(hipMemcpyAsync(hi.data(), cur.p, 4 * (size_t)nV, hipMemcpyDeviceToHost, stream));
+        MXS_TRY(hipMemcpyAsync(hh.data(), has_cost.p, nV, hipMemcpyDeviceToHost, stream));
+        MXS_TRY(hipMemcpyAsync(hc.data(), cost.p, sizeof(T) * nV, hipMemcpyDeviceToHost, stream));
+        MXS_TRY(hipStreamSynchronize(stream));
         for (int v = 0; v < nV; ++v) {
             if (idx) idx[v] = hi[v];
             if (has) has[v] = hh[v];
@@ -561,26 +510,7 @@ struct Engine : Base {
             if (rc) return rc;
             idx = c.data();
         }
-        double soft = 0;
-        int64_t hard = 0;
-        const int nF = (int)h_frow.size() - 1;
-        for (int f = 0; f < nF; ++f) {
-            int64_t lin = 0;
-            for (int e = h_frow[f]; e < h_frow[f + 1]; ++e) {
-                const int v = h_evar[e];
-                if (idx[v] < 0 || idx[v] >= h_dom[v]) return fail(MXS_E_INVALID, "assignment index out of the domain");
-                lin = lin * h_dom[v] + idx[v];
-            }
-            const double r = h_tables[h_toff[f] + lin];
-            if (r != infinity) soft += r; else hard += 1;
-        }
-        for (int v = 0; v < g.n_vars; ++v) {
-            const double x = h_eval_cost[h_coff[v] + idx[v]];
-            if (x != infinity) soft += x; else hard += 1;
-        }
-        if (cst) *cst = soft;
-        if (viol) *viol = hard;
-        return MXS_OK;
+        return hg.eval_cost(idx, infinity, cst, viol);
     }
 };
 
@@ -594,38 +524,24 @@ extern "C" {
 
 int mxs_mgm2_create(const mxs_graph* g, const mxs_params* p, const int32_t* name_rank, double threshold, int32_t favor,
                     uint64_t seed, int32_t device, mxs_mgm2** out) {
-    if (!g || !p || !out) return mgm::fail(MXS_E_INVALID, "null argument");
-    *out = nullptr;
-    try {
-        mgm2::Base* impl = p->dtype == MXS_DTYPE_F32 ? (mgm2::Base*)new mgm2::Engine<float>()
-                                                     : (mgm2::Base*)new mgm2::Engine<double>();
-        int rc = impl->init(*g, *p, name_rank, threshold, favor, seed, device);
-        if (rc) {
-            delete impl;
-            return rc;
-        }
-        *out = new mxs_mgm2{impl};
-        return MXS_OK;
-    } catch (const std::exception& ex) {
-        return mgm::fail(MXS_E_NOMEM, ex.what());
-    }
+    return mxs_host::create<mxs_mgm2, mgm2::Engine>(g, p, out, name_rank, threshold, favor, seed, device);
 }
-int mxs_mgm2_reset(mxs_mgm2* e) { return e ? e->impl->reset() : mgm::fail(MXS_E_INVALID, "null handle"); }
+int mxs_mgm2_reset(mxs_mgm2* e) { return e ? e->impl->reset() : mxs_host::fail(MXS_E_INVALID, "null handle"); }
 int mxs_mgm2_run(mxs_mgm2* e, int32_t n_rounds) {
-    if (!e) return mgm::fail(MXS_E_INVALID, "null handle");
-    if (n_rounds < 0) return mgm::fail(MXS_E_INVALID, "negative round count");
+    if (!e) return mxs_host::fail(MXS_E_INVALID, "null handle");
+    if (n_rounds < 0) return mxs_host::fail(MXS_E_INVALID, "negative round count");
     return e->impl->run(n_rounds);
 }
 int mxs_mgm2_rounds(const mxs_mgm2* e, int64_t* rounds) {
-    if (!e) return mgm::fail(MXS_E_INVALID, "null handle");
+    if (!e) return mxs_host::fail(MXS_E_INVALID, "null handle");
     if (rounds) *rounds = e->impl->rounds;
     return MXS_OK;
 }
 int mxs_mgm2_get_state(mxs_mgm2* e, int32_t* idx, double* cost, uint8_t* has_cost) {
-    return e ? e->impl->get_state(idx, cost, has_cost) : mgm::fail(MXS_E_INVALID, "null handle");
+    return e ? e->impl->get_state(idx, cost, has_cost) : mxs_host::fail(MXS_E_INVALID, "null handle");
 }
 int mxs_mgm2_eval_cost(mxs_mgm2* e, const int32_t* idx, double infinity, double* cost, int64_t* violations) {
-    return e ? e->impl->eval_cost(idx, infinity, cost, violations) : mgm::fail(MXS_E_INVALID, "null handle");
+    return e ? e->impl->eval_cost(idx, infinity, cost, violations) : mxs_host::fail(MXS_E_INVALID, "null handle");
 }
 int mxs_mgm2_destroy(mxs_mgm2* e) {
     if (e) {

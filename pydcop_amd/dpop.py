@@ -7,7 +7,8 @@ from typing import List, Optional, Tuple
 
 import numpy as np
 
-from .engine import MaxSumGpuError, load_library
+from ._binding import EngineBinding
+from .engine import load_library
 from .graph import FlatGraph, Params
 
 STATS = ("components", "depth", "widest_separator", "widest_util_entries", "total_entries", "bytes",
@@ -105,15 +106,15 @@ def pack_tree(parent, children):
     return np.array(parent, dtype=np.int32), rowptr, idx
 
 
-class DpopEngine:
+class DpopEngine(EngineBinding):
     """>>> with DpopEngine(graph, Params(mode="min")) as eng:
     ...     eng.solve()
     ...     idx, cost = eng.assignment()      # cost[root]: the optimum of the root's component
     """
+    PREFIX = "mxs_dpop"
 
     def __init__(self, graph: FlatGraph, params: Optional[Params] = None, tree=None, max_bytes: int = 0,
                  fuse_entries: int = -1, device: int = 0, lib_path: Optional[str] = None):
-        self._h = None
         self._lib = load_library(lib_path)
         self.graph = graph
         self.params = params or Params()
@@ -131,20 +132,16 @@ class DpopEngine:
                                               int(max_bytes), int(fuse_entries), int(device), C.byref(h)))
         self._h = h
 
-    def _check(self, rc: int):
-        if rc != 0:
-            raise MaxSumGpuError(f"maxsum_gpu error {rc}: {self._lib.mxs_last_error().decode()}")
-
     def solve(self):
         """UTIL bottom-up, then VALUE top-down."""
-        self._check(self._lib.mxs_dpop_solve(self._h))
+        self._call("solve")
 
     cycle_count = 0      # DPOP has no cycles
 
     def state(self) -> dict:
         n = self.graph.n_vars
         out = {"idx": np.empty(n, dtype=np.int32), "cost": np.empty(n)}
-        self._check(self._lib.mxs_dpop_get_state(self._h, out["idx"].ctypes.data, out["cost"].ctypes.data))
+        self._call("get_state", out["idx"].ctypes.data, out["cost"].ctypes.data)
         return out
 
     def assignment(self) -> Tuple[np.ndarray, np.ndarray]:
@@ -153,14 +150,14 @@ class DpopEngine:
 
     def stats(self) -> dict:
         out = np.zeros(len(STATS), dtype=np.int64)
-        self._check(self._lib.mxs_dpop_stats(self._h, out.ctypes.data, len(STATS)))
+        self._call("stats", out.ctypes.data, len(STATS))
         return dict(zip(STATS, (int(x) for x in out)))
 
     def util_dims(self, var: int) -> np.ndarray:
         n = C.c_int32(0)
-        self._check(self._lib.mxs_dpop_util_dims(self._h, int(var), None, C.byref(n)))
+        self._call("util_dims", int(var), None, C.byref(n))
         dims = np.empty(n.value, dtype=np.int32)
-        self._check(self._lib.mxs_dpop_util_dims(self._h, int(var), dims.ctypes.data, C.byref(n)))
+        self._call("util_dims", int(var), dims.ctypes.data, C.byref(n))
         return dims
 
     def util(self, var: int) -> Tuple[np.ndarray, np.ndarray]:
@@ -168,31 +165,5 @@ class DpopEngine:
         dims = self.util_dims(var)
         shape = tuple(int(self.graph.dom_size[u]) for u in dims)
         table = np.empty(shape, dtype=np.float64)
-        self._check(self._lib.mxs_dpop_get_util(self._h, int(var), table.ctypes.data, int(table.size)))
+        self._call("get_util", int(var), table.ctypes.data, int(table.size))
         return dims, table
-
-    def eval_cost(self, idx=None, infinity: float = float("inf")) -> Tuple[float, int]:
-        cost, viol = C.c_double(0), C.c_int64(0)
-        p = None
-        if idx is not None:
-            idx = np.ascontiguousarray(idx, dtype=np.int32)
-            p = idx.ctypes.data
-        self._check(self._lib.mxs_dpop_eval_cost(self._h, p, float(infinity), C.byref(cost), C.byref(viol)))
-        return float(cost.value), int(viol.value)
-
-    def close(self):
-        if getattr(self, "_h", None):
-            self._lib.mxs_dpop_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()

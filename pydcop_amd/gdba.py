@@ -6,7 +6,8 @@ from typing import Optional, Tuple
 
 import numpy as np
 
-from .engine import MaxSumGpuError, load_library
+from ._binding import EngineBinding
+from .engine import load_library
 from .graph import FlatGraph, Params
 from .mgm import name_ranks
 
@@ -25,18 +26,19 @@ def check_params(modifier, violation, increase_mode):
     return MODIFIERS.index(modifier), VIOLATIONS.index(violation), INCREASE_MODES.index(increase_mode)
 
 
-class GdbaEngine:
+class GdbaEngine(EngineBinding):
     """>>> eng = GdbaEngine(graph, Params(mode="min"), modifier="A", violation="NZ", increase_mode="E", seed=0)
     >>> eng.run(30)                                    # 30 rounds of (ok, improve)
     >>> idx, cost = eng.assignment()
 
     `pool_budget`: the most bytes the modifier tables may take on the device (0: the library's default);
     an instance past it is refused before anything is allocated."""
+    PREFIX = "mxs_gdba"
+    COUNTER = "rounds"
 
     def __init__(self, graph: FlatGraph, params: Optional[Params] = None, modifier: str = "A", violation: str = "NZ",
                  increase_mode: str = "E", seed: int = 0, pool_budget: int = 0, device: int = 0,
                  lib_path: Optional[str] = None):
-        self._h = None
         codes = check_params(modifier, violation, increase_mode)
         self.modifier, self.violation, self.increase_mode, self.seed = modifier, violation, increase_mode, int(seed)
         self._lib = load_library(lib_path)
@@ -54,28 +56,17 @@ class GdbaEngine:
                                               int(pool_budget), int(device), C.byref(h)))
         self._h = h
 
-    def _check(self, rc: int):
-        if rc != 0:
-            raise MaxSumGpuError(f"maxsum_gpu error {rc}: {self._lib.mxs_last_error().decode()}")
-
     def reset(self):
-        self._check(self._lib.mxs_gdba_reset(self._h))
+        self._call("reset")
 
     def run(self, n_rounds: int):
-        self._check(self._lib.mxs_gdba_run(self._h, int(n_rounds)))
-
-    @property
-    def cycle_count(self) -> int:
-        n = C.c_int64(0)
-        self._check(self._lib.mxs_gdba_rounds(self._h, C.byref(n)))
-        return int(n.value)
+        self._call("run", int(n_rounds))
 
     def state(self) -> dict:
         n = self.graph.n_vars
         out = {"idx": np.empty(n, dtype=np.int32), "cost": np.empty(n), "has_cost": np.empty(n, dtype=np.uint8),
                "improve": np.empty(n), "new": np.empty(n, dtype=np.int32)}
-        self._check(self._lib.mxs_gdba_get_state(self._h, *[out[k].ctypes.data for k in
-                                                            ("idx", "cost", "has_cost", "improve", "new")]))
+        self._call("get_state", *[out[k].ctypes.data for k in ("idx", "cost", "has_cost", "improve", "new")])
         return out
 
     def assignment(self) -> Tuple[np.ndarray, np.ndarray]:
@@ -86,40 +77,14 @@ class GdbaEngine:
         """The modifier table of slot = var_rowptr[v] + k (variable v, its k-th constraint), in the layout of the
         constraint's table; one entry in mode T; empty where the engine stores none (no look-up can reach it)."""
         n = C.c_int64(0)
-        self._check(self._lib.mxs_gdba_get_modifiers(self._h, int(slot), None, 0, C.byref(n)))
+        self._call("get_modifiers", int(slot), None, 0, C.byref(n))
         out = np.empty(int(n.value), dtype=np.int32)
         if n.value:
-            self._check(self._lib.mxs_gdba_get_modifiers(self._h, int(slot), out.ctypes.data, int(n.value), C.byref(n)))
+            self._call("get_modifiers", int(slot), out.ctypes.data, int(n.value), C.byref(n))
         return out
 
     @property
     def pool_bytes(self) -> int:
         n = C.c_int64(0)
-        self._check(self._lib.mxs_gdba_get_modifiers(self._h, -1, None, 0, C.byref(n)))
+        self._call("get_modifiers", -1, None, 0, C.byref(n))
         return int(n.value)
-
-    def eval_cost(self, idx=None, infinity: float = float("inf")) -> Tuple[float, int]:
-        cost, viol = C.c_double(0), C.c_int64(0)
-        p = None
-        if idx is not None:
-            idx = np.ascontiguousarray(idx, dtype=np.int32)
-            p = idx.ctypes.data
-        self._check(self._lib.mxs_gdba_eval_cost(self._h, p, float(infinity), C.byref(cost), C.byref(viol)))
-        return float(cost.value), int(viol.value)
-
-    def close(self):
-        if getattr(self, "_h", None):
-            self._lib.mxs_gdba_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()

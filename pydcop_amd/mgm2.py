@@ -6,7 +6,8 @@ from typing import Optional, Tuple
 
 import numpy as np
 
-from .engine import MaxSumGpuError, load_library
+from ._binding import EngineBinding
+from .engine import load_library
 from .graph import FlatGraph, Params
 from .mgm import name_ranks
 
@@ -27,15 +28,16 @@ def check_params(threshold, favor):
     return threshold, FAVORS.index(favor)
 
 
-class Mgm2Engine:
+class Mgm2Engine(EngineBinding):
     """>>> eng = Mgm2Engine(graph, Params(mode="min"), threshold=0.5, favor="unilateral", seed=0)
     >>> eng.run(30)                                    # 30 rounds (= the reference's stop_cycle 31)
     >>> idx, cost = eng.assignment()
     """
+    PREFIX = "mxs_mgm2"
+    COUNTER = "rounds"
 
     def __init__(self, graph: FlatGraph, params: Optional[Params] = None, threshold: float = 0.5,
                  favor: str = "unilateral", seed: int = 0, device: int = 0, lib_path: Optional[str] = None):
-        self._h = None
         self.threshold, favor_code = check_params(threshold, favor)
         self.favor, self.seed = favor, int(seed)
         self._lib = load_library(lib_path)
@@ -50,54 +52,18 @@ class Mgm2Engine:
                                               C.byref(h)))
         self._h = h
 
-    def _check(self, rc: int):
-        if rc != 0:
-            raise MaxSumGpuError(f"maxsum_gpu error {rc}: {self._lib.mxs_last_error().decode()}")
-
     def reset(self):
-        self._check(self._lib.mxs_mgm2_reset(self._h))
+        self._call("reset")
 
     def run(self, n_rounds: int):
-        self._check(self._lib.mxs_mgm2_run(self._h, int(n_rounds)))
-
-    @property
-    def cycle_count(self) -> int:
-        n = C.c_int64(0)
-        self._check(self._lib.mxs_mgm2_rounds(self._h, C.byref(n)))
-        return int(n.value)
+        self._call("run", int(n_rounds))
 
     def state(self) -> dict:
         n = self.graph.n_vars
         out = {"idx": np.empty(n, dtype=np.int32), "cost": np.empty(n), "has_cost": np.empty(n, dtype=np.uint8)}
-        self._check(self._lib.mxs_mgm2_get_state(self._h, *[out[k].ctypes.data for k in ("idx", "cost", "has_cost")]))
+        self._call("get_state", *[out[k].ctypes.data for k in ("idx", "cost", "has_cost")])
         return out
 
     def assignment(self) -> Tuple[np.ndarray, np.ndarray]:
         s = self.state()
         return s["idx"], s["cost"]
-
-    def eval_cost(self, idx=None, infinity: float = float("inf")) -> Tuple[float, int]:
-        cost, viol = C.c_double(0), C.c_int64(0)
-        p = None
-        if idx is not None:
-            idx = np.ascontiguousarray(idx, dtype=np.int32)
-            p = idx.ctypes.data
-        self._check(self._lib.mxs_mgm2_eval_cost(self._h, p, float(infinity), C.byref(cost), C.byref(viol)))
-        return float(cost.value), int(viol.value)
-
-    def close(self):
-        if getattr(self, "_h", None):
-            self._lib.mxs_mgm2_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()

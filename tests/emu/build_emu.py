@@ -11,7 +11,8 @@ OUT = os.path.join(HERE, "_build", "libmaxsum_emu.so")
 
 def build(force=False):
     srcs = [os.path.join(CSRC, f) for f in ("engine.hip", "layout.cpp", "amaxsum.hip", "mgm.hip", "dsa.hip", "bin_box.hip", "small_box.hip")]
-    deps = srcs + [os.path.join(CSRC, f) for f in ("kernels.h", "nary_box.h", "bin_box.h", "small_box.h", "layout.h", "local_search.h")] + [
+    deps = srcs + [os.path.join(CSRC, f) for f in ("kernels.h", "nary_box.h", "bin_box.h", "small_box.h", "layout.h", "local_search.h",
+                                                   "engine_common.h", "mgm2.h", "dpop.h", "gdba.h")] + [
         os.path.join(HERE, "hip", "hip_runtime.h"), os.path.join(HERE, "hipcub", "hipcub.hpp"),
         os.path.join(ROOT, "include", "maxsum_gpu.h")]
     if not force and os.path.exists(OUT) and all(
@@ -38,20 +39,6 @@ def build_fake_rccl(force=False):
     return FAKE_RCCL
 
 
-FAKE_RCCL = os.path.join(HERE, "_build", "libfake_rccl.so")
-
-
-def build_fake_rccl(force=False):
-    """tests/emu/fake_rccl: the RCCL entry points the engine binds, over files (TEST ONLY)."""
-    src = os.path.join(HERE, "fake_rccl", "fake_rccl.cpp")
-    if not force and os.path.exists(FAKE_RCCL) and os.path.getmtime(FAKE_RCCL) >= os.path.getmtime(src):
-        return FAKE_RCCL
-    os.makedirs(os.path.dirname(FAKE_RCCL), exist_ok=True)
-    subprocess.check_call(["g++", "-O1", "-g", "-std=c++17", "-fPIC", "-shared", "-pthread", src, "-o", FAKE_RCCL])
-    return FAKE_RCCL
-
-
 if __name__ == "__main__":
-    print(build_fake_rccl(force=True))
     print(build_fake_rccl(force=True))
     print(build(force=True))

@@ -1,7 +1,6 @@
 """DPOP on the emulated engine build (the very same mgm.hip / dpop.h, g++ against the fake HIP runtime)
 against tests/dpop_oracle.py, bit for bit -- the CPU twin of tests/test_gpu_dpop.py."""
 import itertools
-import os
 
 import numpy as np
 import pytest
@@ -10,16 +9,11 @@ from dpop_common import FUSE, check_golden, compare_dpop, dpop_cases, dpop_golde
 from pydcop_amd import generators as G
 from pydcop_amd.graph import Params
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
 
 @pytest.fixture(scope="module")
 def emu_lib():
-    """build_emu's dependency list does not name dpop.h: rebuild when it is newer than the library."""
-    from emu.build_emu import OUT, build
-    header = os.path.join(ROOT, "pydcop_amd", "csrc", "dpop.h")
-    stale = not os.path.exists(OUT) or os.path.getmtime(OUT) < os.path.getmtime(header)
-    return build(force=stale)
+    from emu.build_emu import build
+    return build()
 
 
 @pytest.mark.parametrize("case", dpop_cases(), ids=lambda c: c[0])

@@ -1,24 +1,17 @@
 """GDBA on the emulated engine build (the very same mgm.hip / gdba.h, g++ against the fake HIP runtime)
 against tests/gdba_oracle.py and the reference-recorded fixtures, bit for bit, round by round -- the
 CPU twin of tests/test_gpu_gdba.py."""
-import os
-
 import numpy as np
 import pytest
 
 from gdba_common import compare_gdba, gdba_cases
 from pydcop_amd.graph import Params
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
 
 @pytest.fixture(scope="module")
 def emu_lib():
-    """build_emu's dependency list does not name gdba.h: rebuild when it is newer than the library."""
-    from emu.build_emu import OUT, build
-    header = os.path.join(ROOT, "pydcop_amd", "csrc", "gdba.h")
-    stale = not os.path.exists(OUT) or os.path.getmtime(OUT) < os.path.getmtime(header)
-    return build(force=stale)
+    from emu.build_emu import build
+    return build()
 
 
 @pytest.mark.parametrize("case", gdba_cases(), ids=lambda c: c[0])

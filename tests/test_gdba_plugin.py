@@ -19,9 +19,8 @@ pytestmark = pytest.mark.skipif(not os.path.isdir(os.path.join(REF, "pydcop")),
 @pytest.fixture(scope="module")
 def pydcop_ready():
     import sys
-    from emu.build_emu import OUT, build
-    header = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "pydcop_amd", "csrc", "gdba.h")
-    emu_lib = build(force=not os.path.exists(OUT) or os.path.getmtime(OUT) < os.path.getmtime(header))
+    from emu.build_emu import build
+    emu_lib = build()
     if REF not in sys.path:
         sys.path.insert(0, REF)
     from pydcop_amd import plugin

@@ -1,22 +1,15 @@
 """MGM-2 on the emulated engine build (the very same mgm.hip / mgm2.h, g++ against the fake HIP runtime)
 against tests/mgm2_oracle.py, bit for bit, round by round -- the CPU twin of tests/test_gpu_mgm2.py."""
-import os
-
 import pytest
 
 from mgm2_common import compare_mgm2, mgm2_cases
 from pydcop_amd.graph import Params
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
 
 @pytest.fixture(scope="module")
 def emu_lib():
-    """build_emu's dependency list does not name mgm2.h: rebuild when it is newer than the library."""
-    from emu.build_emu import OUT, build
-    header = os.path.join(ROOT, "pydcop_amd", "csrc", "mgm2.h")
-    stale = not os.path.exists(OUT) or os.path.getmtime(OUT) < os.path.getmtime(header)
-    return build(force=stale)
+    from emu.build_emu import build
+    return build()
 
 
 @pytest.mark.parametrize("case", mgm2_cases(), ids=lambda c: c[0])
