@@ -596,6 +596,44 @@ int mxs_gdba_get_modifiers(mxs_gdba *e, int32_t slot, int32_t *out, int64_t capa
 int mxs_gdba_eval_cost(mxs_gdba *e, const int32_t *idx, double infinity, double *cost, int64_t *violations);
 int mxs_gdba_destroy(mxs_gdba *e);
 
+/* ---- DBA (pydcop/algorithms/dba.py) on the same flat arrays: Distributed Breakout, satisfaction only ----
+ * One round = the two phases of DbaComputation for every variable: ok (:366-445: eval(x) = the sum of
+ * the weights of the constraints whose entry at x is >= `infinity`, the best values from `infinity`
+ * down, the improvement) and improve (:504-562: counter = min over the neighbourhood, the move of the
+ * most improving variable (ties by name), or + 1 on the weights of the violated constraints in a
+ * quasi-local minimum).  A variable whose termination counter reaches `max_distance` (==, as written)
+ * stops: the run ends with that round, every other variable having finished it; _run after that is an
+ * error-free no-op and _rounds stays at the stop round.  Only MXS_MODE_MIN (the reference raises
+ * ValueError for max).  The cost tables do not reach the device: per (variable, constraint) slot one
+ * BIT per entry, `entry >= infinity` compared in double on the host (NaN: no; +inf: yes), in rows of
+ * ceil(D_v / 32) words per combination of the other scope variables.  `mask_budget_bytes`: the most
+ * those rows may take (0: 4 GiB); an instance past it is refused before anything is allocated.
+ * Weights and evals are int32: _run refuses to go past the round at which (largest number of
+ * constraints of a variable) x (1 + rounds) could reach 2^31.  _run fails (the text names `infinity`)
+ * where the reference raises IndexError: a variable improves while every eval of it is above
+ * `infinity`.  Initial values are not looked at (:343); the two draws of the reference's unseeded
+ * `random` come from the keyed generator of DSA (seed, variable, cycle, draw): 8 the start value at
+ * cycle 0, 9 one of the best values at the computation's cycle_count (round - 1).  `name_rank` as
+ * for MGM (may be NULL).  `infinity` must be finite. */
+typedef struct mxs_dba mxs_dba;
+int mxs_dba_create(const mxs_graph *g, const mxs_params *p, const int32_t *name_rank, double infinity,
+                   int32_t max_distance, uint64_t seed, int64_t mask_budget_bytes, int32_t device, mxs_dba **out);
+int mxs_dba_reset(mxs_dba *e);
+int mxs_dba_run(mxs_dba *e, int32_t n_rounds);
+int mxs_dba_rounds(const mxs_dba *e, int64_t *rounds);
+/* *stopped = 1 once a stop condition held, *stop_round = the round it held in (0: none yet) */
+int mxs_dba_finished(const mxs_dba *e, int32_t *stopped, int64_t *stop_round);
+/* per variable: the current value index, the cost the computation holds (has_cost = 0: still None),
+ * the eval at the last ok phase, the improvement, the value it would move to (-1: still None), the
+ * termination counter and the consistent flag after the round.  Any pointer may be NULL. */
+int mxs_dba_get_state(mxs_dba *e, int32_t *idx, int32_t *cost, uint8_t *has_cost, int32_t *eval, int32_t *improve,
+                      int32_t *new_value, int32_t *counter, uint8_t *consistent);
+/* the weight of every slot (variable v, its k-th constraint: slot = var_rowptr[v] + k) */
+int mxs_dba_get_weights(mxs_dba *e, int32_t *out /* [n_slots] */);
+int mxs_dba_mask_bytes(const mxs_dba *e, int64_t *bytes);
+int mxs_dba_eval_cost(mxs_dba *e, const int32_t *idx, double infinity, double *cost, int64_t *violations);
+int mxs_dba_destroy(mxs_dba *e);
+
 /* Library/ABI version (major*100+minor). */
 int32_t mxs_version(void);
 

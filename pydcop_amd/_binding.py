@@ -1,4 +1,4 @@
-"""What the ctypes bindings of the `mxs_dsa_*`, `mxs_mgm_*`, `mxs_mgm2_*`, `mxs_gdba_*` and `mxs_dpop_*` entry points
+"""What the ctypes bindings of the `mxs_dsa_*`, `mxs_mgm_*`, `mxs_mgm2_*`, `mxs_gdba_*`, `mxs_dba_*` and `mxs_dpop_*` entry points
 (include/maxsum_gpu.h) share: the handle, the error check, `eval_cost`, the cycle counter and the life cycle."""
 import ctypes as C
 from typing import Tuple

@@ -1,0 +1,107 @@
+"""dba_gpu -- the reference's DBA (pydcop/algorithms/dba.py, Yokoo & Hirayama's Distributed Breakout) on the
+GPU, behind the algorithm-module contract (same GRAPH_TYPE `constraints_hypergraph`, the reference's
+`infinity` and `max_distance` with their defaults, the same footprint / load formulas), reusing the proxies
+and the session of `maxsum_gpu`.
+
+One round of DBA = two launches over all variables (pydcop_amd/csrc/dba.h).  DBA is a constraint
+SATISFACTION algorithm: a constraint is violated where its cost is >= `infinity`, nothing else of the costs
+is looked at, and only the `min` objective is accepted (the reference raises ValueError for `max`, and so
+does this module).  The run ends FINISHED, as the reference's does, with the first round in which a
+variable's termination counter reaches `max_distance`; `stop_cycle: n` ends it after n - 1 rounds at the
+latest, 0 = keep going, `chunk` rounds per report.  Extra parameter `seed` (default 0): the two stochastic
+choices -- start value, one of the best values -- come from the counter-based generator of dsa_gpu keyed on
+(seed, variable, cycle, draw) over domain order, where the reference draws from Python's unseeded `random`:
+a run is reproducible, and value for value the reference's own DbaComputation under the same generator.
+"""
+from pydcop.algorithms import AlgoParameterDef
+
+from pydcop_amd.algorithms import maxsum_gpu as _base
+from pydcop_amd.algorithms.mgm2_gpu import _compile_hypergraph
+from pydcop_amd.algorithms.mgm_gpu import _MgmSession
+from pydcop_amd.graph import Params
+
+GRAPH_TYPE = "constraints_hypergraph"
+HEADER_SIZE = 100
+UNIT_SIZE = 5
+
+algo_params = [
+    AlgoParameterDef("infinity", "int", None, 10000),
+    AlgoParameterDef("max_distance", "int", None, 50),
+    AlgoParameterDef("stop_cycle", "int", None, 0),
+    AlgoParameterDef("seed", "int", None, 0),
+    AlgoParameterDef("chunk", "int", None, 10),
+]
+
+
+def computation_memory(computation) -> float:
+    """pydcop/algorithms/dba.py:130-151: one value per neighbour."""
+    neighbors = set((n for l in computation.links for n in l.nodes if n not in computation.name))
+    return len(neighbors) * UNIT_SIZE
+
+
+def communication_load(src, target: str) -> float:
+    """pydcop/algorithms/dba.py:154-176: a value and a possible improvement."""
+    return 2 * UNIT_SIZE + HEADER_SIZE
+
+
+class _RoundEngine:
+    """DbaEngine behind the surface the session drives."""
+
+    def __init__(self, graph, params, p):
+        from pydcop_amd.dba import DbaEngine
+        self.graph = graph
+        self._e = DbaEngine(graph, params, infinity=p["infinity"], max_distance=int(p["max_distance"]), seed=int(p["seed"]))
+
+    def run(self, n: int):
+        self._e.run(int(n))
+
+    @property
+    def quiescent(self) -> bool:
+        """the engine has stopped: the session ends the run FINISHED, as the reference's does"""
+        return self._e.finished
+
+    def assignment(self):
+        return self._e.assignment()
+
+    @property
+    def cycle_count(self) -> int:
+        return self._e.cycle_count
+
+    def close(self):
+        self._e.close()
+
+
+class _DbaSession(_MgmSession):      # (same compilation of the hypergraph nodes and stop_cycle as mgm_gpu)
+    ALGO = "dba_gpu"
+
+    def _compile_graph(self, p):
+        return _compile_hypergraph(cd.node for cd in self.comp_defs.values())
+
+    def _engine_params(self, algo, p):
+        if algo.mode != "min":   # the constructor of DbaComputation (dba.py:295-298)
+            raise ValueError("DBA is a constraint **satisfaction** algorithm and only support minimization objective")
+        return Params(mode=algo.mode)
+
+    def _make_engine(self, params, p):
+        return _RoundEngine(self.graph, params, p)
+
+    def update_factor(self, name, old, fn):
+        raise ValueError("dba_gpu: change_factor_function is a maxsum_gpu feature")
+
+
+_base.SESSION_CLASSES["dba_gpu"] = _DbaSession
+
+
+class DbaGpuComputation(_base.MaxSumGpuVariableComputation):
+    """Stands for a DbaComputation (pydcop/algorithms/dba.py:272)."""
+
+    def footprint(self) -> float:
+        return computation_memory(self.computation_def.node)
+
+
+def build_computation(comp_def):
+    if comp_def.node.type != "VariableComputationNode":
+        raise ValueError("dba_gpu: unsupported computation node type " + str(comp_def.node.type))
+    if comp_def.algo.mode != "min":   # dba.py:295-298
+        raise ValueError("DBA is a constraint **satisfaction** algorithm and only support minimization objective")
+    return DbaGpuComputation(comp_def)

@@ -1,5 +1,5 @@
 """Direct API: solve a pyDCOP `DCOP` object (or a YAML file, or an .npz instance) on the GPU
-without agents -- synchronous Max-Sum by default, `algo=` "amaxsum", "dsa", "mgm", "mgm2" or "gdba" for the other
+without agents -- synchronous Max-Sum by default, `algo=` "amaxsum", "dsa", "mgm", "mgm2", "gdba" or "dba" for the other
 engines of the library.
 
 `pydcop.infrastructure.run.solve` (pydcop/infrastructure/run.py:49) deploys one
@@ -18,7 +18,7 @@ from .compile import assignment_to_values, compile_nodes
 from .graph import FlatGraph, Params
 
 
-ALGOS = ("maxsum", "amaxsum", "dsa", "mgm", "mgm2", "gdba")    # the iterative ones: `cycles` of them
+ALGOS = ("maxsum", "amaxsum", "dsa", "mgm", "mgm2", "gdba", "dba")    # the iterative ones: `cycles` of them
 CLI_ALGOS = ALGOS + ("dpop",)                              # DPOP has no cycles: solve_dcop_dpop / solve_flat_dpop
 
 
@@ -46,6 +46,9 @@ def _engine_for(graph: FlatGraph, params: Params, device: int, devices: int, lib
         if algo == "gdba":
             from .gdba import GdbaEngine
             return GdbaEngine(graph, params, device=device, lib_path=lib_path, **algo_kw)
+        if algo == "dba":
+            from .dba import DbaEngine
+            return DbaEngine(graph, params, device=device, lib_path=lib_path, **algo_kw)
         from .mgm import MgmEngine
         return MgmEngine(graph, params, device=device, lib_path=lib_path)
     from .engine import MaxSumEngine
@@ -56,7 +59,9 @@ def _engine_for(graph: FlatGraph, params: Params, device: int, devices: int, lib
 
 
 def _algo_kw(algo, variant, probability, p_mode, seed, threshold, favor, modifier="A", violation="NZ",
-             increase_mode="E"):
+             increase_mode="E", dba_infinity=10000, max_distance=50):
+    if algo == "dba":
+        return dict(infinity=dba_infinity, max_distance=max_distance, seed=seed)
     if algo == "gdba":
         return dict(modifier=modifier, violation=violation, increase_mode=increase_mode, seed=seed)
     if algo == "dsa":
@@ -81,6 +86,11 @@ def _run_and_trace(eng, algo: str, cycles: int, cost_every: int, infinity: float
     return curve
 
 
+def _dba_end(eng, algo):
+    """DBA stops by itself: the rounds it ran and whether a termination counter reached max_distance"""
+    return {"cycle": eng.cycle_count, "finished": eng.finished} if algo == "dba" else {}
+
+
 def compile_dcop(dcop, noise: float = 0.0, seed: int = 0) -> FlatGraph:
     """DCOP -> FlatGraph in the node / links order the reference's factor graph has
     (pydcop/computations_graph/factor_graph.py:245-296), built in O(E)."""
@@ -98,14 +108,18 @@ def solve_dcop(dcop, cycles: int = 30, *, damping: float = 0.5, damping_nodes: s
                precision: str = "f64", seed: int = 0, infinity: float = 10000, device: int = 0,
                cost_every: int = 0, lib_path: Optional[str] = None, devices: int = 1, algo: str = "maxsum",
                variant: str = "B", probability: float = 0.7, p_mode: str = "fixed", threshold: float = 0.5,
-               favor: str = "unilateral", modifier: str = "A", violation: str = "NZ", increase_mode: str = "E") -> Dict:
+               favor: str = "unilateral", modifier: str = "A", violation: str = "NZ", increase_mode: str = "E",
+               dba_infinity: int = 10000, max_distance: int = 50) -> Dict:
     """Synchronous Max-Sum for exactly `cycles` cycles; parameters and defaults are those
     of `pydcop.algorithms.maxsum` (maxsum.py:212-220), `infinity` that of
     `pydcop.infrastructure.run.solve` (run.py:49).  `algo`: "amaxsum" (`cycles` = generations of
     messages under FIFO delivery, same parameters), "dsa" (`variant`, `probability`, `p_mode` of
     pydcop.algorithms.dsa, dsa.py:119-125; `seed` keys its draws), "mgm" or "mgm2" (`threshold`,
     `favor` of pydcop.algorithms.mgm2, mgm2.py:142-146; `seed` keys its draws) or "gdba" (`modifier`,
-    `violation`, `increase_mode` of pydcop.algorithms.gdba, gdba.py:181-185; `seed` keys its draws); the local-search
+    `violation`, `increase_mode` of pydcop.algorithms.gdba, gdba.py:181-185; `seed` keys its draws) or "dba"
+    (`dba_infinity`, `max_distance`: the `infinity` and `max_distance` of pydcop.algorithms.dba, dba.py:265-268 -- a
+    cost >= dba_infinity is a violated constraint; min only; the run stops by itself, "cycle" is then the round it
+    stopped in and "finished" is true; `seed` keys its draws); the local-search
     algorithms take no noise (their variable costs enter as the reference's do).
 
     Returns {"assignment", "cost", "violation", "cycle", "cost_curve"}: the first three
@@ -116,14 +130,16 @@ def solve_dcop(dcop, cycles: int = 30, *, damping: float = 0.5, damping_nodes: s
     graph = compile_dcop(dcop, noise=noise if algo in ("maxsum", "amaxsum") else 0.0, seed=seed)
     params = Params(mode=dcop.objective, damping=damping, damping_nodes=damping_nodes,
                     stability=stability, start_messages=start_messages, dtype=precision)
-    algo_kw = _algo_kw(algo, variant, probability, p_mode, seed, threshold, favor, modifier, violation, increase_mode)
+    algo_kw = _algo_kw(algo, variant, probability, p_mode, seed, threshold, favor, modifier, violation, increase_mode,
+                       dba_infinity, max_distance)
     with _engine_for(graph, params, device, devices, lib_path, algo, algo_kw) as eng:
         curve = _run_and_trace(eng, algo, cycles, cost_every, infinity)
         idx, _ = eng.assignment()
+        extra = _dba_end(eng, algo)
     assignment = assignment_to_values(graph, idx)
     violation, cost = dcop.solution_cost(assignment, infinity)
     return {"assignment": assignment, "cost": cost, "violation": violation, "cycle": cycles,
-            "cost_curve": curve}
+            "cost_curve": curve, **extra}
 
 
 def solve_flat(graph: FlatGraph, objective: str = "min", cycles: int = 30, *, damping: float = 0.5,
@@ -131,24 +147,27 @@ def solve_flat(graph: FlatGraph, objective: str = "min", cycles: int = 30, *, da
                precision: str = "f64", infinity: float = 10000, device: int = 0, cost_every: int = 0,
                lib_path: Optional[str] = None, devices: int = 1, algo: str = "maxsum", variant: str = "B",
                probability: float = 0.7, p_mode: str = "fixed", seed: int = 0, threshold: float = 0.5,
-               favor: str = "unilateral", modifier: str = "A", violation: str = "NZ", increase_mode: str = "E") -> Dict:
+               favor: str = "unilateral", modifier: str = "A", violation: str = "NZ", increase_mode: str = "E",
+               dba_infinity: int = 10000, max_distance: int = 50) -> Dict:
     """`solve_dcop` for an already compiled instance (`FlatGraph`, e.g. loaded from the
     .npz instance format): no pyDCOP import at all.  Cost and violations come from the
     device (`mxs_eval_cost` = DCOP.solution_cost, pydcop/dcop/dcop.py:308-367); noise, if
     wanted, is already folded into `graph.var_cost` by whoever compiled the instance."""
     params = Params(mode=objective, damping=damping, damping_nodes=damping_nodes,
                     stability=stability, start_messages=start_messages, dtype=precision)
-    algo_kw = _algo_kw(algo, variant, probability, p_mode, seed, threshold, favor, modifier, violation, increase_mode)
+    algo_kw = _algo_kw(algo, variant, probability, p_mode, seed, threshold, favor, modifier, violation, increase_mode,
+                       dba_infinity, max_distance)
     with _engine_for(graph, params, device, devices, lib_path, algo, algo_kw) as eng:
         curve = _run_and_trace(eng, algo, cycles, cost_every, infinity)
         idx, _ = eng.assignment()
         cost, violation = eng.eval_cost(infinity=infinity)
+        extra = _dba_end(eng, algo)
     if graph.var_names is not None and graph.domains is not None:
         assignment = assignment_to_values(graph, idx)
     else:
         assignment = {f"v{i}": int(x) for i, x in enumerate(idx)}
     return {"assignment": assignment, "cost": cost, "violation": violation, "cycle": cycles,
-            "cost_curve": curve}
+            "cost_curve": curve, **extra}
 
 
 def solve_dcop_dpop(dcop, *, precision: str = "f64", infinity: float = 10000, device: int = 0, max_bytes: int = 0,
@@ -222,13 +241,15 @@ def main(argv=None):
     kinds = {"damping": float, "stability": float, "noise": float, "seed": int,
              "damping_nodes": str, "start_messages": str, "precision": str, "devices": int,
              "variant": str, "probability": float, "p_mode": str, "threshold": float, "favor": str,
-             "modifier": str, "violation": str, "increase_mode": str}
+             "modifier": str, "violation": str, "increase_mode": str, "infinity": int, "max_distance": int}
     kw = {}
     for item in args.algo_params:
         name, _, value = item.partition(":")
         if name not in kinds:
             raise SystemExit(f"Error: unknown parameter {name!r} (one of {sorted(kinds)})")
         kw[name] = kinds[name](value)
+    if "infinity" in kw:          # (`--infinity` is the one of DCOP.solution_cost; this one is dba.py:266)
+        kw["dba_infinity"] = kw.pop("infinity")
     t0 = time.perf_counter()
     if args.export:
         from . import plugin
@@ -243,7 +264,7 @@ def main(argv=None):
     if len(args.dcop_files) == 1 and args.dcop_files[0].endswith(".npz"):
         graph, header = FlatGraph.load(args.dcop_files[0])
         kw.pop("noise", None)  # folded into the instance when it was compiled
-        if args.algo not in ("dsa", "mgm2", "gdba"):
+        if args.algo not in ("dsa", "mgm2", "gdba", "dba"):
             kw.pop("seed", None)
         if args.algo == "dpop":
             res = solve_flat_dpop(graph, header.get("objective", "min"), infinity=args.infinity,

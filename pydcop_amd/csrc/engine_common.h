@@ -1,4 +1,4 @@
-// engine_common.h -- the host scaffold the DSA / MGM / MGM-2 / GDBA / DPOP engines share (dsa.hip, mgm.hip and the
+// engine_common.h -- the host scaffold the DSA / MGM / MGM-2 / GDBA / DBA / DPOP engines share (dsa.hip, mgm.hip and the
 // headers mgm.hip includes): error helpers, the device buffer, the counter-based generator, the host copy of an
 // mxs_graph with its checks and DCOP.solution_cost, the device side of the slot and the packed view of
 // local_search.h, and the shell of the mxs_*_create entry points.  Nothing here is a kernel; what only one engine
@@ -62,6 +62,7 @@ struct Buf {
 //   DSA    0 start value, 1 move test, 2 choice among the best values
 //   MGM-2  0 start, 1 offerer test, 2 partner, 3 best unilateral value, 4 the `favor: no` coin, 5 the accepted offer
 //   GDBA   6 start value (cycle 0), 7 one of the best values
+//   DBA    8 start value (cycle 0), 9 one of the best values (at the computation's cycle_count: round - 1)
 __host__ __device__ inline uint64_t mix64(uint64_t z) {
     z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
     z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;

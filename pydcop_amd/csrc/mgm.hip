@@ -711,3 +711,6 @@ int mxs_mgm_destroy(mxs_mgm* e) {
 
 // GDBA (pydcop/algorithms/gdba.py): the two phases of MGM's round plus per-slot modifier tables
 #include "gdba.h"
+
+// DBA (pydcop/algorithms/dba.py): the satisfaction algorithm GDBA generalises, on one bit per table entry
+#include "dba.h"

@@ -55,6 +55,8 @@ ABI_SYMBOLS = (
     "mxs_dpop_util_dims", "mxs_dpop_get_util", "mxs_dpop_destroy",
     "mxs_gdba_create", "mxs_gdba_reset", "mxs_gdba_run", "mxs_gdba_rounds", "mxs_gdba_get_state",
     "mxs_gdba_get_modifiers", "mxs_gdba_eval_cost", "mxs_gdba_destroy",
+    "mxs_dba_create", "mxs_dba_reset", "mxs_dba_run", "mxs_dba_rounds", "mxs_dba_finished", "mxs_dba_get_state",
+    "mxs_dba_get_weights", "mxs_dba_mask_bytes", "mxs_dba_eval_cost", "mxs_dba_destroy",
 )
 
 # ... and the MGM-2 entry points (kept apart: the header check of tests/test_abi.py reads names without digits)
@@ -211,6 +213,17 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
         "mxs_gdba_get_modifiers": ([vp, i32, vp, i64, C.POINTER(i64)], C.c_int),
         "mxs_gdba_eval_cost": ([vp, vp, C.c_double, C.POINTER(C.c_double), C.POINTER(i64)], C.c_int),
         "mxs_gdba_destroy": ([vp], C.c_int),
+        "mxs_dba_create": ([C.POINTER(CGraph), C.POINTER(CParams), vp, C.c_double, i32, C.c_uint64, i64, i32,
+                            C.POINTER(vp)], C.c_int),
+        "mxs_dba_reset": ([vp], C.c_int),
+        "mxs_dba_run": ([vp, i32], C.c_int),
+        "mxs_dba_rounds": ([vp, C.POINTER(i64)], C.c_int),
+        "mxs_dba_finished": ([vp, C.POINTER(i32), C.POINTER(i64)], C.c_int),
+        "mxs_dba_get_state": ([vp, vp, vp, vp, vp, vp, vp, vp, vp], C.c_int),
+        "mxs_dba_get_weights": ([vp, vp], C.c_int),
+        "mxs_dba_mask_bytes": ([vp, C.POINTER(i64)], C.c_int),
+        "mxs_dba_eval_cost": ([vp, vp, C.c_double, C.POINTER(C.c_double), C.POINTER(i64)], C.c_int),
+        "mxs_dba_destroy": ([vp], C.c_int),
         "mxs_cycle_bytes": ([vp, C.POINTER(i64), C.POINTER(i32)], C.c_int),
         "mxs_factor_order": ([vp, C.POINTER(i32)], C.c_int),
         "mxs_factor_kernels": ([vp, vp], C.c_int),

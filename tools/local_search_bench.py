@@ -1,7 +1,7 @@
 """Cycles per second of the DSA, MGM and MGM-2 engines (pydcop_amd/csrc/dsa.hip, mgm.hip, mgm2.h) on the
 100k-variable colouring instance of the bench and on the meeting instance (24 values, arity 3):
 
-    python tools/local_search_bench.py [--cycles 500] [--mgm2-rounds 200] [--gdba-rounds 200]
+    python tools/local_search_bench.py [--cycles 500] [--mgm2-rounds 200] [--gdba-rounds 200] [--dba-rounds 200]
 
 One JSON line per (algorithm, instance, kernels); "kernels": "packed" = the default (lane per
 constraint where the instance allows it, local_search.h), "slots" = the thread-per-variable
@@ -13,6 +13,9 @@ instance.  GDBA ("kernels": "gdba", pydcop_amd/csrc/gdba.h) follows, in f64 and 
 heaviest mode with live tables): the median of three timed runs after a warm-up, next to an MGM row timed the same
 way in the same precision (both tagged "timing": "median3"; "ratio_to_mgm"), with the bytes the engine keeps on the device for the share of the HBM
 peak; every timing ends with the engine's stream synchronised (run() returns after it).
+`--dba-rounds N` (default 0) prints three rows instead, timed the same way in one process on the hard 100k-variable
+3-colouring: DBA ("kernels": "dba", pydcop_amd/csrc/dba.h; `infinity: 1000`, `max_distance` above the round count so
+that nothing stops), GDBA (A, NZ, T, f64) and MGM (f64), with DBA's ratio to each.
 """
 import argparse
 import json
@@ -30,6 +33,40 @@ from pydcop_amd.mgm import MgmEngine  # noqa: E402
 from pydcop_amd.mgm2 import Mgm2Engine  # noqa: E402
 
 
+def median_us(eng, rounds):
+    eng.run(10)
+    times = []
+    for _ in range(3):
+        t0 = time.perf_counter()
+        eng.run(rounds)
+        times.append(1e6 * (time.perf_counter() - t0) / rounds)
+    return sorted(times)[1]
+
+
+def dba_rows(a):
+    from pydcop_amd.dba import DbaEngine
+    g = G.random_coloring(100_000, seed=0, variant="hard", unary_noise=0, names=False)
+    n = a.dba_rounds
+    rows = {}
+    eng = DbaEngine(g, Params(), infinity=1000, max_distance=4 * n + 100, seed=1, lib_path=a.lib)
+    rows["dba"] = median_us(eng, n)
+    assert not eng.finished
+    extra = {"mask_bytes": eng.mask_bytes, "violations": eng.eval_cost(infinity=1000)[1]}
+    eng.close()
+    eng = GdbaEngine(g, Params(), modifier="A", violation="NZ", increase_mode="T", seed=1, lib_path=a.lib)
+    rows["gdba"] = median_us(eng, n)
+    eng.close()
+    eng = MgmEngine(g, Params(), lib_path=a.lib)
+    rows["mgm"] = median_us(eng, n)
+    eng.close()
+    for algo, us in rows.items():
+        row = {"algo": algo, "instance": "coloring_100k_hard", "dtype": "int32" if algo == "dba" else "f64",
+               "timing": "median3", "n_vars": g.n_vars, "us_per_cycle": round(us, 2)}
+        if algo == "dba":
+            row.update(extra, kernels="dba", ratio_to_gdba_T=round(us / rows["gdba"], 3), ratio_to_mgm=round(us / rows["mgm"], 3))
+        print(json.dumps(row), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--cycles", type=int, default=500)
@@ -38,7 +75,10 @@ def main():
     ap.add_argument("--kernels", nargs="*", default=["packed", "strided", "slots", "csr_walk"])
     ap.add_argument("--mgm2-rounds", type=int, default=200, help="0: no MGM-2 rows")
     ap.add_argument("--gdba-rounds", type=int, default=200, help="0: no GDBA rows")
+    ap.add_argument("--dba-rounds", type=int, default=0, help="> 0: only the DBA / GDBA-T / MGM rows on the hard colouring")
     a = ap.parse_args()
+    if a.dba_rounds > 0:
+        return dba_rows(a)
     instances = [("coloring_100k", lambda: G.random_coloring(100_000, seed=0, names=False), Params()),
                  ("meeting_50k", lambda: G.meeting_like(50_000, dom=24, seed=0, names=False), Params(mode="max"))]
     for inst, g, p in instances:
