@@ -1,7 +1,13 @@
-"""Random small instances (domains 1..17, arities 1..4, both modes, both precisions, every
-start_messages / damping_nodes choice, random layout flags) through an engine build and its oracle,
-bit for bit.  `python tests/fuzz_common.py FIRST LAST` runs the seeds FIRST..LAST-1 on the emulated
-build; tests/test_fuzz_emu.py runs a few of them in the CPU suite."""
+"""Random instances through an engine build and its oracle, bit for bit.
+
+`instance(seed)` (domains 1..17, arities 1..4, both modes, both precisions, every start_messages /
+damping_nodes choice, random layout flags) feeds the Max-Sum sweep (`fuzz_maxsum`) and asynchronous Max-Sum,
+DSA and MGM (`fuzz_others`).  `local_instance(seed)` (3..60 or 65..200 variables: a full wave, a second and a
+third block of the thread-per-variable kernels; two or three unequal domain sizes in one graph) feeds MGM-2,
+GDBA and DBA (`fuzz_mgm2`, `fuzz_gdba`, `fuzz_dba`), `dpop_instance(seed)` (4..40 variables, sparse, forests,
+one-value variables, the caller's own tree every fourth seed) feeds DPOP (`fuzz_dpop`).
+`python tests/fuzz_common.py FIRST LAST` runs the seeds FIRST..LAST-1 of every driver on the emulated build;
+tests/test_fuzz_emu.py runs a few of them in the CPU suite, tests/test_gpu_fuzz.py on the GPU."""
 import os
 import sys
 
@@ -79,15 +85,318 @@ def fuzz_others(seed, lib_path):
         e.close(), o.close()
 
 
+# ---- MGM-2, GDBA, DBA, DPOP ---------------------------------------------------------------------------
+STEPS = (0, 1, 1, 3, 5)                  # the Python oracles dominate the run time: ten rounds in all
+LOCAL_DOMS = (1, 2, 3, 4, 5, 8, 9, 17)
+DBA_DOMS = (2, 3, 4, 5, 8, 9, 24, 32, 33, 64, 65)
+DPOP_DOMS = (1, 2, 3, 4, 5, 7)
+MAX_TABLE = 16_000                       # entries of one constraint table (and, over 32, words of a slot's bit rows)
+DPOP_MAX_ENTRIES = 300_000
+GDBA_STREAM = 22                         # of the streams 20..35 tried: every GDBA variant raises a modifier and moves within its two GPU seeds
+DPOP_FACTORS = (0.8, 1.8)                # constraints per variable
+GPU_SEEDS = {"mgm2": range(0, 48), "gdba": range(0, 48), "dba": range(0, 48), "dpop": range(0, 40)}   # tests/test_gpu_fuzz.py
+
+
+def local_instance(seed, dom_set=LOCAL_DOMS, slots=(0.8, 3.2), stream=20):
+    """-> (graph, rng).  Half the seeds 3..60 variables, the other half 65..200 (the halves alternate every 24
+    seeds, so that a seed-indexed choice of period 24 meets both); two or three distinct domain sizes of
+    `dom_set` in one graph; arities up to 3, up to 4 when every domain is 5 or less, fewer where a table would
+    pass MAX_TABLE entries; `slots`: the range of constraints a variable is in, on average (or a function
+    of the drawn domain sizes that gives it); `stream`: which random stream of the seed."""
+    from mgm_common import shuffled_names, with_init
+    rng = np.random.default_rng([seed, stream])
+    big = (seed + seed // 24) % 2 == 1
+    nv = int(rng.integers(65, 201)) if big else int(rng.integers(3, 61))
+    doms = tuple(int(x) for x in rng.choice(dom_set, size=int(rng.integers(2, 4)), replace=False))
+    top = max(doms)
+    max_arity = int(rng.integers(2, 5 if top <= 5 else 4))
+    while max_arity > 2 and top ** max_arity > MAX_TABLE:
+        max_arity -= 1
+    lo, hi = slots(doms) if callable(slots) else slots
+    nf = max(1, int(nv * rng.uniform(lo, hi) / (0.5 * (1 + max_arity))))     # (arities 1..max_arity, equally likely)
+    g = G.random_mixed(nv, nf, seed=int(rng.integers(0, 2 ** 31)), max_arity=max_arity, dom_choices=doms,
+                       float_tables=bool(rng.integers(0, 2)))
+    if rng.integers(0, 2):
+        g = with_init(g, seed)
+    if rng.integers(0, 2):
+        g = shuffled_names(g, seed)
+    return g, rng
+
+
+def mgm2_instance(seed):
+    """-> (graph, Params, MGM-2 kwargs)"""
+    from mgm2_oracle import FAVORS
+    g, rng = local_instance(seed)
+    kw = dict(favor=FAVORS[int(rng.integers(0, 3))], threshold=float(rng.choice([0.0, 0.3, 0.5, 0.6, 1.0])), seed=seed)
+    p = Params(mode="max" if rng.integers(0, 2) else "min", dtype="f32" if rng.integers(0, 3) == 0 else "f64")
+    if rng.integers(0, 4) == 0:          # 0 / 1 tables: global gains tie with unilateral ones, `favor` decides
+        g.tables = np.floor(g.tables) % 2
+    return g, p, kw
+
+
+def gdba_instance(seed):
+    """-> (graph, Params, GDBA kwargs): the variant follows the seed, 24 consecutive seeds cover all 24"""
+    import itertools
+    from gdba_common import dyadic_var_costs
+    from gdba_oracle import INCREASE_MODES, MODIFIERS, VIOLATIONS
+    mod, vio, inc = list(itertools.product(MODIFIERS, VIOLATIONS, INCREASE_MODES))[seed % 24]
+    g, rng = local_instance(seed, stream=GDBA_STREAM)
+    p = Params(mode="max" if rng.integers(0, 2) else "min", dtype="f32" if rng.integers(0, 3) == 0 else "f64")
+    # the reference sums the variable costs in the order of a Python set: real-valued ones (random_mixed's) only in
+    # mode T, as the pinned cases do (gdba_oracle.py, Determinism); dyadic ones or none elsewhere
+    costs = int(rng.integers(0, 3 if inc == "T" else 2))
+    if costs == 0:
+        g.var_cost = np.zeros_like(g.var_cost)
+    elif costs == 1:
+        g = dyadic_var_costs(g, seed)
+    return g, p, dict(modifier=mod, violation=vio, increase_mode=inc, seed=seed)
+
+
+def dba_slots(doms, density, infinity):
+    """How many constraints a variable of a DBA instance is in.  A value is free of violations with probability
+    (1 - density)^k under k constraints: k = ln D / -ln(1 - density) leaves about one such value among D, the
+    instances that are neither satisfied at once (the run stops, no weight ever rises) nor hopeless.  With
+    `infinity: 2` two violated constraints already reach infinity, and a variable all of whose values meet
+    three ends the run in round 1 ("no best value"): 0.4 k there, at most 4.5, about one at the highest density."""
+    k = float(np.log(np.mean(doms)) / -np.log(1.0 - density))
+    if infinity == 2:
+        if density > 0.5:
+            return 0.7, 1.5
+        k = min(max(0.4 * k, 1.5), 4.5)
+    else:
+        k = min(max(k, 1.5), 8.0)
+    return 0.75 * k, 1.25 * k
+
+
+def dba_instance(seed):
+    """-> (graph, Params, DBA kwargs): tables of 0 or c at a drawn violation density; (c, infinity) = (2, 2): an
+    eval can EQUAL infinity; (1000, 999.5): ceil(infinity) differs from it"""
+    pre = np.random.default_rng([seed, 22])
+    c, infinity = [(1000.0, 1000), (1000.0, 999.5), (2.0, 2)][int(pre.integers(0, 3))]
+    density = float(pre.choice([0.15, 0.5, 0.85]))
+    g, rng = local_instance(seed, DBA_DOMS, slots=lambda doms: dba_slots(doms, density, infinity))
+    g.tables = c * (rng.random(g.tables.shape[0]) < density)
+    g.var_cost = np.zeros_like(g.var_cost)
+    return g, Params(), dict(infinity=infinity, max_distance=int(rng.choice([2, 3, 50])), seed=seed)
+
+
+def keep_factors(g, n):
+    """the graph with its first n constraints only"""
+    from pydcop_amd.generators import _finish
+    h = _finish(g.dom_size, g.var_cost, g.factor_rowptr[:n + 1].copy(), g.edge_var[:g.factor_rowptr[n]].copy(),
+                g.tables[:g.table_off[n]].copy(), g.table_off[:n + 1].copy())
+    h.var_names = g.var_names
+    return h
+
+
+def reversed_dfs_tree(g):
+    """A pseudo-tree other than build_pseudotree's: per component a depth-first search from its variable of
+    the highest index, the neighbours walked in reverse; every constraint's scope is a clique of the
+    neighbour graph, and a depth-first tree keeps a clique on one root path."""
+    from pydcop_amd.dpop import neighbor_lists, pack_tree
+    nbrs = neighbor_lists(g)
+    n = g.n_vars
+    parent, children, seen = [-1] * n, [[] for _ in range(n)], [False] * n
+    for root in range(n - 1, -1, -1):
+        if seen[root]:
+            continue
+        seen[root] = True
+        stack = [(root, iter(reversed(nbrs[root])))]
+        while stack:
+            v, it = stack[-1]
+            u = next((u for u in it if not seen[u]), None)
+            if u is None:
+                stack.pop()
+                continue
+            seen[u] = True
+            parent[u] = v
+            children[v].append(u)
+            stack.append((u, iter(reversed(nbrs[u]))))
+    return pack_tree(parent, children)
+
+
+def measure_tree(g, tree):
+    """What the engine checks of a tree and sizes from it (dpop.h): parent and children lists consistent, every
+    variable reached from a root, every scope on one root path -> (separators by variable, all UTIL entries)."""
+    parent, crow, cidx = (np.asarray(a) for a in tree)
+    n = g.n_vars
+    assert len(parent) == n and len(crow) == n + 1 and len(cidx) == crow[-1]
+    for v in range(n):
+        assert all(parent[c] == v for c in cidx[crow[v]:crow[v + 1]])
+    assert sorted(int(c) for c in cidx) == [v for v in range(n) if parent[v] >= 0]
+    depth, order = np.zeros(n, dtype=np.int64), []
+    stack = [r for r in range(n) if parent[r] < 0]
+    while stack:
+        v = stack.pop()
+        order.append(v)
+        for c in cidx[crow[v]:crow[v + 1]]:
+            depth[c] = depth[v] + 1
+            stack.append(int(c))
+    assert len(order) == n, "a cycle"
+    sep = [set() for _ in range(n)]
+    for f in range(g.n_factors):
+        scope = [int(u) for u in g.edge_var[g.factor_rowptr[f]:g.factor_rowptr[f + 1]]]
+        low, path = max(scope, key=lambda u: depth[u]), set()
+        a = low
+        while a >= 0:
+            path.add(a)
+            a = int(parent[a])
+        assert set(scope) <= path, f"the scope of constraint {f} does not lie on one root path"
+        sep[low].update(scope)
+    total = 0
+    for v in reversed(order):
+        sep[v].discard(v)
+        if parent[v] >= 0:
+            sep[parent[v]].update(sep[v])
+            total += int(np.prod([int(g.dom_size[u]) for u in sep[v]], dtype=np.int64))
+    return sep, total
+
+
+def dpop_instance(seed):
+    """-> (graph, Params, tree or None, shrink steps).  4..40 variables, about as many constraints (forests and
+    variables without any among them), domains of DPOP_DOMS; every third seed integer tables on a few levels;
+    every fourth seed a tree of its own.  While the UTILs hold more than DPOP_MAX_ENTRIES entries in all, the
+    last quarter of the constraints goes: no seed is left out."""
+    from dpop_common import int_ties
+    from pydcop_amd.dpop import build_pseudotree
+    rng = np.random.default_rng([seed, 21])
+    nv = int(rng.integers(4, 41))
+    nf = max(1, int(nv * rng.uniform(*DPOP_FACTORS)))
+    doms = tuple(int(x) for x in rng.choice(DPOP_DOMS, size=int(rng.integers(2, 4)), replace=False))
+    g = G.random_mixed(nv, nf, seed=int(rng.integers(0, 2 ** 31)), max_arity=int(rng.integers(2, 4)), dom_choices=doms,
+                       float_tables=bool(rng.integers(0, 2)))
+    p = Params(mode="max" if rng.integers(0, 2) else "min", dtype="f32" if rng.integers(0, 3) == 0 else "f64")
+    if seed % 3 == 2:
+        g = int_ties(g, 2 + seed % 2)
+    own, shrinks = seed % 4 == 3, 0
+    while True:
+        tree = reversed_dfs_tree(g) if own else build_pseudotree(g)
+        if measure_tree(g, tree)[1] <= DPOP_MAX_ENTRIES:
+            return g, p, (tree if own else None), shrinks
+        g = keep_factors(g, g.n_factors - max(1, g.n_factors // 4))
+        shrinks += 1
+
+
+def fuzz_mgm2(seed, lib_path, steps=STEPS):
+    from mgm2_common import compare_mgm2
+    from mgm2_oracle import OracleMgm2
+    g, p, kw = mgm2_instance(seed)
+    compare_mgm2(OracleMgm2, g, p, kw, lib_path=lib_path, steps=steps)
+
+
+def fuzz_gdba(seed, lib_path, steps=STEPS):
+    from gdba_common import compare_gdba
+    from gdba_oracle import OracleGdba
+    g, p, kw = gdba_instance(seed)
+    compare_gdba(OracleGdba, g, p, kw, lib_path=lib_path, steps=steps)
+
+
+def dba_failing_step(g, p, kw, steps=STEPS):
+    """the index of the run call of `steps` in which the oracle raises IndexError (improve > 0 with no best
+    value: every eval above infinity), None where it raises in none"""
+    from dba_oracle import OracleDba
+    o = OracleDba(g, p, **kw)
+    for i, n in enumerate(steps):
+        try:
+            o.run(n)
+        except IndexError:
+            return i
+    return None
+
+
+def compare_dba_fallible(g, p, kw, lib_path=None, steps=STEPS):
+    """compare_dba; where the oracle raises IndexError, the engine returns its "no best value" error in the
+    same run call, and everything before that call is equal"""
+    import pytest
+    from dba_common import compare_dba, same_state
+    from dba_oracle import OracleDba
+    from pydcop_amd.dba import DbaEngine
+    from pydcop_amd.engine import MaxSumGpuError
+    bad = dba_failing_step(g, p, kw, steps)
+    if bad is None:
+        compare_dba(OracleDba, g, p, kw, lib_path=lib_path, steps=steps)
+        return
+    with DbaEngine(g, p, lib_path=lib_path, **kw) as eng:
+        ora = OracleDba(g, p, **kw)
+        assert eng.mask_bytes == ora.mask_bytes
+        for n in steps[:bad]:
+            eng.run(n), ora.run(n)
+            same_state(eng, ora, f"after {ora.cycle_count} rounds")
+        with pytest.raises(IndexError):
+            ora.run(steps[bad])
+        with pytest.raises(MaxSumGpuError, match="no best value"):
+            eng.run(steps[bad])
+
+
+def fuzz_dba(seed, lib_path, steps=STEPS):
+    g, p, kw = dba_instance(seed)
+    compare_dba_fallible(g, p, kw, lib_path=lib_path, steps=steps)
+
+
+def fuzz_dpop(seed, lib_path):
+    from dpop_common import compare_dpop
+    from dpop_oracle import OracleDpop
+    g, p, tree, _ = dpop_instance(seed)
+    compare_dpop(OracleDpop, g, p, lib_path=lib_path, tree=tree)
+
+
+# ---- what the oracles alone show of the sweep (tests/test_fuzz_emu.py asserts that it is not vacuous) ----
+def oracle_summary(engine, seed, steps=STEPS):
+    from dba_oracle import OracleDba
+    from dpop_oracle import OracleDpop
+    from gdba_oracle import OracleGdba
+    from mgm2_oracle import OracleMgm2
+    if engine == "dba":
+        g, p, kw = dba_instance(seed)
+        o, failed = OracleDba(g, p, **kw), False
+        try:
+            o.run(sum(steps))
+        except IndexError:
+            failed = True
+        return dict(stop_round=o.stop_round, increases=o.increases, moves=o.moves, failed=failed, kw=kw)
+    if engine == "gdba":
+        g, p, kw = gdba_instance(seed)
+        o = OracleGdba(g, p, **kw)
+        o.run(sum(steps))
+        return dict(pool=int(o.pool[:o.pool_size].sum()), moves=o.moves, kw=kw)
+    if engine == "mgm2":
+        g, p, kw = mgm2_instance(seed)
+        o = OracleMgm2(g, p, **kw)
+        o.run(sum(steps))
+        return dict(pair_moves=o.pair_moves, kw=kw)
+    g, p, tree, shrinks = dpop_instance(seed)
+    o = OracleDpop(g, p, tree=tree).solve()
+    seps = [dims for dims, _ in o.util.values()]
+    return dict(shrinks=shrinks, widest=max([len(d) for d in seps] or [0]),
+                one_value_in_separator=any(g.dom_size[u] == 1 for d in seps for u in d),
+                entries=o.stats()["total_entries"])
+
+
+def small_seeds(make, n=5, max_vars=20, ok=lambda *inst: True):
+    """the first n seeds whose instance `make(seed)` has at most max_vars variables (the reference is a Python
+    message loop) and passes `ok`"""
+    out, seed = [], 0
+    while len(out) < n:
+        inst = make(seed)
+        if inst[0].n_vars <= max_vars and ok(*inst):
+            out.append(seed)
+        seed += 1
+    return out
+
+
+DRIVERS = (fuzz_maxsum, fuzz_others, fuzz_mgm2, fuzz_gdba, fuzz_dba, fuzz_dpop)
+
+
 if __name__ == "__main__":
-    from emu.build_emu import build
+    import time
+    import dba_common
     from pydcop_amd import engine
     from oracle.maxsum_oracle import build as build_oracles
     build_oracles()
-    lib, bad = build(), 0
+    lib, bad, t0 = dba_common.emu_lib(), 0, time.time()
     engine.register_test_engine(lib)
     for s in range(int(sys.argv[1]), int(sys.argv[2])):
-        for f in (fuzz_maxsum, fuzz_others):
+        for f in DRIVERS:
             try:
                 f(s, lib)
             except Exception as ex:  # report and go on
@@ -95,4 +404,4 @@ if __name__ == "__main__":
                 print("FAIL", f.__name__, "seed", s, repr(ex)[:300], flush=True)
         if s % 25 == 24:
             print("... seed", s, "failures so far:", bad, flush=True)
-    print("failures:", bad)
+    print("failures:", bad, f"({time.time() - t0:.0f} s)")

@@ -165,6 +165,7 @@ class OracleMgm2:
         self.cost = np.zeros(nV, dtype=T)
         self.has_cost = np.zeros(nV, dtype=np.uint8)
         self.rounds = 0
+        self.pair_moves = 0          # moves of committed variables (both ends of a pair count)
         lonely = []
         for v in range(nV):
             if self.has_nb[v]:
@@ -323,6 +324,7 @@ class OracleMgm2:
             if move:
                 self.cur[v] = pv[v]
                 self.cost[v] = T(lcost[v] - pg[v])
+                self.pair_moves += v in committed
         self.rounds += 1
 
     @property

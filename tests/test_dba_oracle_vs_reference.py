@@ -70,3 +70,26 @@ def test_dba_reference_refuses_max():
         run_reference_dba(dcop, 1)
     with pytest.raises(ValueError, match="satisfaction"):
         OracleDba(g, Params(mode="max"))
+
+
+def _fuzz_seeds():
+    from fuzz_common import dba_instance, small_seeds
+    return small_seeds(dba_instance, n=6)
+
+
+@pytest.mark.parametrize("seed", _fuzz_seeds())
+def test_dba_oracle_equals_reference_on_random_instances(seed):
+    """the small end of the sweep of tests/fuzz_common.py: domains up to 65 values, `infinity` of 1000, 999.5
+    and 2 (an eval can equal it); where the oracle raises IndexError, so does the reference"""
+    from dba_oracle import OracleDba
+    from dba_reference import reference_state
+    from fuzz_common import STEPS, dba_failing_step, dba_instance
+    from pydcop_amd.graph import Params
+    g, p, kw = dba_instance(seed)
+    rounds = (1, 4, 10)
+    bad = dba_failing_step(g, p, kw, rounds)
+    for n in rounds[:bad]:
+        check_against_reference(g, kw, n)
+    if bad is not None:
+        with pytest.raises(IndexError):
+            reference_state(g, kw, rounds[bad])

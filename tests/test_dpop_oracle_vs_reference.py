@@ -105,3 +105,18 @@ def test_dpop_oracle_and_trees_equal_reference_on_yaml(instance):
         odims, otable = o.util[g.var_names.index(n)]
         assert [g.var_names[u] for u in odims] == dims
         np.testing.assert_array_equal(otable, table)
+
+
+def _fuzz_seeds():
+    from fuzz_common import dpop_instance, measure_tree, small_seeds
+    from pydcop_amd.dpop import build_pseudotree
+    # (the reference builds its own tree: the seeds of build_pseudotree's; its join is a Python loop)
+    return small_seeds(dpop_instance, n=6, ok=lambda g, p, tree, _: tree is None and measure_tree(g, build_pseudotree(g))[1] <= 12_000)
+
+
+@pytest.mark.parametrize("seed", _fuzz_seeds())
+def test_dpop_oracle_equals_reference_on_random_instances(seed):
+    """the small end of the sweep of tests/fuzz_common.py: one-value variables, forests, unequal domains"""
+    from fuzz_common import dpop_instance
+    g, p, _, _ = dpop_instance(seed)
+    check_against_reference(g, p.mode)

@@ -1,7 +1,13 @@
 """A slice of the random-instance sweep of tests/fuzz_common.py (emulated engine build against the
-oracles, bit for bit): domains 1..17, arities 1..4, every mode / precision / start / damping choice."""
+oracles, bit for bit): the Max-Sum sweep, asynchronous Max-Sum, DSA and MGM on domains 1..17, arities 1..4,
+every mode / precision / start / damping choice; MGM-2, GDBA, DBA and DPOP on the instances of
+`local_instance` / `dpop_instance` and on every constructed instance of tests/edge_shapes.py; and what the
+oracles alone must show over the seeds of tests/test_gpu_fuzz.py for that sweep to prove anything."""
 import pytest
 
+import dba_common
+import edge_shapes
+import fuzz_common
 from fuzz_common import fuzz_maxsum, fuzz_others
 
 
@@ -24,3 +30,85 @@ def test_fuzz_maxsum_emu_wide_domains(seed, oracle_built, monkeypatch):
     from emu.build_emu import build
     monkeypatch.setenv("FUZZ_DOMS", "big")
     fuzz_maxsum(seed, build())
+
+
+@pytest.fixture(scope="module")
+def emu_lib():
+    return dba_common.emu_lib()
+
+
+# (seeds past the GPU twin's: small and large halves of local_instance alternate)
+@pytest.mark.parametrize("seed", range(100, 108))
+def test_fuzz_mgm2_emu(seed, emu_lib, oracle_built):
+    fuzz_common.fuzz_mgm2(seed, emu_lib)
+
+
+@pytest.mark.parametrize("seed", range(100, 108))
+def test_fuzz_gdba_emu(seed, emu_lib):
+    fuzz_common.fuzz_gdba(seed, emu_lib)
+
+
+@pytest.mark.parametrize("seed", range(100, 108))
+def test_fuzz_dba_emu(seed, emu_lib):
+    fuzz_common.fuzz_dba(seed, emu_lib)
+
+
+@pytest.mark.parametrize("seed", range(100, 108))
+def test_fuzz_dpop_emu(seed, emu_lib):
+    fuzz_common.fuzz_dpop(seed, emu_lib)
+
+
+@pytest.mark.parametrize("edge", edge_shapes.all_edges(), ids=lambda e: e[0])
+def test_edge_shapes_emu(edge, emu_lib, oracle_built):
+    edge[1](emu_lib)
+
+
+def test_custom_trees_of_the_dpop_sweep_differ_from_the_built_in_ones():
+    import numpy as np
+    from pydcop_amd.dpop import build_pseudotree
+    differ = 0
+    for seed in range(3, 40, 4):
+        g, _, tree, _ = fuzz_common.dpop_instance(seed)
+        assert tree is not None
+        fuzz_common.measure_tree(g, tree)
+        differ += not np.array_equal(tree[0], build_pseudotree(g)[0])
+    assert differ >= 8
+
+
+# ---- the sweep must not pass vacuously: the oracles alone, over the seeds the GPU runs -------------------
+@pytest.mark.parametrize("engine", sorted(fuzz_common.GPU_SEEDS))
+def test_the_sweep_is_not_vacuous(engine, oracle_built):
+    seeds = fuzz_common.GPU_SEEDS[engine]
+    rows = [fuzz_common.oracle_summary(engine, s) for s in seeds]
+    n = len(rows)
+    if engine == "dba":
+        idle = [s for s, r in zip(seeds, rows) if 0 < r["stop_round"] < 3 or r["increases"] == 0]
+        failed = [s for s, r in zip(seeds, rows) if r["failed"]]
+        equal_inf = [s for s, r in zip(seeds, rows) if r["kw"]["infinity"] == 2]
+        print(f"dba: {len(idle)} of {n} seeds stop before round 3 or never raise a weight {idle}; "
+              f"{len(failed)} end in the 'no best value' error {failed}; {len(equal_inf)} with infinity = 2")
+        assert 4 * len(idle) <= n
+        assert failed and len(failed) < len(equal_inf)      # both ends of the `infinity: 2` draws are met
+    elif engine == "gdba":
+        zero = [s for s, r in zip(seeds, rows) if r["pool"] == 0]
+        print(f"gdba: {len(zero)} of {n} seeds end with an all-zero modifier pool {zero}")
+        assert 4 * len(zero) <= n
+        variants = {}
+        for r in rows:
+            k = (r["kw"]["modifier"], r["kw"]["violation"], r["kw"]["increase_mode"])
+            pool, moves = variants.get(k, (0, 0))
+            variants[k] = (pool + (r["pool"] > 0), moves + (r["moves"] > 0))
+        assert len(variants) == 24
+        assert all(pool > 0 and moves > 0 for pool, moves in variants.values()), variants
+    elif engine == "mgm2":
+        inner = [r for r in rows if 0 < r["kw"]["threshold"] < 1]
+        moved = sum(r["pair_moves"] > 0 for r in inner)
+        print(f"mgm2: {moved} of {len(inner)} seeds with 0 < threshold < 1 see a committed pair move")
+        assert inner and 2 * moved >= len(inner)
+    else:
+        wide = sum(r["widest"] >= 2 for r in rows)
+        ones = sum(r["one_value_in_separator"] for r in rows)
+        shrinks = max(r["shrinks"] for r in rows)
+        print(f"dpop: {wide} of {n} seeds with a separator of two or more variables, {ones} with a one-value variable "
+              f"in a separator, at most {shrinks} shrink steps, {sum(r['shrinks'] > 0 for r in rows)} seeds shrunk")
+        assert 2 * wide >= n and ones >= 5 and shrinks <= 2

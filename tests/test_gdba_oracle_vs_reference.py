@@ -59,3 +59,24 @@ def test_gdba_oracle_equals_reference_early_rounds(pick, rounds):
     from gdba_common import gdba_cases
     name, make, pkw, kw = gdba_cases()[pick]
     check_against_reference(make(), pkw["mode"], kw, rounds)
+
+
+def _fuzz_seeds():
+    from fuzz_common import gdba_instance, small_seeds
+    from pydcop_amd.dpop import neighbor_lists
+
+    def ok(g, p, kw):
+        # real-valued variable costs: the reference sums them in the order of a Python set (gdba_oracle.py);
+        # mode C walks every assignment of a variable's neighbours in Python
+        walk = max(int(np.prod(g.dom_size[nb], dtype=np.int64)) for nb in neighbor_lists(g))
+        return bool((g.var_cost * 64 == np.round(g.var_cost * 64)).all()) and walk <= 500
+    return small_seeds(gdba_instance, ok=ok)
+
+
+@pytest.mark.parametrize("seed", _fuzz_seeds())
+def test_gdba_oracle_equals_reference_on_random_instances(seed):
+    """the small end of the sweep of tests/fuzz_common.py: unequal domains, arities up to 4, the seed's variant"""
+    from fuzz_common import gdba_instance
+    g, p, kw = gdba_instance(seed)
+    for rounds in (1, 4, 10):
+        check_against_reference(g, p.mode, kw, rounds)

@@ -79,3 +79,17 @@ def test_mgm2_oracle_equals_reference_on_yaml(instance, favor):
         assert {n: g.domains[i][idx[i]] for i, n in enumerate(g.var_names)} == vals
         for i, n in enumerate(g.var_names):
             assert costs[n] is None or o.state()["cost"][i] == costs[n]
+
+
+def _fuzz_seeds():
+    from fuzz_common import mgm2_instance, small_seeds
+    return small_seeds(mgm2_instance)
+
+
+@pytest.mark.parametrize("seed", _fuzz_seeds())
+def test_mgm2_oracle_equals_reference_on_random_instances(seed):
+    """the small end of the sweep of tests/fuzz_common.py: unequal neighbour domains, every favor / threshold"""
+    from fuzz_common import mgm2_instance
+    g, p, kw = mgm2_instance(seed)
+    for rounds in (1, 4, 10):
+        check_against_reference(g, p.mode, kw, rounds)
