@@ -504,6 +504,41 @@ int mxs_dsa_cycles(const mxs_dsa *e, int64_t *cycles);
 int mxs_dsa_get_state(mxs_dsa *e, int32_t *idx, double *cost);
 int mxs_dsa_eval_cost(mxs_dsa *e, const int32_t *idx, double infinity, double *cost, int64_t *violations);
 int mxs_dsa_destroy(mxs_dsa *e);
+/* REPLICAS (2.7): n_replicas seeded runs of the instance in ONE engine, 1 <= n_replicas <= 4096 (else
+ * MXS_E_INVALID; device memory that does not suffice: MXS_E_NOMEM, nothing stays allocated).  The static data is
+ * stored once, the dynamic state is [replica][variable], every cycle of all replicas is the launches one replica
+ * needs.  Replica r is bit for bit mxs_dsa_create with seed seeds[r]; mxs_dsa_create IS n_replicas = 1 of this
+ * call.  Device memory per replica: n_vars * (8 + sizeof(T)) bytes of state plus 8 bytes per variable the packed
+ * kernel takes (its draws' keys are stored per (replica, variable), not recomputed in the kernel) -- 2.4 GB + 3.3 GB
+ * at 4096 replicas of 100 000 variables in f64; mxs_dsa_track_best adds 4 * n_vars bytes per replica.
+ * mxs_dsa_reset / _run / _set_value_rank act on all replicas; mxs_dsa_get_state and
+ * mxs_dsa_eval_cost(idx = NULL) mean replica 0. */
+int mxs_dsa_create_replicas(const mxs_graph *g, const mxs_params *p, int32_t variant, double probability,
+                            int32_t arity_mode, const uint64_t *seeds, int32_t n_replicas, int32_t device,
+                            mxs_dsa **out);
+int mxs_dsa_replicas(const mxs_dsa *e, int32_t *n);
+int mxs_dsa_get_state_replica(mxs_dsa *e, int32_t r, int32_t *idx, double *cost);
+/* DCOP.solution_cost of every replica's current assignment, reduced ON THE DEVICE: cost[n_replicas],
+ * violations[n_replicas] (either may be NULL).  What mxs_dsa_eval_cost gives for that assignment -- the
+ * constraints' entries plus eval_var_cost, an entry equal to `infinity` counted as a violation instead -- summed
+ * in f64 in a fixed order (no atomics: the same bits from call to call; the order is not the host's, so the two
+ * agree to rounding and exactly where every partial sum is exact).  The constraints' tables on the device are the
+ * engine's: with MXS_DTYPE_F32 the cost is that of the tables narrowed to f32 (eval_var_cost stays f64). */
+int mxs_dsa_replica_costs(mxs_dsa *e, double infinity, double *cost, int64_t *violations);
+/* The best state of every replica, kept on the device.  every > 0: each replica gets a record (violations, cost,
+ * cycle) and a snapshot of its values; the record is taken from the state as it is at this call (cycle 0 of a
+ * fresh engine) and again after mxs_dsa_reset, then inside mxs_dsa_run after every cycle c with c % every == 0,
+ * and replaced only on STRICT improvement: fewer violations, or as many and a strictly lower cost (higher with
+ * MXS_MODE_MAX).  Costs are those of mxs_dsa_replica_costs with this `infinity`.  every = 0: no records (the
+ * `infinity` is kept for mxs_dsa_get_best).  Every call clears the records.  every < 0: MXS_E_INVALID.  A call
+ * that fails with MXS_E_NOMEM leaves no records and mxs_dsa_get_best as the last successful call set it. */
+int mxs_dsa_track_best(mxs_dsa *e, int32_t every, double infinity);
+/* r >= 0: that replica; r = -1: the best replica = the lexicographic minimum of (violations, cost, index), the
+ * cost negated with MXS_MODE_MAX.  With records (every > 0) the records are ranked and returned (`cycle`: the
+ * cycle the record was taken after, `idx`: the snapshot); with every = 0 the current states are (`cycle`: the
+ * cycles run).  Any out pointer may be NULL.  Before the first mxs_dsa_track_best: MXS_E_STATE. */
+int mxs_dsa_get_best(mxs_dsa *e, int32_t r, int32_t *replica, int64_t *cycle, double *cost, int64_t *violations,
+                     int32_t *idx);
 
 /* ---- MGM-2 (pydcop/algorithms/mgm2.py) on the same flat arrays ----------------------------------
  * One round = the five phases of Mgm2Computation (value :742-786, offer :787-856, answer :858-890,

@@ -9,6 +9,16 @@ the orchestrator's timeout.  Extra parameter `seed` (default 0): every stochasti
 value, move test, choice among equally good values -- comes from a counter-based generator keyed on
 (seed, variable, cycle, draw), where the reference draws from Python's unseeded `random`: a run is
 reproducible, and bit for bit the reference's own DsaComputation under the same generator.
+
+`restarts: R` (default 1) runs R seeded replicas (seeds seed .. seed + R - 1) in the one engine and reports the
+best replica's values -- fewest entries equal to infinity, then the best solution cost, evaluated on the device;
+`best_every: k` (default 0: off) keeps every replica's best state seen at cycle 0 and after every k-th cycle and
+reports the best record instead of the best final state.  With the defaults the module is the single run above.
+The ranking takes no `infinity`: the module has no such parameter (the orchestrator applies its own to the values it
+collects), so every table entry, however large, is a cost and the replicas are ranked by the plain sum
+(`solve_dcop` / `solve_flat` rank with the caller's infinity).  The cost published beside a value is the one the
+replica's computation HOLDS NOW (dsa.py: the cost of its last move): with `best_every` the values are a snapshot of
+an earlier cycle, the held costs are still the current ones -- the engine keeps no snapshot of them.
 """
 from pydcop.algorithms import AlgoParameterDef
 
@@ -28,6 +38,8 @@ algo_params = [
     AlgoParameterDef("precision", "str", ["f64", "f32"], "f64"),
     AlgoParameterDef("seed", "int", None, 0),
     AlgoParameterDef("chunk", "int", None, 10),
+    AlgoParameterDef("restarts", "int", None, 1),
+    AlgoParameterDef("best_every", "int", None, 0),
 ]
 
 
@@ -49,13 +61,19 @@ class _CycleEngine:
         from pydcop_amd.dsa import DsaEngine
         self.graph = graph
         self._e = DsaEngine(graph, params, variant=p["variant"], probability=float(p["probability"]),
-                            p_mode=p["p_mode"], seed=int(p["seed"]))
+                            p_mode=p["p_mode"], seed=int(p["seed"]), replicas=int(p["restarts"]))
+        self._many = int(p["restarts"]) > 1 or int(p["best_every"]) > 0
+        if self._many:
+            self._e.track_best(int(p["best_every"]), float("inf"))
 
     def run(self, n: int):
         self._e.run(int(n))
 
     def assignment(self):
-        return self._e.assignment()
+        if not self._many:
+            return self._e.assignment()
+        best = self._e.best()               # the best replica: its record (best_every > 0) or its state
+        return best["idx"], self._e.assignment(best["replica"])[1]   # (held costs: the current ones, see above)
 
     @property
     def cycle_count(self) -> int:

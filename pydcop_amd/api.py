@@ -59,13 +59,13 @@ def _engine_for(graph: FlatGraph, params: Params, device: int, devices: int, lib
 
 
 def _algo_kw(algo, variant, probability, p_mode, seed, threshold, favor, modifier="A", violation="NZ",
-             increase_mode="E", dba_infinity=10000, max_distance=50):
+             increase_mode="E", dba_infinity=10000, max_distance=50, restarts=1):
     if algo == "dba":
         return dict(infinity=dba_infinity, max_distance=max_distance, seed=seed)
     if algo == "gdba":
         return dict(modifier=modifier, violation=violation, increase_mode=increase_mode, seed=seed)
     if algo == "dsa":
-        return dict(variant=variant, probability=probability, p_mode=p_mode, seed=seed)
+        return dict(variant=variant, probability=probability, p_mode=p_mode, seed=seed, replicas=int(restarts))
     if algo == "mgm2":
         return dict(threshold=threshold, favor=favor, seed=seed)
     return None
@@ -84,6 +84,26 @@ def _run_and_trace(eng, algo: str, cycles: int, cost_every: int, infinity: float
             c, v = eng.eval_cost(infinity=infinity)
             curve.append((done, c, v))
     return curve
+
+
+def _check_restarts(algo, restarts, best_every):
+    if int(restarts) < 1 or int(best_every) < 0:
+        raise ValueError("restarts must be at least 1 and best_every at least 0")
+    if algo != "dsa" and (int(restarts) != 1 or int(best_every) != 0):
+        raise ValueError("restarts / best_every: algo=\"dsa\" only")
+
+
+def _dsa_best(eng, algo, restarts, best_every, infinity):
+    """algo="dsa" with restarts / best_every: (idx of the best replica -- its record when tracking, else its final
+    state --, the result's extra keys); the device cost only ranks.  Else None."""
+    if algo != "dsa" or (int(restarts) == 1 and int(best_every) == 0):
+        return None
+    if int(best_every) == 0:
+        eng.track_best(0, infinity)         # (no records: ranks the final states)
+    best = eng.best()
+    costs, _ = eng.replica_costs(infinity)
+    return best["idx"], {"replica": best["replica"], "best_cycle": best["cycle"],
+                         "replica_costs": [float(c) for c in costs]}
 
 
 def _dba_end(eng, algo):
@@ -109,7 +129,7 @@ def solve_dcop(dcop, cycles: int = 30, *, damping: float = 0.5, damping_nodes: s
                cost_every: int = 0, lib_path: Optional[str] = None, devices: int = 1, algo: str = "maxsum",
                variant: str = "B", probability: float = 0.7, p_mode: str = "fixed", threshold: float = 0.5,
                favor: str = "unilateral", modifier: str = "A", violation: str = "NZ", increase_mode: str = "E",
-               dba_infinity: int = 10000, max_distance: int = 50) -> Dict:
+               dba_infinity: int = 10000, max_distance: int = 50, restarts: int = 1, best_every: int = 0) -> Dict:
     """Synchronous Max-Sum for exactly `cycles` cycles; parameters and defaults are those
     of `pydcop.algorithms.maxsum` (maxsum.py:212-220), `infinity` that of
     `pydcop.infrastructure.run.solve` (run.py:49).  `algo`: "amaxsum" (`cycles` = generations of
@@ -126,16 +146,29 @@ def solve_dcop(dcop, cycles: int = 30, *, damping: float = 0.5, damping_nodes: s
     as `DCOP.solution_cost` computes them for the selected values; `cost_curve` (when
     `cost_every` > 0) = [(cycle, cost, violations)] evaluated on the device every
     `cost_every` cycles (the reference's `--collect_on cycle_change`,
-    pydcop/commands/solve.py:356-376, without leaving the GPU)."""
+    pydcop/commands/solve.py:356-376, without leaving the GPU).
+
+    algo="dsa" only: `restarts` = R seeded runs (seeds seed .. seed + R - 1) in one engine, `best_every` = k > 0
+    keeps every run's best state seen at cycle 0 and after every k-th cycle, on the device.  The assignment is then
+    the best run's (its best record when tracking, else its final state; fewest violations, then cost, ranked on
+    the device -- `cost` and `violation` are still `DCOP.solution_cost` of it) and the result gains "replica",
+    "best_cycle" and "replica_costs" (the final states' device costs; `cost_curve` follows replica 0)."""
+    _check_restarts(algo, restarts, best_every)
     graph = compile_dcop(dcop, noise=noise if algo in ("maxsum", "amaxsum") else 0.0, seed=seed)
     params = Params(mode=dcop.objective, damping=damping, damping_nodes=damping_nodes,
                     stability=stability, start_messages=start_messages, dtype=precision)
     algo_kw = _algo_kw(algo, variant, probability, p_mode, seed, threshold, favor, modifier, violation, increase_mode,
-                       dba_infinity, max_distance)
+                       dba_infinity, max_distance, restarts)
     with _engine_for(graph, params, device, devices, lib_path, algo, algo_kw) as eng:
+        if algo == "dsa" and int(best_every) > 0:
+            eng.track_best(int(best_every), infinity)
         curve = _run_and_trace(eng, algo, cycles, cost_every, infinity)
         idx, _ = eng.assignment()
         extra = _dba_end(eng, algo)
+        best = _dsa_best(eng, algo, restarts, best_every, infinity)
+        if best:
+            idx, more = best
+            extra.update(more)
     assignment = assignment_to_values(graph, idx)
     violation, cost = dcop.solution_cost(assignment, infinity)
     return {"assignment": assignment, "cost": cost, "violation": violation, "cycle": cycles,
@@ -148,20 +181,27 @@ def solve_flat(graph: FlatGraph, objective: str = "min", cycles: int = 30, *, da
                lib_path: Optional[str] = None, devices: int = 1, algo: str = "maxsum", variant: str = "B",
                probability: float = 0.7, p_mode: str = "fixed", seed: int = 0, threshold: float = 0.5,
                favor: str = "unilateral", modifier: str = "A", violation: str = "NZ", increase_mode: str = "E",
-               dba_infinity: int = 10000, max_distance: int = 50) -> Dict:
+               dba_infinity: int = 10000, max_distance: int = 50, restarts: int = 1, best_every: int = 0) -> Dict:
     """`solve_dcop` for an already compiled instance (`FlatGraph`, e.g. loaded from the
     .npz instance format): no pyDCOP import at all.  Cost and violations come from the
     device (`mxs_eval_cost` = DCOP.solution_cost, pydcop/dcop/dcop.py:308-367); noise, if
     wanted, is already folded into `graph.var_cost` by whoever compiled the instance."""
     params = Params(mode=objective, damping=damping, damping_nodes=damping_nodes,
                     stability=stability, start_messages=start_messages, dtype=precision)
+    _check_restarts(algo, restarts, best_every)
     algo_kw = _algo_kw(algo, variant, probability, p_mode, seed, threshold, favor, modifier, violation, increase_mode,
-                       dba_infinity, max_distance)
+                       dba_infinity, max_distance, restarts)
     with _engine_for(graph, params, device, devices, lib_path, algo, algo_kw) as eng:
+        if algo == "dsa" and int(best_every) > 0:
+            eng.track_best(int(best_every), infinity)
         curve = _run_and_trace(eng, algo, cycles, cost_every, infinity)
         idx, _ = eng.assignment()
-        cost, violation = eng.eval_cost(infinity=infinity)
         extra = _dba_end(eng, algo)
+        best = _dsa_best(eng, algo, restarts, best_every, infinity)
+        if best:
+            idx, more = best
+            extra.update(more)
+        cost, violation = eng.eval_cost(idx, infinity=infinity) if best else eng.eval_cost(infinity=infinity)
     if graph.var_names is not None and graph.domains is not None:
         assignment = assignment_to_values(graph, idx)
     else:
@@ -241,7 +281,8 @@ def main(argv=None):
     kinds = {"damping": float, "stability": float, "noise": float, "seed": int,
              "damping_nodes": str, "start_messages": str, "precision": str, "devices": int,
              "variant": str, "probability": float, "p_mode": str, "threshold": float, "favor": str,
-             "modifier": str, "violation": str, "increase_mode": str, "infinity": int, "max_distance": int}
+             "modifier": str, "violation": str, "increase_mode": str, "infinity": int, "max_distance": int,
+             "restarts": int, "best_every": int}
     kw = {}
     for item in args.algo_params:
         name, _, value = item.partition(":")
@@ -286,6 +327,9 @@ def main(argv=None):
            "msg_count": 0, "msg_size": 0, "agt_metrics": {}}
     if res["cost_curve"]:
         out["cost_curve"] = res["cost_curve"]
+    for key in ("replica", "best_cycle", "replica_costs"):      # (-p restarts / best_every)
+        if key in res:
+            out[key] = res[key]
     print(json.dumps(out, sort_keys=True, indent="  "))
 
 

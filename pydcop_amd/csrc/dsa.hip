@@ -8,6 +8,16 @@
 // variable on the slot view or the CSR walk otherwise; bit-identical results.  The dynamic state lives
 // in packed order (Dev::q).
 //
+// REPLICAS: one engine advances R seeded runs of the instance with the same launches (the restarts a user of
+// a randomised local search makes anyway).  Everything static -- CSR arrays, slot view, row view, packed
+// records, tables, f_opt, prob -- is stored once; the dynamic state is [R][n_vars] (cur[2], cost), the seeds
+// are a device array, the packed kernel's keys are [R][packed variables].  The replica is folded into
+// blockIdx.x (block = replica * blocks_per_replica + block of the replica): whole blocks belong to one
+// replica, everything a kernel derives from the replica is block-uniform (R = 1 runs instantiations without it).  Replica r is bit for bit the
+// single-seed run with seed seeds[r]; mxs_dsa_create is R = 1 of the same path.  Per replica, the solution
+// cost of the current assignment is reduced on the device (k_dsa_cost_partial / k_dsa_cost_final: fixed
+// shape, no atomics) and the best state seen can be kept on the device (k_dsa_best_copy).
+//
 // The reference draws from Python's unseeded `random` module (initial value, move test, choice
 // among the best values).  Here every draw comes from a counter-based generator keyed on (seed,
 // variable, cycle, draw) -- uniform() of engine_common.h, the same function in oracle/dsa_oracle.c and, patched into
@@ -42,13 +52,15 @@ constexpr int TPB = 64;  // one wave per block: 100k variables spread over every
 template <typename T>
 struct Dev {
     int32_t n_vars, is_max, variant;
-    uint64_t seed;
+    int32_t bpr;          // blocks per replica of the launch being made (block = replica * bpr + b)
+    int32_t n_pack;       // packed variables (the row length of pack_key)
+    const uint64_t* seeds;  // [replicas]
     int64_t cycle;        // cycle_count of the evaluation being made
     const int32_t *dom_size, *factor_rowptr, *edge_var, *edge_factor, *var_rowptr, *var_edges, *n_neigh;
     const int64_t* table_off;
     const T *tables, *f_opt;
     const double* prob;
-    const int32_t* cur;
+    const int32_t* cur;          // [replicas][n_vars], as cur_out and cost: replica r at + r * n_vars (64-bit)
     int32_t* cur_out;
     T* cost;
     lsearch::Slots slots;
@@ -63,37 +75,57 @@ struct Dev {
     // thread-per-variable kernels translate through q[]; the random draws stay keyed on graph indices.
     const int32_t* q;
     const int32_t* pack_dom;               // [packed variables] dom_size, in packed order
-    const uint64_t* pack_key;              // [packed variables] uniform_key(seed, graph index): the random draws' key
+    const uint64_t* pack_key;              // [replicas][packed variables] uniform_key(seeds[r], graph index): the draws' key
     const double* pack_prob;               // [packed variables] the change probability
 };
 
+// the replica of this block and the block's index inside the replica (block-uniform).  REP = false: the
+// instantiation of the cycle kernels for ONE replica -- nothing is derived from blockIdx.x, the code of a
+// single-seed engine is what it was before there were replicas.
+template <bool REP, typename T>
+__device__ inline int replica_of_block(const Dev<T>& g, int* b) {
+    if constexpr (!REP) {
+        *b = (int)blockIdx.x;
+        return 0;
+    } else {
+        const int r = (int)(blockIdx.x / (unsigned)g.bpr);
+        *b = (int)blockIdx.x - r * g.bpr;
+        return r;
+    }
+}
+
 template <typename T>
-__device__ T constraint_at(const Dev<T>& g, int f, int v, int x) {
+__device__ T constraint_at(const Dev<T>& g, const int32_t* cur, int f, int v, int x) {
     int64_t lin = 0;
     for (int e = g.factor_rowptr[f]; e < g.factor_rowptr[f + 1]; ++e) {
         const int u = g.edge_var[e];
-        lin = lin * g.dom_size[u] + (u == v ? x : g.cur[g.q[u]]);
+        lin = lin * g.dom_size[u] + (u == v ? x : cur[g.q[u]]);
     }
     return g.tables[g.table_off[f] + lin];
 }
 
 // assignment_cost (relations.py:1513-1533): cost = 0; cost += c(...) in constraints order
 template <typename T>
-__device__ T assignment_cost(const Dev<T>& g, int v, int x) {
+__device__ T assignment_cost(const Dev<T>& g, const int32_t* cur, int v, int x) {
     T cost = (T)0;
     for (int k = g.var_rowptr[v]; k < g.var_rowptr[v + 1]; ++k)
-        cost += constraint_at(g, g.edge_factor[g.var_edges[k]], v, x);
+        cost += constraint_at(g, cur, g.edge_factor[g.var_edges[k]], v, x);
     return cost;
 }
 
 // evaluate_cycle, dsa.py:319-359 + variant_a/b/c :361-409 + probabilistic_change :411-419
-template <typename T>
+template <typename T, bool REP>
 __global__ void __launch_bounds__(TPB) k_dsa_cycle(Dev<T> g) {
-    const int tid = blockIdx.x * blockDim.x + threadIdx.x;
+    int b;
+    const int r = replica_of_block<REP>(g, &b);
+    const int tid = b * (int)blockDim.x + (int)threadIdx.x;
     if (tid >= g.n_list) return;
+    const int64_t roff = (int64_t)r * g.n_vars;
+    const int32_t* cur = g.cur + roff;
+    const uint64_t seed = g.seeds[r];
     const int v = g.var_list ? g.var_list[tid] : tid;
     const int qv = g.q[v];
-    const int mine = g.cur[qv];
+    const int mine = cur[qv];
     int out = mine;
     if (g.n_neigh[v] != 0) {
         const int D = g.dom_size[v];
@@ -101,7 +133,7 @@ __global__ void __launch_bounds__(TPB) k_dsa_cycle(Dev<T> g) {
         int n_best = 0, first_best = -1;
         bool has_cur = false;
         for (int x = 0; x < D; ++x) {
-            const T c = assignment_cost(g, v, x);
+            const T c = assignment_cost(g, cur, v, x);
             if (c == best_cost) {
                 n_best += 1;
                 if (x == mine) has_cur = true;
@@ -112,7 +144,7 @@ __global__ void __launch_bounds__(TPB) k_dsa_cycle(Dev<T> g) {
                 has_cur = x == mine;
             }
         }
-        const T current_cost = assignment_cost(g, v, mine);
+        const T current_cost = assignment_cost(g, cur, v, mine);
         const T diff = current_cost - best_cost;
         const T delta = diff < (T)0 ? -diff : diff;
         bool attempt = false, drop_cur = false;
@@ -122,19 +154,19 @@ __global__ void __launch_bounds__(TPB) k_dsa_cycle(Dev<T> g) {
             if (g.variant == 1) {  // B: some constraint is not at its optimum (dsa.py:421-433)
                 for (int k = g.var_rowptr[v]; k < g.var_rowptr[v + 1] && !attempt; ++k) {
                     const int f = g.edge_factor[g.var_edges[k]];
-                    if (constraint_at(g, f, v, mine) != g.f_opt[f]) attempt = true;
+                    if (constraint_at(g, cur, f, v, mine) != g.f_opt[f]) attempt = true;
                 }
             } else if (g.variant == 2) {
                 attempt = true;
             }
             if (attempt && n_best > 1 && has_cur) drop_cur = true;  // best_values.remove(current_value)
         }
-        if (attempt && g.prob[v] > uniform(g.seed, v, g.cycle + 1, 1)) {
+        if (attempt && g.prob[v] > uniform(seed, v, g.cycle + 1, 1)) {
             const int n = n_best - (drop_cur ? 1 : 0);
-            int j = (int)(uniform(g.seed, v, g.cycle + 1, 2) * n);
+            int j = (int)(uniform(seed, v, g.cycle + 1, 2) * n);
             int pick = first_best;
             for (int x = 0; x < D; ++x) {  // the j-th best value in domain order, the current one skipped
-                if (assignment_cost(g, v, x) != best_cost) continue;
+                if (assignment_cost(g, cur, v, x) != best_cost) continue;
                 if (drop_cur && x == mine) continue;
                 if (j-- == 0) {
                     pick = x;
@@ -142,31 +174,36 @@ __global__ void __launch_bounds__(TPB) k_dsa_cycle(Dev<T> g) {
                 }
             }
             out = pick;
-            g.cost[qv] = best_cost;  // value_selection(choice, best_cost)
+            g.cost[roff + qv] = best_cost;  // value_selection(choice, best_cost)
         }
     }
-    g.cur_out[qv] = out;
+    g.cur_out[roff + qv] = out;
 }
 
 // the same cycle on the slot view (local_search.h): the D costs in registers, one pass over the
 // variable's constraints instead of 2D+1 CSR walks; domains of at most MAXD values
-template <typename T, int MAXD>
+template <typename T, int MAXD, bool REP>
 __global__ void __launch_bounds__(TPB) k_dsa_cycle_slots(Dev<T> g) {
-    const int tid = blockIdx.x * blockDim.x + threadIdx.x;
+    int b;
+    const int r = replica_of_block<REP>(g, &b);
+    const int tid = b * (int)blockDim.x + (int)threadIdx.x;
     if (tid >= g.n_list) return;
+    const int64_t roff = (int64_t)r * g.n_vars;
+    const int32_t* cur = g.cur + roff;
+    const uint64_t seed = g.seeds[r];
     const int v = g.var_list ? g.var_list[tid] : tid;
     const int qv = g.q[v];
-    const int mine = g.cur[qv];
+    const int mine = cur[qv];
     int out = mine;
     if (g.n_neigh[v] != 0) {
         const int D = g.dom_size[v];
         const int s0 = g.var_rowptr[v], s1 = g.var_rowptr[v + 1];
         T c[MAXD];
         if (g.slots.rows != nullptr && s0 < s1 && g.slots.row_base[s0] >= 0) {  // contiguous rows (local_search.h)
-            if (g.slots.rows_int8) lsearch::costs_of_values_rows<T, int8_t, MAXD>(g.slots, g.cur, s0, s1, D, true, c);
-            else lsearch::costs_of_values_rows<T, T, MAXD>(g.slots, g.cur, s0, s1, D, true, c);
+            if (g.slots.rows_int8) lsearch::costs_of_values_rows<T, int8_t, MAXD>(g.slots, cur, s0, s1, D, true, c);
+            else lsearch::costs_of_values_rows<T, T, MAXD>(g.slots, cur, s0, s1, D, true, c);
         } else {
-            lsearch::costs_of_values<T, MAXD>(g.slots, g.tables, g.cur, s0, s1, D, true, c);
+            lsearch::costs_of_values<T, MAXD>(g.slots, g.tables, cur, s0, s1, D, true, c);
         }
         T best_cost = g.is_max ? -(T)INFINITY : (T)INFINITY;
         int n_best = 0, first_best = -1;
@@ -194,7 +231,7 @@ __global__ void __launch_bounds__(TPB) k_dsa_cycle_slots(Dev<T> g) {
                 for (int s = s0; s < s1 && !attempt; ++s) {
                     int64_t off = g.slots.base[s] + (int64_t)mine * g.slots.stride_v[s];
                     for (int k = g.slots.nb_rowptr[s]; k < g.slots.nb_rowptr[s + 1]; ++k)
-                        off += (int64_t)g.cur[g.slots.nb_var[k]] * g.slots.nb_stride[k];
+                        off += (int64_t)cur[g.slots.nb_var[k]] * g.slots.nb_stride[k];
                     if (g.tables[off] != g.f_opt[g.edge_factor[g.var_edges[s]]]) attempt = true;
                 }
             } else if (g.variant == 2) {
@@ -202,9 +239,9 @@ __global__ void __launch_bounds__(TPB) k_dsa_cycle_slots(Dev<T> g) {
             }
             if (attempt && n_best > 1 && has_cur) drop_cur = true;
         }
-        if (attempt && g.prob[v] > uniform(g.seed, v, g.cycle + 1, 1)) {
+        if (attempt && g.prob[v] > uniform(seed, v, g.cycle + 1, 1)) {
             const int n = n_best - (drop_cur ? 1 : 0);
-            int j = (int)(uniform(g.seed, v, g.cycle + 1, 2) * n);
+            int j = (int)(uniform(seed, v, g.cycle + 1, 2) * n);
             int pick = first_best;
             bool done = false;
 #pragma unroll
@@ -216,10 +253,10 @@ __global__ void __launch_bounds__(TPB) k_dsa_cycle_slots(Dev<T> g) {
                     }
                 }
             out = pick;
-            g.cost[qv] = best_cost;
+            g.cost[roff + qv] = best_cost;
         }
     }
-    g.cur_out[qv] = out;
+    g.cur_out[roff + qv] = out;
 }
 
 // the same cycle on the PACKED view (local_search.h): one lane per (variable, constraint), the
@@ -227,11 +264,15 @@ __global__ void __launch_bounds__(TPB) k_dsa_cycle_slots(Dev<T> g) {
 // record, the D costs by cross-lane sums in slot order; every lane of a variable then takes the
 // same decision, lane k = 0 writes it.  TT = int8_t (records of small integers) or T.
 constexpr int PACK_TPB = 256;
-template <typename T, typename TT>
+template <typename T, typename TT, bool REP>
 __global__ void __launch_bounds__(PACK_TPB) k_dsa_cycle_pack(Dev<T> g) {
     constexpr int MAXD = lsearch::PACK_D;
-    const int64_t pos = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    int b;
+    const int r = replica_of_block<REP>(g, &b);
+    const int64_t pos = (int64_t)b * blockDim.x + threadIdx.x;
     if (pos >= g.pack.n_lanes) return;  // whole waves (n_lanes is a multiple of 64)
+    const int64_t roff = (int64_t)r * g.n_vars;
+    const int32_t* cur = g.cur + roff;
     const lsearch::PackWave wm = g.pack.waves[__builtin_amdgcn_readfirstlane((int)(pos >> 6))];
     const uint32_t dn = (uint32_t)wm.deg_nv;
     const int deg = (int)(dn & 255u), nv = (int)((dn >> 8) & 255u);
@@ -241,12 +282,12 @@ __global__ void __launch_bounds__(PACK_TPB) k_dsa_cycle_pack(Dev<T> g) {
     const bool has = var < nv;
     const int qv = wm.first + (has ? var : 0);  // packed position: the index into the dynamic state
     const int seg = l - k;
-    const int mine = g.cur[qv];
+    const int mine = cur[qv];
     const int D = g.pack_dom[qv];
-    const uint64_t key = g.pack_key[qv];     // the variable's key of the random draws (its graph index inside)
+    const uint64_t key = g.pack_key[(int64_t)r * g.n_pack + qv];     // the variable's key of the random draws (its graph index inside)
     const double prob = g.pack_prob[qv];     // requested with the others, used after the decision
     T t[MAXD], c[MAXD];
-    lsearch::pack_costs<T, TT>(g.pack, g.cur, pos, deg, seg, true, t, c);
+    lsearch::pack_costs<T, TT>(g.pack, cur, pos, deg, seg, true, t, c);
     T best_cost = g.is_max ? -(T)INFINITY : (T)INFINITY;   // find_optimal, relations.py:1622-1638
     int n_best = 0, first_best = -1;
     bool has_cur = false;
@@ -297,21 +338,149 @@ __global__ void __launch_bounds__(PACK_TPB) k_dsa_cycle_pack(Dev<T> g) {
         moved = true;
     }
     if (has && k == 0) {
-        g.cur_out[qv] = out;
-        if (moved) g.cost[qv] = best_cost;  // value_selection(choice, best_cost)
+        g.cur_out[roff + qv] = out;
+        if (moved) g.cost[roff + qv] = best_cost;  // value_selection(choice, best_cost)
     }
 }
+
+// the start state of every replica: draw 0 of cycle 0 under seeds[r] (random_value_selection, dsa.py:291); a
+// variable without neighbours takes its optimal_cost_value (iso_val >= 0, the same in every replica).  Both
+// `cur` buffers: the packed launch writes only the variables that have neighbours.
+constexpr int AUX_TPB = 256;
+template <typename T>
+__global__ void __launch_bounds__(AUX_TPB) k_dsa_init(Dev<T> g, const int32_t* iso_val, const T* iso_cost, int32_t* cur0,
+                                                      int32_t* cur1) {
+    int b;
+    const int r = replica_of_block<true>(g, &b);
+    const int v = b * (int)blockDim.x + (int)threadIdx.x;
+    if (v >= g.n_vars) return;
+    const int64_t at = (int64_t)r * g.n_vars + g.q[v];
+    const int iso = iso_val[v];
+    const int x = iso >= 0 ? iso : (int32_t)(uniform(g.seeds[r], v, 0, 0) * g.dom_size[v]);
+    cur0[at] = x;
+    cur1[at] = x;
+    g.cost[at] = iso >= 0 ? iso_cost[v] : (T)0;
+}
+
+// ---- the solution cost of every replica's current assignment (HostGraph::eval_cost = DCOP.solution_cost):
+// the constraints' entries plus the variables' own eval_var_cost, an entry equal to `infinity` counted as a
+// violation instead.  Items = the constraints, then the variables.  FIXED SHAPE: a thread folds COST_RUN
+// consecutive items in index order, the block's COST_TPB sums are combined by one tree in LDS, the block's
+// partial goes to part[r][b]; k_dsa_cost_final adds a replica's partials in index order.  No atomics: the same
+// bits from run to run.  Sums in f64; the tables are the engine's (T): in f32 mode the cost is that of the
+// narrowed tables (eval_var_cost is kept in f64).
+constexpr int COST_TPB = 256, COST_RUN = 4;
+struct CostArgs {
+    const int64_t* coff;     // [n_vars + 1] offsets into evc
+    const double* evc;       // eval_var_cost
+    int32_t n_factors;
+    double infinity;
+    double* part_cost;       // [n_rep][bpr]
+    long long* part_viol;
+};
+template <typename T>
+__global__ void __launch_bounds__(COST_TPB) k_dsa_cost_partial(Dev<T> g, CostArgs a) {
+    __shared__ double s_cost[COST_TPB];
+    __shared__ long long s_viol[COST_TPB];
+    int b;
+    const int r = replica_of_block<true>(g, &b);
+    const int32_t* cur = g.cur + (int64_t)r * g.n_vars;
+    const int t = (int)threadIdx.x;
+    const int64_t n_items = (int64_t)a.n_factors + g.n_vars;
+    const int64_t i0 = ((int64_t)b * COST_TPB + t) * COST_RUN;
+    double soft = 0.0;
+    long long hard = 0;
+    for (int64_t i = i0; i < i0 + COST_RUN && i < n_items; ++i) {
+        double e;
+        if (i < a.n_factors) {
+            e = (double)constraint_at(g, cur, (int)i, -1, 0);
+        } else {
+            const int v = (int)(i - a.n_factors);
+            e = a.evc[a.coff[v] + cur[g.q[v]]];
+        }
+        if (e != a.infinity) soft += e;
+        else hard += 1;
+    }
+    s_cost[t] = soft;
+    s_viol[t] = hard;
+    __syncthreads();
+    for (int s = COST_TPB / 2; s > 0; s >>= 1) {
+        if (t < s) {
+            s_cost[t] += s_cost[t + s];
+            s_viol[t] += s_viol[t + s];
+        }
+        __syncthreads();
+    }
+    if (t == 0) {
+        a.part_cost[(int64_t)r * g.bpr + b] = s_cost[0];
+        a.part_viol[(int64_t)r * g.bpr + b] = s_viol[0];
+    }
+}
+
+// the best state a replica has shown (mxs_dsa_track_best): the record and the snapshot, in packed order
+struct BestRec {
+    double* cost;          // [n_rep]
+    long long* viol;
+    long long* cycle;
+    int32_t* improved;     // [n_rep] written by k_dsa_cost_final, read by k_dsa_best_copy (the next launch)
+    int32_t* idx;          // [n_rep][n_vars]
+};
+// thread per replica: the partials in index order; mode 0: the costs alone, 1: improved[r] = the current state
+// is STRICTLY better than the record (fewer violations, or as many and a lower -- max: higher -- cost),
+// 2: improved[r] = 1 (the first record).  The record itself is not touched here.
+__global__ void __launch_bounds__(64) k_dsa_cost_final(int n_rep, int n_blocks, int is_max, const double* part_cost,
+                                                       const long long* part_viol, double* cost, long long* viol, int mode,
+                                                       BestRec best) {
+    const int r = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+    if (r >= n_rep) return;
+    double soft = 0.0;
+    long long hard = 0;
+    for (int b = 0; b < n_blocks; ++b) {
+        soft += part_cost[(int64_t)r * n_blocks + b];
+        hard += part_viol[(int64_t)r * n_blocks + b];
+    }
+    cost[r] = soft;
+    viol[r] = hard;
+    if (mode == 2) {
+        best.improved[r] = 1;
+    } else if (mode == 1) {
+        const long long bv = best.viol[r];
+        const double bc = best.cost[r];
+        best.improved[r] = (hard < bv || (hard == bv && (is_max ? soft > bc : soft < bc))) ? 1 : 0;
+    }
+}
+// a launch of its own, after k_dsa_cost_final in stream order: the replicas that improved copy their state
+// and take the new record (nothing in this launch reads a record)
+__global__ void __launch_bounds__(AUX_TPB) k_dsa_best_copy(int n_vars, int bpr, const int32_t* cur, const double* cost,
+                                                           const long long* viol, long long cycle, BestRec best) {
+    const int r = (int)(blockIdx.x / (unsigned)bpr);
+    const int b = (int)blockIdx.x - r * bpr;
+    if (!best.improved[r]) return;
+    const int i = b * (int)blockDim.x + (int)threadIdx.x;
+    if (i < n_vars) best.idx[(int64_t)r * n_vars + i] = cur[(int64_t)r * n_vars + i];
+    if (i == 0) {
+        best.cost[r] = cost[r];
+        best.viol[r] = viol[r];
+        best.cycle[r] = cycle;
+    }
+}
+
+constexpr int MAX_REPLICAS = 4096;
 
 struct Base {
     virtual ~Base() {}
     virtual int init(const mxs_graph& G, const mxs_params& p, int variant, double probability, int arity_mode,
-                     uint64_t seed, int device) = 0;
+                     const uint64_t* seeds, int n_replicas, int device) = 0;
     virtual int reset() = 0;
     virtual int set_value_rank(const int32_t* rank) = 0;
     virtual int run(int32_t n) = 0;
-    virtual int get_state(int32_t* idx, double* cost) = 0;
+    virtual int get_state(int32_t r, int32_t* idx, double* cost) = 0;
     virtual int eval_cost(const int32_t* idx, double infinity, double* cost, int64_t* viol) = 0;
+    virtual int replica_costs(double infinity, double* cost, int64_t* viol) = 0;
+    virtual int track_best(int32_t every, double infinity) = 0;
+    virtual int get_best(int32_t r, int32_t* replica, int64_t* cycle, double* cost, int64_t* viol, int32_t* idx) = 0;
     int64_t cycles = 0;
+    int32_t n_rep = 1;
 };
 
 template <typename T>
@@ -320,33 +489,68 @@ struct Engine : Base {
     hipStream_t stream = nullptr;
     Dev<T> g{};
     int which = 0;
-    uint64_t seed = 0;
+    std::vector<uint64_t> h_seeds;
     mxs_host::HostGraph hg;
     std::vector<int32_t> h_nn, h_q, h_vrank;
     Buf<int32_t> dom_size, factor_rowptr, edge_var, edge_factor, var_rowptr, var_edges, n_neigh, qmap;
-    Buf<int32_t> cur[2];
+    Buf<int32_t> cur[2];    // [R][n_vars]
     Buf<int64_t> table_off;
     Buf<T> tables, f_opt, cost;
     Buf<double> prob;
+    Buf<uint64_t> seeds;
     mxs_host::DevSlots sl;
     mxs_host::DevPack<T> pk;
     Buf<uint64_t> pk_key;   // what only DSA keeps per packed variable / lane (Dev::pack_key, pack_prob, pack_fopt)
     Buf<double> pk_prob;
     Buf<T> pk_fopt;
     int max_dom = 0;
+    // the start state of the variables without neighbours (k_dsa_init)
+    Buf<int32_t> iso_val;
+    Buf<T> iso_cost;
+    // the device cost (k_dsa_cost_partial / k_dsa_cost_final)
+    Buf<int64_t> coff;
+    Buf<double> evc, part_cost, rep_cost;
+    Buf<long long> part_viol, rep_viol;
+    int cost_blocks = 1;
+    // the best state (track_best): `tracked`: track_best was called, `every` > 0: records are kept
+    bool tracked = false;
+    int32_t every = 0;
+    double best_infinity = INFINITY;
+    Buf<double> best_cost;
+    Buf<long long> best_viol, best_cycle;
+    Buf<int32_t> best_improved, best_idx;
 
     ~Engine() override {
         if (stream) (void)hipStreamDestroy(stream);
     }
 
+    // an allocation that grows with the number of replicas: its failure is MXS_E_NOMEM (the caller's
+    // destructor frees what was allocated before)
+    template <typename U>
+    static int alloc_rep(Buf<U>& b, size_t count, const char* what) {
+        if (b.alloc(count) != hipSuccess) {
+            (void)hipGetLastError();
+            b.p = nullptr;
+            b.n = 0;
+            return fail(MXS_E_NOMEM, std::string("out of device memory for the replicas' ") + what);
+        }
+        return MXS_OK;
+    }
+
+    static int blocks_of(int64_t n, int per_block) { return (int)((n + per_block - 1) / per_block); }
+
     int init(const mxs_graph& G, const mxs_params& p, int variant, double probability, int arity_mode,
-             uint64_t sd, int dev) override {
+             const uint64_t* sds, int n_replicas, int dev) override {
         device = dev;
-        seed = sd;
+        if (n_replicas < 1 || n_replicas > MAX_REPLICAS) return fail(MXS_E_INVALID, "the number of replicas must be in 1 .. 4096");
+        if (!sds) return fail(MXS_E_INVALID, "null seeds");
+        n_rep = n_replicas;
+        h_seeds.assign(sds, sds + n_replicas);
         if (int rc = mxs_host::open_device(dev, &stream)) return rc;
         if (variant < 0 || variant > 2) return fail(MXS_E_INVALID, "variant must be 0 (A), 1 (B) or 2 (C)");
         if (int rc = hg.load(G, p)) return rc;  // (init_idx is not read: the reference's DSA ignores initial values)
         const int nV = hg.nV, nF = hg.nF;
+        const size_t R = (size_t)n_rep;
         const std::vector<int32_t> &efac = hg.efac, &vrow = hg.vrow, &vedges = hg.vedges;
         h_nn.assign(nV, 0);
         std::vector<int64_t> n_count(nV, 0);
@@ -381,21 +585,30 @@ struct Engine : Base {
             for (size_t i = 0; i < hp.slot.size(); ++i)
                 if (hp.slot[i] >= 0) fopt_lane[i] = fo[efac[vedges[hp.slot[i]]]];
             h_q = mxs_host::packed_order(hp, nV);
-            std::vector<uint64_t> pkey(hp.vars.size());
-            std::vector<double> pprob(hp.vars.size());
-            for (int v : hp.vars) {
-                pkey[h_q[v]] = uniform_key(seed, v);
-                pprob[h_q[v]] = pr[v];
-            }
+            const size_t nP = hp.vars.size();
+            // every launch folds the replica into blockIdx.x: the largest grid must fit
+            const int64_t most = std::max<int64_t>({blocks_of((int64_t)hp.nb.size(), PACK_TPB), blocks_of(nV, TPB), 1});
+            if (most * (int64_t)n_rep > INT32_MAX) return fail(MXS_E_INVALID, "too many replicas for an instance of this size");
+            std::vector<double> pprob(nP);
+            for (int v : hp.vars) pprob[h_q[v]] = pr[v];
             if (int rc = pk.upload(hp, h_q, hg.dom, stream)) return rc;
             MXS_TRY(qmap.upload(h_q, stream));
-            MXS_TRY(pk_key.upload(pkey, stream));
             MXS_TRY(pk_prob.upload(pprob, stream));
             MXS_TRY(pk_fopt.upload(fopt_lane, stream));
+            {   // the keys of the packed variables' draws, per replica
+                std::vector<uint64_t> pkey(R * nP);
+                for (size_t r = 0; r < R; ++r)
+                    for (int v : hp.vars) pkey[r * nP + h_q[v]] = uniform_key(h_seeds[r], v);
+                if (int rc = alloc_rep(pk_key, R * nP, "keys")) return rc;
+                if (!pkey.empty())
+                    MXS_TRY(hipMemcpyAsync(pk_key.p, pkey.data(), 8 * pkey.size(), hipMemcpyHostToDevice, stream));
+                MXS_TRY(hipStreamSynchronize(stream));
+            }
             if (int rc = sl.upload(hs, stream, &h_q, true)) return rc;
             sl.upload_rows(hs, hp.rest, hg, max_dom, (int)sizeof(T), stream);
             g.q = qmap.p;
             g.pack = pk.view();
+            g.n_pack = (int32_t)nP;
             g.pack_dom = pk.dom.p;
             g.pack_key = pk_key.p;
             g.pack_prob = pk_prob.p;
@@ -413,12 +626,23 @@ struct Engine : Base {
         MXS_TRY(tables.upload(tt, stream));
         MXS_TRY(f_opt.upload(fo, stream));
         MXS_TRY(prob.upload(pr, stream));
-        for (int b = 0; b < 2; ++b) MXS_TRY(cur[b].alloc(nV));
-        MXS_TRY(cost.alloc(nV));
+        MXS_TRY(seeds.upload(h_seeds, stream));
+        MXS_TRY(coff.upload(hg.coff, stream));
+        MXS_TRY(evc.upload(hg.eval_var_cost, stream));
+        MXS_TRY(iso_val.alloc(nV));
+        MXS_TRY(iso_cost.alloc(nV));
+        for (int b = 0; b < 2; ++b)
+            if (int rc = alloc_rep(cur[b], R * nV, "values")) return rc;
+        if (int rc = alloc_rep(cost, R * nV, "held costs")) return rc;
+        cost_blocks = std::max(1, blocks_of((int64_t)nF + nV, COST_TPB * COST_RUN));
+        if (int rc = alloc_rep(part_cost, R * cost_blocks, "cost partials")) return rc;
+        if (int rc = alloc_rep(part_viol, R * cost_blocks, "cost partials")) return rc;
+        if (int rc = alloc_rep(rep_cost, R, "costs")) return rc;
+        if (int rc = alloc_rep(rep_viol, R, "costs")) return rc;
         g.n_vars = nV;
         g.is_max = p.mode == MXS_MODE_MAX;
         g.variant = variant;
-        g.seed = seed;
+        g.seeds = seeds.p;
         g.dom_size = dom_size.p; g.factor_rowptr = factor_rowptr.p; g.edge_var = edge_var.p;
         g.edge_factor = edge_factor.p; g.var_rowptr = var_rowptr.p; g.var_edges = var_edges.p;
         g.n_neigh = n_neigh.p; g.table_off = table_off.p; g.tables = tables.p; g.f_opt = f_opt.p;
@@ -434,97 +658,233 @@ struct Engine : Base {
         return reset();
     }
 
+    // every replica back to its start state (k_dsa_init); the records of track_best start again
     int reset() override {
         MXS_TRY(hipSetDevice(device));
         const int nV = g.n_vars;
-        std::vector<int32_t> c0(nV);
+        std::vector<int32_t> v0(nV, -1);
         std::vector<T> k0(nV, (T)0);
-        for (int v = 0; v < nV; ++v) {
+        for (int v = 0; v < nV; ++v)
             if (h_nn[v] == 0) {  // optimal_cost_value (dsa.py:278-289)
-                const int best = hg.optimal_cost_value<T>(v, g.is_max, h_vrank);
-                c0[h_q[v]] = best;  // (the state lives in packed order, Dev::q)
-                k0[h_q[v]] = (T)hg.var_cost[hg.coff[v] + best];
-            } else {  // random_value_selection (dsa.py:291): draw 0 of cycle 0
-                c0[h_q[v]] = (int32_t)(uniform(seed, v, 0, 0) * hg.dom[v]);
+                v0[v] = hg.optimal_cost_value<T>(v, g.is_max, h_vrank);
+                k0[v] = (T)hg.var_cost[hg.coff[v] + v0[v]];
             }
-        }
         which = 0;
-        if (nV) {
-            MXS_TRY(hipMemcpyAsync(cur[0].p, c0.data(), 4 * nV, hipMemcpyHostToDevice, stream));
-            // (both buffers: the packed launch writes only the variables that have neighbours)
-            MXS_TRY(hipMemcpyAsync(cur[1].p, c0.data(), 4 * nV, hipMemcpyHostToDevice, stream));
-            MXS_TRY(hipMemcpyAsync(cost.p, k0.data(), sizeof(T) * nV, hipMemcpyHostToDevice, stream));
-            MXS_TRY(hipStreamSynchronize(stream));
-        }
         cycles = 0;
+        if (nV) {
+            MXS_TRY(hipMemcpyAsync(iso_val.p, v0.data(), 4 * (size_t)nV, hipMemcpyHostToDevice, stream));
+            MXS_TRY(hipMemcpyAsync(iso_cost.p, k0.data(), sizeof(T) * (size_t)nV, hipMemcpyHostToDevice, stream));
+            g.bpr = blocks_of(nV, AUX_TPB);
+            const dim3 grid((unsigned)(g.bpr * n_rep)), block(AUX_TPB);
+            hipLaunchKernelGGL((k_dsa_init<T>), grid, block, 0, stream, g, iso_val.p, iso_cost.p, cur[0].p, cur[1].p);
+            MXS_TRY(hipGetLastError());
+        }
+        const int rc = every > 0 ? record(2) : MXS_OK;
+        MXS_TRY(hipStreamSynchronize(stream));  // (v0 / k0 leave scope: also when record() failed)
+        return rc;
+    }
+
+    // the costs of the replicas' current assignments into rep_cost / rep_viol, on the stream; mode: k_dsa_cost_final
+    int launch_costs(double infinity, int mode) {
+        g.cur = cur[which].p;
+        g.bpr = cost_blocks;
+        const CostArgs a{coff.p, evc.p, hg.nF, infinity, part_cost.p, part_viol.p};
+        hipLaunchKernelGGL((k_dsa_cost_partial<T>), dim3((unsigned)(cost_blocks * n_rep)), dim3(COST_TPB), 0, stream, g, a);
+        MXS_TRY(hipGetLastError());
+        hipLaunchKernelGGL(k_dsa_cost_final, dim3((unsigned)blocks_of(n_rep, 64)), dim3(64), 0, stream, (int)n_rep, cost_blocks,
+                           (int)g.is_max, (const double*)part_cost.p, (const long long*)part_viol.p, rep_cost.p, rep_viol.p,
+                           mode, best_rec());
+        MXS_TRY(hipGetLastError());
+        return MXS_OK;
+    }
+
+    BestRec best_rec() const { return BestRec{best_cost.p, best_viol.p, best_cycle.p, best_improved.p, best_idx.p}; }
+
+    // the current states against the records (mode 1; 2: the first record), three launches in stream order
+    int record(int mode) {
+        if (int rc = launch_costs(best_infinity, mode)) return rc;
+        const int bpr = std::max(1, blocks_of(g.n_vars, AUX_TPB));
+        hipLaunchKernelGGL(k_dsa_best_copy, dim3((unsigned)(bpr * n_rep)), dim3(AUX_TPB), 0, stream, (int)g.n_vars, bpr,
+                           (const int32_t*)cur[which].p, (const double*)rep_cost.p, (const long long*)rep_viol.p,
+                           (long long)cycles, best_rec());
+        MXS_TRY(hipGetLastError());
+        return MXS_OK;
+    }
+
+    // the launches of one cycle of all replicas: packed plus rest, or thread per variable alone
+    template <bool REP>
+    int launch_cycle(bool packed, bool generic) {
+        if (packed) {
+            g.bpr = blocks_of(g.pack.n_lanes, PACK_TPB);
+            const dim3 pgrid((unsigned)(g.bpr * n_rep)), pblock(PACK_TPB);
+            if (pk.int8) hipLaunchKernelGGL((k_dsa_cycle_pack<T, int8_t, REP>), pgrid, pblock, 0, stream, g);
+            else hipLaunchKernelGGL((k_dsa_cycle_pack<T, T, REP>), pgrid, pblock, 0, stream, g);
+            MXS_TRY(hipGetLastError());
+            g.var_list = pk.rest.p;
+            g.n_list = pk.n_rest;
+        }
+        if (g.n_list > 0) {
+            g.bpr = blocks_of(g.n_list, TPB);
+            const dim3 grid((unsigned)(g.bpr * n_rep)), block(TPB);
+            if (generic || max_dom > 32) hipLaunchKernelGGL((k_dsa_cycle<T, REP>), grid, block, 0, stream, g);
+            else if (max_dom <= 4) hipLaunchKernelGGL((k_dsa_cycle_slots<T, 4, REP>), grid, block, 0, stream, g);
+            else if (max_dom <= 8) hipLaunchKernelGGL((k_dsa_cycle_slots<T, 8, REP>), grid, block, 0, stream, g);
+            else if (max_dom <= 16) hipLaunchKernelGGL((k_dsa_cycle_slots<T, 16, REP>), grid, block, 0, stream, g);
+            else hipLaunchKernelGGL((k_dsa_cycle_slots<T, 32, REP>), grid, block, 0, stream, g);
+            MXS_TRY(hipGetLastError());
+        }
         return MXS_OK;
     }
 
     int run(int32_t n) override {
         MXS_TRY(hipSetDevice(device));
         const int nV = g.n_vars;
-        if (nV == 0) {
-            cycles += n > 0 ? n : 0;
-            return MXS_OK;
-        }
         const char* env = std::getenv("MAXSUM_LOCAL_SEARCH_GENERIC");  // =1: the CSR-walk kernel, =2: the slot
         const bool generic = env && env[0] == '1';                     // kernel for every variable (A/B, tests)
         const bool packed = !generic && !(env && env[0] == '2') && g.pack.n_lanes > 0;
-        for (int32_t r = 0; r < n; ++r) {
+        for (int32_t c = 0; c < n; ++c) {
             g.cur = cur[which].p;
             g.cur_out = cur[which ^ 1].p;
             g.cycle = cycles;
             g.var_list = nullptr;
             g.n_list = nV;
-            if (packed) {
-                const dim3 pgrid((unsigned)((g.pack.n_lanes + PACK_TPB - 1) / PACK_TPB)), pblock(PACK_TPB);
-                if (pk.int8) hipLaunchKernelGGL((k_dsa_cycle_pack<T, int8_t>), pgrid, pblock, 0, stream, g);
-                else hipLaunchKernelGGL((k_dsa_cycle_pack<T, T>), pgrid, pblock, 0, stream, g);
-                MXS_TRY(hipGetLastError());
-                g.var_list = pk.rest.p;
-                g.n_list = pk.n_rest;
-            }
-            if (g.n_list > 0) {
-                const dim3 grid((unsigned)((g.n_list + TPB - 1) / TPB)), block(TPB);
-                if (generic || max_dom > 32) hipLaunchKernelGGL((k_dsa_cycle<T>), grid, block, 0, stream, g);
-                else if (max_dom <= 4) hipLaunchKernelGGL((k_dsa_cycle_slots<T, 4>), grid, block, 0, stream, g);
-                else if (max_dom <= 8) hipLaunchKernelGGL((k_dsa_cycle_slots<T, 8>), grid, block, 0, stream, g);
-                else if (max_dom <= 16) hipLaunchKernelGGL((k_dsa_cycle_slots<T, 16>), grid, block, 0, stream, g);
-                else hipLaunchKernelGGL((k_dsa_cycle_slots<T, 32>), grid, block, 0, stream, g);
-                MXS_TRY(hipGetLastError());
-            }
+            if (int rc = n_rep == 1 ? launch_cycle<false>(packed, generic) : launch_cycle<true>(packed, generic)) return rc;
             which ^= 1;
             cycles += 1;
+            if (every > 0 && cycles % every == 0)
+                if (int rc = record(1)) return rc;
         }
         MXS_TRY(hipStreamSynchronize(stream));
         return MXS_OK;
     }
 
-    int get_state(int32_t* idx, double* cst) override {
+    // packed order (Dev::q) -> graph order
+    void unpack(const std::vector<int32_t>& hi, int32_t* idx) const {
+        for (int v = 0; v < g.n_vars; ++v) idx[v] = hi[h_q[v]];
+    }
+
+    int get_state(int32_t r, int32_t* idx, double* cst) override {
+        if (r < 0 || r >= n_rep) return fail(MXS_E_INVALID, "replica out of range");
         MXS_TRY(hipSetDevice(device));
         const int nV = g.n_vars;
         if (!nV) return MXS_OK;
         std::vector<T> hc(nV);
         std::vector<int32_t> hi(nV);
-        MXS_TRY(hipMemcpyAsync(hi.data(), cur[which].p, 4 * nV, hipMemcpyDeviceToHost, stream));
-        MXS_TRY(hipMemcpyAsync(hc.data(), cost.p, sizeof(T) * nV, hipMemcpyDeviceToHost, stream));
+        const size_t roff = (size_t)r * nV;
+        MXS_TRY(hipMemcpyAsync(hi.data(), cur[which].p + roff, 4 * (size_t)nV, hipMemcpyDeviceToHost, stream));
+        MXS_TRY(hipMemcpyAsync(hc.data(), cost.p + roff, sizeof(T) * (size_t)nV, hipMemcpyDeviceToHost, stream));
         MXS_TRY(hipStreamSynchronize(stream));
-        for (int v = 0; v < nV; ++v) {  // the state lives in packed order (Dev::q)
-            if (idx) idx[v] = hi[h_q[v]];
+        if (idx) unpack(hi, idx);
+        for (int v = 0; v < nV; ++v)
             if (cst) cst[v] = (double)hc[h_q[v]];
-        }
         return MXS_OK;
     }
 
     int eval_cost(const int32_t* idx, double infinity, double* cst, int64_t* viol) override {
         std::vector<int32_t> c;
-        if (!idx) {
+        if (!idx) {  // replica 0
             c.resize(g.n_vars);
-            int rc = get_state(c.data(), nullptr);
+            int rc = get_state(0, c.data(), nullptr);
             if (rc) return rc;
             idx = c.data();
         }
         return hg.eval_cost(idx, infinity, cst, viol);
+    }
+
+    int fetch_costs(std::vector<double>& hc, std::vector<long long>& hv, const double* dc, const long long* dv) {
+        hc.resize(n_rep), hv.resize(n_rep);
+        MXS_TRY(hipMemcpyAsync(hc.data(), dc, 8 * (size_t)n_rep, hipMemcpyDeviceToHost, stream));
+        MXS_TRY(hipMemcpyAsync(hv.data(), dv, 8 * (size_t)n_rep, hipMemcpyDeviceToHost, stream));
+        MXS_TRY(hipStreamSynchronize(stream));
+        return MXS_OK;
+    }
+
+    int replica_costs(double infinity, double* cst, int64_t* viol) override {
+        MXS_TRY(hipSetDevice(device));
+        if (int rc = launch_costs(infinity, 0)) return rc;
+        std::vector<double> hc;
+        std::vector<long long> hv;
+        if (int rc = fetch_costs(hc, hv, rep_cost.p, rep_viol.p)) return rc;
+        for (int r = 0; r < n_rep; ++r) {
+            if (cst) cst[r] = hc[r];
+            if (viol) viol[r] = (int64_t)hv[r];
+        }
+        return MXS_OK;
+    }
+
+    void drop_records() {
+        best_cost.release(), best_viol.release(), best_cycle.release(), best_improved.release(), best_idx.release();
+        every = 0;
+    }
+
+    int track_best(int32_t ev, double infinity) override {
+        if (ev < 0) return fail(MXS_E_INVALID, "every must be 0 (off) or positive");
+        MXS_TRY(hipSetDevice(device));
+        drop_records();
+        if (ev == 0) {
+            tracked = true;
+            best_infinity = infinity;
+            return MXS_OK;
+        }
+        const size_t R = (size_t)n_rep;
+        int rc = alloc_rep(best_cost, R, "records");
+        if (!rc) rc = alloc_rep(best_viol, R, "records");
+        if (!rc) rc = alloc_rep(best_cycle, R, "records");
+        if (!rc) rc = alloc_rep(best_improved, R, "records");
+        if (!rc) rc = alloc_rep(best_idx, R * g.n_vars, "best states");
+        if (rc) {  // no records, and get_best keeps what the last successful call set (tracked, best_infinity)
+            drop_records();
+            return rc;
+        }
+        tracked = true;
+        best_infinity = infinity;
+        every = ev;
+        if (int rc2 = record(2)) return rc2;  // the state as it is now: cycle 0 of a fresh engine
+        MXS_TRY(hipStreamSynchronize(stream));
+        return MXS_OK;
+    }
+
+    // (violations, cost -- negated in max mode --, index): the lexicographic minimum
+    int best_replica(const std::vector<double>& hc, const std::vector<long long>& hv) const {
+        int best = 0;
+        for (int r = 1; r < n_rep; ++r) {
+            const double a = g.is_max ? -hc[r] : hc[r], b = g.is_max ? -hc[best] : hc[best];
+            if (hv[r] < hv[best] || (hv[r] == hv[best] && a < b)) best = r;
+        }
+        return best;
+    }
+
+    int get_best(int32_t r, int32_t* replica, int64_t* cycle, double* cst, int64_t* viol, int32_t* idx) override {
+        if (r < -1 || r >= n_rep) return fail(MXS_E_INVALID, "replica out of range");
+        if (!tracked) return fail(MXS_E_STATE, "mxs_dsa_get_best before mxs_dsa_track_best");
+        MXS_TRY(hipSetDevice(device));
+        std::vector<double> hc;
+        std::vector<long long> hv, hy(n_rep, (long long)cycles);
+        if (every > 0) {  // the records
+            if (int rc = fetch_costs(hc, hv, best_cost.p, best_viol.p)) return rc;
+            MXS_TRY(hipMemcpyAsync(hy.data(), best_cycle.p, 8 * (size_t)n_rep, hipMemcpyDeviceToHost, stream));
+            MXS_TRY(hipStreamSynchronize(stream));
+        } else {          // the current states
+            if (int rc = launch_costs(best_infinity, 0)) return rc;
+            if (int rc = fetch_costs(hc, hv, rep_cost.p, rep_viol.p)) return rc;
+        }
+        if (r < 0) r = best_replica(hc, hv);
+        if (replica) *replica = r;
+        if (cycle) *cycle = (int64_t)hy[r];
+        if (cst) *cst = hc[r];
+        if (viol) *viol = (int64_t)hv[r];
+        if (idx && g.n_vars) {
+            if (every > 0) {
+                std::vector<int32_t> hi(g.n_vars);
+                MXS_TRY(hipMemcpyAsync(hi.data(), best_idx.p + (size_t)r * g.n_vars, 4 * (size_t)g.n_vars,
+                                       hipMemcpyDeviceToHost, stream));
+                MXS_TRY(hipStreamSynchronize(stream));
+                unpack(hi, idx);
+            } else if (int rc = get_state(r, idx, nullptr)) {
+                return rc;
+            }
+        }
+        return MXS_OK;
     }
 };
 
@@ -538,7 +898,16 @@ extern "C" {
 
 int mxs_dsa_create(const mxs_graph* g, const mxs_params* p, int32_t variant, double probability, int32_t arity_mode,
                    uint64_t seed, int32_t device, mxs_dsa** out) {
-    return mxs_host::create<mxs_dsa, dsa::Engine>(g, p, out, variant, probability, arity_mode, seed, device);
+    return mxs_dsa_create_replicas(g, p, variant, probability, arity_mode, &seed, 1, device, out);
+}
+int mxs_dsa_create_replicas(const mxs_graph* g, const mxs_params* p, int32_t variant, double probability,
+                            int32_t arity_mode, const uint64_t* seeds, int32_t n_replicas, int32_t device, mxs_dsa** out) {
+    return mxs_host::create<mxs_dsa, dsa::Engine>(g, p, out, variant, probability, arity_mode, seeds, n_replicas, device);
+}
+int mxs_dsa_replicas(const mxs_dsa* e, int32_t* n) {
+    if (!e) return mxs_host::fail(MXS_E_INVALID, "null handle");
+    if (n) *n = e->impl->n_rep;
+    return MXS_OK;
 }
 int mxs_dsa_reset(mxs_dsa* e) { return e ? e->impl->reset() : mxs_host::fail(MXS_E_INVALID, "null handle"); }
 int mxs_dsa_set_value_rank(mxs_dsa* e, const int32_t* value_rank) {
@@ -555,10 +924,23 @@ int mxs_dsa_cycles(const mxs_dsa* e, int64_t* cycles) {
     return MXS_OK;
 }
 int mxs_dsa_get_state(mxs_dsa* e, int32_t* idx, double* cost) {
-    return e ? e->impl->get_state(idx, cost) : mxs_host::fail(MXS_E_INVALID, "null handle");
+    return e ? e->impl->get_state(0, idx, cost) : mxs_host::fail(MXS_E_INVALID, "null handle");
+}
+int mxs_dsa_get_state_replica(mxs_dsa* e, int32_t r, int32_t* idx, double* cost) {
+    return e ? e->impl->get_state(r, idx, cost) : mxs_host::fail(MXS_E_INVALID, "null handle");
 }
 int mxs_dsa_eval_cost(mxs_dsa* e, const int32_t* idx, double infinity, double* cost, int64_t* violations) {
     return e ? e->impl->eval_cost(idx, infinity, cost, violations) : mxs_host::fail(MXS_E_INVALID, "null handle");
+}
+int mxs_dsa_replica_costs(mxs_dsa* e, double infinity, double* cost, int64_t* violations) {
+    return e ? e->impl->replica_costs(infinity, cost, violations) : mxs_host::fail(MXS_E_INVALID, "null handle");
+}
+int mxs_dsa_track_best(mxs_dsa* e, int32_t every, double infinity) {
+    return e ? e->impl->track_best(every, infinity) : mxs_host::fail(MXS_E_INVALID, "null handle");
+}
+int mxs_dsa_get_best(mxs_dsa* e, int32_t r, int32_t* replica, int64_t* cycle, double* cost, int64_t* violations,
+                     int32_t* idx) {
+    return e ? e->impl->get_best(r, replica, cycle, cost, violations, idx) : mxs_host::fail(MXS_E_INVALID, "null handle");
 }
 int mxs_dsa_destroy(mxs_dsa* e) {
     if (e) {

@@ -2236,12 +2236,13 @@ int mxs_destroy(mxs_engine* e) {
 
 const char* mxs_last_error(void) { return g_err.c_str(); }
 
-int32_t mxs_version(void) { return 260; }  // 2.1: + mxs_run_reps, mxs_factor_kernels, mxs_variable_kernels (round 5)
+int32_t mxs_version(void) { return 270; }  // 2.1: + mxs_run_reps, mxs_factor_kernels, mxs_variable_kernels (round 5)
                                            // 2.2: mxs_variable_kernels reports six classes (+ the hub class, round 6)
                                            // 2.3: + mxs_mgm2_*
                                            // 2.4: + mxs_dpop_*
                                            // 2.5: + mxs_gdba_*
                                            // 2.6: + mxs_dba_*
+                                           // 2.7: + mxs_dsa_create_replicas, _replicas, _get_state_replica, _replica_costs, _track_best, _get_best
 #ifndef MXS_BUILD_KIND   // 1: the hipcc build for gfx950; 0: anything else (the host emulation of tests/emu), refused by the
 #if defined(__HIPCC__)   // binding outside tests (pydcop_amd/engine.py, load_library).  Derived from the compiler: a build that
 #define MXS_BUILD_KIND 1 // forgets the flag cannot claim to be the device build.

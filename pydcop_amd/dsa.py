@@ -4,7 +4,7 @@ FlatGraph as the Max-Sum engine.  Every stochastic choice comes from a counter-b
 on (seed, variable, cycle, draw): a run is reproducible and independent of scheduling.  No CPU
 fallback."""
 import ctypes as C
-from typing import Optional, Tuple
+from typing import Dict, Optional, Sequence, Tuple
 
 import numpy as np
 
@@ -19,13 +19,20 @@ class DsaEngine(EngineBinding):
     """>>> eng = DsaEngine(graph, Params(mode="min"), variant="B", probability=0.7, seed=1)
     >>> eng.run(30)                                    # 30 cycles (= the reference's stop_cycle 30)
     >>> idx, cost = eng.assignment()
+
+    `replicas=R`: R seeded runs of the instance in one engine (seeds `seed + r` modulo 2**64, or `seeds`),
+    advanced by the same launches over one copy of the tables; replica r is bit for bit the engine with that seed.
+    >>> eng = DsaEngine(graph, replicas=8, seed=5)
+    >>> eng.track_best(every=1, infinity=10000)        # keep every replica's best state on the device
+    >>> eng.run(30)
+    >>> eng.best()                                     # the best replica's record
     """
     PREFIX = "mxs_dsa"
     COUNTER = "cycles"
 
     def __init__(self, graph: FlatGraph, params: Optional[Params] = None, variant: str = "B",
                  probability: float = 0.7, p_mode: str = "fixed", seed: int = 0, device: int = 0,
-                 lib_path: Optional[str] = None):
+                 lib_path: Optional[str] = None, replicas: int = 1, seeds: Optional[Sequence[int]] = None):
         if variant not in VARIANTS:
             raise ValueError(f"Invalid value {variant!r} for parameter variant, must be one of ['A', 'B', 'C']")
         if p_mode not in ("fixed", "arity"):
@@ -34,10 +41,17 @@ class DsaEngine(EngineBinding):
         self.graph = graph
         self.params = params or Params()
         cg, cp = graph.to_c(), self.params.to_c()
+        if seeds is None:
+            seeds = [int(seed) + r for r in range(int(replicas))]
+        elif replicas not in (1, len(seeds)):
+            raise ValueError(f"{len(seeds)} seeds for {replicas} replicas")
+        self.seeds = [int(x) & (2 ** 64 - 1) for x in seeds]
+        self.replicas = len(self.seeds)
+        sd = np.array(self.seeds, dtype=np.uint64)
         h = C.c_void_p()
-        self._check(self._lib.mxs_dsa_create(C.byref(cg), C.byref(cp), VARIANTS[variant], float(probability),
-                                             1 if p_mode == "arity" else 0, int(seed) & (2 ** 64 - 1),
-                                             int(device), C.byref(h)))
+        self._check(self._lib.mxs_dsa_create_replicas(C.byref(cg), C.byref(cp), VARIANTS[variant], float(probability),
+                                                      1 if p_mode == "arity" else 0, sd.ctypes.data, self.replicas,
+                                                      int(device), C.byref(h)))
         self._h = h
         # cost ties of a variable without neighbours break on the domain VALUE (relations.py:1661-1665):
         # only needed when some domain is not written in ascending order
@@ -51,8 +65,30 @@ class DsaEngine(EngineBinding):
     def run(self, n_cycles: int):
         self._call("run", int(n_cycles))
 
-    def assignment(self) -> Tuple[np.ndarray, np.ndarray]:
+    def assignment(self, replica: int = 0) -> Tuple[np.ndarray, np.ndarray]:
         idx = np.empty(self.graph.n_vars, dtype=np.int32)
         cost = np.empty(self.graph.n_vars)
-        self._call("get_state", idx.ctypes.data, cost.ctypes.data)
+        self._call("get_state_replica", int(replica), idx.ctypes.data, cost.ctypes.data)
         return idx, cost
+
+    def replica_costs(self, infinity: float = float("inf")) -> Tuple[np.ndarray, np.ndarray]:
+        """(cost[R], violations[R]) of the replicas' current assignments, reduced on the device: what
+        `eval_cost(assignment(r)[0], infinity)` gives, in a fixed summation order of its own."""
+        cost = np.empty(self.replicas)
+        viol = np.empty(self.replicas, dtype=np.int64)
+        self._call("replica_costs", float(infinity), cost.ctypes.data, viol.ctypes.data)
+        return cost, viol
+
+    def track_best(self, every: int = 1, infinity: float = float("inf")):
+        """Keep, per replica, the best state seen at cycle 0 and after every `every`-th cycle (0: off; the
+        `infinity` then only serves `best()`).  Clears the records."""
+        self._call("track_best", int(every), float(infinity))
+
+    def best(self, replica: int = -1) -> Dict:
+        """The record of `replica` (-1: of the best replica: fewest violations, then best cost, then lowest
+        index) when tracking is on, else its current state: {"replica", "cycle", "cost", "violations", "idx"}."""
+        r, cyc, cost, viol = C.c_int32(0), C.c_int64(0), C.c_double(0), C.c_int64(0)
+        idx = np.empty(self.graph.n_vars, dtype=np.int32)
+        self._call("get_best", int(replica), C.byref(r), C.byref(cyc), C.byref(cost), C.byref(viol), idx.ctypes.data)
+        return {"replica": int(r.value), "cycle": int(cyc.value), "cost": float(cost.value),
+                "violations": int(viol.value), "idx": idx}

@@ -51,6 +51,8 @@ ABI_SYMBOLS = (
     "mxs_mgm_eval_cost", "mxs_mgm_destroy",
     "mxs_dsa_create", "mxs_dsa_reset", "mxs_dsa_set_value_rank", "mxs_dsa_run", "mxs_dsa_cycles", "mxs_dsa_get_state",
     "mxs_dsa_eval_cost", "mxs_dsa_destroy",
+    "mxs_dsa_create_replicas", "mxs_dsa_replicas", "mxs_dsa_get_state_replica", "mxs_dsa_replica_costs",
+    "mxs_dsa_track_best", "mxs_dsa_get_best",
     "mxs_dpop_create", "mxs_dpop_solve", "mxs_dpop_get_state", "mxs_dpop_eval_cost", "mxs_dpop_stats",
     "mxs_dpop_util_dims", "mxs_dpop_get_util", "mxs_dpop_destroy",
     "mxs_gdba_create", "mxs_gdba_reset", "mxs_gdba_run", "mxs_gdba_rounds", "mxs_gdba_get_state",
@@ -196,6 +198,13 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
         "mxs_dsa_get_state": ([vp, vp, vp], C.c_int),
         "mxs_dsa_eval_cost": ([vp, vp, C.c_double, C.POINTER(C.c_double), C.POINTER(i64)], C.c_int),
         "mxs_dsa_destroy": ([vp], C.c_int),
+        "mxs_dsa_create_replicas": ([C.POINTER(CGraph), C.POINTER(CParams), i32, C.c_double, i32, vp, i32, i32,
+                                     C.POINTER(vp)], C.c_int),
+        "mxs_dsa_replicas": ([vp, C.POINTER(i32)], C.c_int),
+        "mxs_dsa_get_state_replica": ([vp, i32, vp, vp], C.c_int),
+        "mxs_dsa_replica_costs": ([vp, C.c_double, vp, vp], C.c_int),
+        "mxs_dsa_track_best": ([vp, i32, C.c_double], C.c_int),
+        "mxs_dsa_get_best": ([vp, i32, C.POINTER(i32), C.POINTER(i64), C.POINTER(C.c_double), C.POINTER(i64), vp], C.c_int),
         "mxs_dpop_create": ([C.POINTER(CGraph), C.POINTER(CParams), vp, vp, vp, i64, i32, i32, C.POINTER(vp)], C.c_int),
         "mxs_dpop_solve": ([vp], C.c_int),
         "mxs_dpop_get_state": ([vp, vp, vp], C.c_int),

@@ -16,6 +16,15 @@ peak; every timing ends with the engine's stream synchronised (run() returns aft
 `--dba-rounds N` (default 0) prints three rows instead, timed the same way in one process on the hard 100k-variable
 3-colouring: DBA ("kernels": "dba", pydcop_amd/csrc/dba.h; `infinity: 1000`, `max_distance` above the round count so
 that nothing stops), GDBA (A, NZ, T, f64) and MGM (f64), with DBA's ratio to each.
+`--replicas R [R ...]` prints the rows of the DSA replica engine instead (DsaEngine(replicas=R), dsa.hip): on
+`random_coloring` at `--replica-sizes` variables (f64, variant B), the time of a cycle of ALL replicas against R times
+the time of a cycle of a single-seed engine (what R restarts cost one engine after the other), the two sides
+alternated in one process, windows of `--window` seconds after a warm-up of `--warmup` seconds per engine,
+`--repeats` pairs (the rows give every repeat: the spread); then the same engine with `best_every` 1 and 10, and the
+device cost reduction (`replica_costs`) against R host `eval_cost` calls with their copies back.  The single-seed side
+is this library's engine ("baseline": "this") or, with `--baseline-lib PATH`, the `mxs_dsa_create` of another build
+of the library -- e.g. the parent commit's, built from `git archive <commit> pydcop_amd/csrc include` with the
+csrc Makefile -- loaded beside this one ("baseline": its mxs_version).
 """
 import argparse
 import json
@@ -67,6 +76,93 @@ def dba_rows(a):
         print(json.dumps(row), flush=True)
 
 
+class BaselineDsa:
+    """The single-seed DSA engine of ANOTHER build of the library (--baseline-lib), through the entry points every
+    version has: mxs_dsa_create / _run / _destroy.  Loaded with plain ctypes beside the library under test."""
+
+    def __init__(self, path, g, p, seed):
+        import ctypes as C
+        from pydcop_amd.engine import load_library
+        load_library()                       # (the HIP runtime first: the libraries are linked without it)
+        self._lib = C.CDLL(os.path.abspath(path))
+        self._lib.mxs_version.restype = C.c_int32
+        self.version = int(self._lib.mxs_version())
+        self._lib.mxs_dsa_create.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_double, C.c_int32, C.c_uint64,
+                                             C.c_int32, C.c_void_p]
+        self._lib.mxs_dsa_run.argtypes = [C.c_void_p, C.c_int32]
+        self._lib.mxs_dsa_destroy.argtypes = [C.c_void_p]
+        self._g, self._p = g.to_c(), p.to_c()      # (kept alive)
+        self._h = C.c_void_p()
+        rc = self._lib.mxs_dsa_create(C.byref(self._g), C.byref(self._p), 1, 0.7, 0, seed, 0, C.byref(self._h))
+        if rc:
+            raise RuntimeError(f"mxs_dsa_create of {path}: {rc}")
+
+    def run(self, n):
+        if self._lib.mxs_dsa_run(self._h, int(n)):
+            raise RuntimeError("mxs_dsa_run of the baseline library failed")
+
+    def close(self):
+        self._lib.mxs_dsa_destroy(self._h)
+
+
+def timed_us(eng, cycles):
+    t0 = time.perf_counter()
+    eng.run(cycles)
+    return 1e6 * (time.perf_counter() - t0) / cycles
+
+
+def cycles_for(eng, window_s, warmup_s=0.0):
+    """the number of cycles that fill the window, after a warm-up of `warmup_s` seconds"""
+    eng.run(20)
+    us = timed_us(eng, 50)
+    if warmup_s > 0:
+        us = timed_us(eng, max(50, int(warmup_s * 1e6 / max(us, 1e-3))))
+    return max(50, int(window_s * 1e6 / max(us, 1e-3)))
+
+
+def replica_rows(a):
+    for n_vars in a.replica_sizes:
+        g = G.random_coloring(n_vars, seed=0, names=False)
+        p = Params()
+        for R in a.replicas:
+            # both engines are created and warmed up anew for every row: neither side carries the history of the
+            # rows before it into the ratio
+            if a.baseline_lib:
+                single = BaselineDsa(a.baseline_lib, g, p, 1)
+                baseline = f"mxs_version {single.version}"
+            else:
+                single, baseline = DsaEngine(g, p, variant="B", seed=1, lib_path=a.lib), "this"
+            n_single = cycles_for(single, a.window, a.warmup)
+            eng = DsaEngine(g, p, variant="B", seed=1, replicas=R, lib_path=a.lib)
+            n_rep = cycles_for(eng, a.window, a.warmup)
+            one, many = [], []
+            for _ in range(a.repeats):      # alternated: both sides see the same machine
+                one.append(timed_us(single, n_single))
+                many.append(timed_us(eng, n_rep))
+            row = {"algo": "dsa_B", "instance": f"coloring_{n_vars}", "dtype": "f64", "n_vars": n_vars, "replicas": R,
+                   "baseline": baseline, "single_us_per_cycle": [round(x, 2) for x in one], "replicas_us_per_cycle": [round(x, 2) for x in many],
+                   "ratio_R_singles_to_replicas": round(R * sorted(one)[len(one) // 2] / sorted(many)[len(many) // 2], 2)}
+            for every in (1, 10):
+                eng.track_best(every, float("inf"))
+                eng.run(20)
+                row[f"best_every_{every}_us_per_cycle"] = [round(timed_us(eng, n_rep), 2) for _ in range(a.repeats)]
+            eng.track_best(0, float("inf"))
+            reps = max(3, int(0.2 * a.window * 1e6 / max(many[0], 1.0)))
+            t0 = time.perf_counter()
+            for _ in range(reps):
+                dev = eng.replica_costs()
+            row["replica_costs_us"] = round(1e6 * (time.perf_counter() - t0) / reps, 1)
+            reps = max(1, min(reps, 2000 // R))
+            t0 = time.perf_counter()
+            for _ in range(reps):
+                host = [eng.eval_cost(eng.assignment(r)[0]) for r in range(R)]
+            row["host_eval_cost_us"] = round(1e6 * (time.perf_counter() - t0) / reps, 1)
+            assert all(abs(dev[0][r] - host[r][0]) <= 1e-9 * max(1.0, abs(host[r][0])) for r in range(R))
+            print(json.dumps(row), flush=True)
+            eng.close()
+            single.close()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--cycles", type=int, default=500)
@@ -76,7 +172,16 @@ def main():
     ap.add_argument("--mgm2-rounds", type=int, default=200, help="0: no MGM-2 rows")
     ap.add_argument("--gdba-rounds", type=int, default=200, help="0: no GDBA rows")
     ap.add_argument("--dba-rounds", type=int, default=0, help="> 0: only the DBA / GDBA-T / MGM rows on the hard colouring")
+    ap.add_argument("--replicas", type=int, nargs="*", default=[], help="the DSA replica rows only: R values")
+    ap.add_argument("--replica-sizes", type=int, nargs="*", default=[1000, 10_000, 100_000])
+    ap.add_argument("--window", type=float, default=1.0, help="seconds per timed window of the replica rows")
+    ap.add_argument("--repeats", type=int, default=3)
+    ap.add_argument("--warmup", type=float, default=0.5, help="seconds of warm-up per engine of the replica rows")
+    ap.add_argument("--baseline-lib", default=None,
+                    help="replica rows: the single-seed side from this other build of the library (mxs_dsa_create)")
     a = ap.parse_args()
+    if a.replicas:
+        return replica_rows(a)
     if a.dba_rounds > 0:
         return dba_rows(a)
     instances = [("coloring_100k", lambda: G.random_coloring(100_000, seed=0, names=False), Params()),
