@@ -481,6 +481,33 @@ int mxs_mgm_rounds(const mxs_mgm *e, int64_t *rounds);
 int mxs_mgm_get_state(mxs_mgm *e, int32_t *idx, double *cost, uint8_t *has_cost, double *gain, int32_t *new_value);
 int mxs_mgm_eval_cost(mxs_mgm *e, const int32_t *idx, double infinity, double *cost, int64_t *violations);
 int mxs_mgm_destroy(mxs_mgm *e);
+/* KEYED DRAWS AND REPLICAS: the two draws mxs_mgm_create fixes come from the counter-based generator DSA uses,
+ * u = uniform(seeds[r], variable, cycle, draw), the variable being its index in this graph:
+ *   draw 10  the start value of a variable with neighbours and init_idx < 0: int(u * D), cycle 0 (mgm.py:301);
+ *            a variable with an initial value, or without neighbours, starts as under mxs_mgm_create, the same in
+ *            every replica;
+ *   draw 11  one of the best values when the gain strictly improves (mgm.py:376-379): B[int(u * |B|)], B = the
+ *            values, in domain order, whose summed constraints EQUAL the optimum exactly (find_arg_optimal); the
+ *            cycle is the computation's cycle_count while it handles the round's values: round k (from 1) is k.
+ * Bit for bit the reference's own MgmComputation objects under that generator (tests/mgm_keyed_oracle.py, pinned by
+ * tests/test_mgm_keyed_oracle_vs_reference.py).  n_replicas seeded runs share ONE engine, 1 <= n_replicas <= 4096
+ * (else MXS_E_INVALID; a grid of more than 2^31 - 1 blocks: MXS_E_INVALID; device memory that does not suffice:
+ * MXS_E_NOMEM): the static data is stored once, the dynamic state is [replica][variable] -- n_vars * (25 + 4 *
+ * sizeof(T)) bytes per replica --, a round of all replicas is the launches one run needs.  Replica r is bit for bit
+ * the one-replica engine with seeds[r].  mxs_mgm_reset / _run / _set_value_rank act on all replicas;
+ * mxs_mgm_get_state and mxs_mgm_eval_cost(idx = NULL) mean replica 0.  An engine of mxs_mgm_create has one replica. */
+int mxs_mgm_create_keyed(const mxs_graph *g, const mxs_params *p, const int32_t *name_rank, const uint64_t *seeds,
+                         int32_t n_replicas, int32_t device, mxs_mgm **out);
+int mxs_mgm_replicas(const mxs_mgm *e, int32_t *n);
+int mxs_mgm_get_state_replica(mxs_mgm *e, int32_t r, int32_t *idx, double *cost, uint8_t *has_cost, double *gain,
+                              int32_t *new_value);
+/* DCOP.solution_cost of every replica's current assignment, reduced on the device: as mxs_dsa_replica_costs (the
+ * same kernels) */
+int mxs_mgm_replica_costs(mxs_mgm *e, double infinity, double *cost, int64_t *violations);
+/* The best replica: the lexicographic minimum of (violations, cost, index) over the CURRENT states, the cost negated
+ * with MXS_MODE_MAX -- the rule of mxs_dsa_get_best with every = 0.  MGM's own sum never rises, so a run's final
+ * state is its best: there is nothing to track.  Any out pointer may be NULL. */
+int mxs_mgm_best_replica(mxs_mgm *e, double infinity, int32_t *replica, double *cost, int64_t *violations);
 
 /* ---- DSA (pydcop/algorithms/dsa.py, variants A / B / C) on the same flat arrays --------------
  * One cycle = every variable's `evaluate_cycle` once all its neighbours' values are in
@@ -669,7 +696,9 @@ int mxs_dba_mask_bytes(const mxs_dba *e, int64_t *bytes);
 int mxs_dba_eval_cost(mxs_dba *e, const int32_t *idx, double infinity, double *cost, int64_t *violations);
 int mxs_dba_destroy(mxs_dba *e);
 
-/* Library/ABI version (major*100+minor). */
+/* Library/ABI version (major*100+minor).  270 also covers the MGM additions made after it was set -- mxs_mgm_create_keyed,
+ * mxs_mgm_replicas, mxs_mgm_get_state_replica, mxs_mgm_replica_costs, mxs_mgm_best_replica: a binding that needs them
+ * looks the symbols up instead of comparing versions (pydcop_amd/mgm.py does, and says so when they are missing). */
 int32_t mxs_version(void);
 
 /* What this binary is: 1 = the product, compiled by hipcc for gfx950; 0 = the host

@@ -9,6 +9,16 @@ from the unseeded `random` module are fixed: first domain value at start (unless
 an initial value), first of equally good values; ties between equal gains by name (the
 reference's `break_mode: random` never triggers -- mgm.py:543 compares the string with the module
 -- so both modes are lexic, here as there).
+
+Extra parameters: `draws: keyed` (default `fixed`) takes the two draws from a counter-based generator keyed on (`seed`,
+variable, cycle, draw) instead -- draw 10 the start value of a variable without initial value, draw 11 one of the
+equally good values when the gain improves --: a run is reproducible, and bit for bit the reference's own
+MgmComputation under the same generator.  The variable index in the keys is the module's compile order: the variables
+sorted by name.  `restarts: R` (default 1; needs `draws: keyed`) runs R seeded replicas (seeds seed .. seed + R - 1) in
+the one engine and publishes the best replica's values -- fewest entries equal to infinity, then the best solution
+cost, evaluated on the device.  MGM's own sum never rises, so a replica's final state is its best: there is no
+`best_every`.  The ranking takes no `infinity` (the module has no such parameter: every table entry, however large, is
+a cost).  With the defaults the module is the single fixed-draw run above.
 """
 from types import SimpleNamespace
 
@@ -27,6 +37,9 @@ algo_params = [
     AlgoParameterDef("stop_cycle", "int", None, 0),
     AlgoParameterDef("precision", "str", ["f64", "f32"], "f64"),
     AlgoParameterDef("chunk", "int", None, 10),
+    AlgoParameterDef("draws", "str", ["fixed", "keyed"], "fixed"),
+    AlgoParameterDef("seed", "int", None, 0),
+    AlgoParameterDef("restarts", "int", None, 1),
 ]
 
 
@@ -44,16 +57,25 @@ def communication_load(src, target: str) -> float:
 class _RoundEngine:
     """MgmEngine behind the surface the session drives."""
 
-    def __init__(self, graph, params):
+    def __init__(self, graph, params, p=None):
         from pydcop_amd.mgm import MgmEngine
         self.graph = graph
-        self._e = MgmEngine(graph, params)
+        draws = p["draws"] if p else "fixed"
+        self._many = bool(p) and int(p["restarts"]) > 1
+        if draws == "fixed":
+            if self._many:
+                raise ValueError("mgm_gpu: restarts needs draws:keyed (with the fixed draws every run is the same run)")
+            self._e = MgmEngine(graph, params)
+        else:
+            self._e = MgmEngine(graph, params, draws=draws, seed=int(p["seed"]), replicas=int(p["restarts"]))
 
     def run(self, n: int):
         self._e.run(int(n))
 
     def assignment(self):
-        return self._e.assignment()
+        if not self._many:
+            return self._e.assignment()
+        return self._e.assignment(self._e.best()["replica"])     # the best replica's values and held costs
 
     @property
     def cycle_count(self) -> int:
@@ -82,7 +104,7 @@ class _MgmSession(_base._Session):
         return Params(mode=algo.mode, dtype=p["precision"])
 
     def _make_engine(self, params, p):
-        return _RoundEngine(self.graph, params)
+        return _RoundEngine(self.graph, params, p)
 
     def _cycles_to_run(self, p) -> int:
         stop = int(p["stop_cycle"])

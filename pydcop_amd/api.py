@@ -50,7 +50,7 @@ def _engine_for(graph: FlatGraph, params: Params, device: int, devices: int, lib
             from .dba import DbaEngine
             return DbaEngine(graph, params, device=device, lib_path=lib_path, **algo_kw)
         from .mgm import MgmEngine
-        return MgmEngine(graph, params, device=device, lib_path=lib_path)
+        return MgmEngine(graph, params, device=device, lib_path=lib_path, **algo_kw)
     from .engine import MaxSumEngine
     if devices and int(devices) > 1:
         from .sharded import LocalShardedMaxSum
@@ -59,7 +59,7 @@ def _engine_for(graph: FlatGraph, params: Params, device: int, devices: int, lib
 
 
 def _algo_kw(algo, variant, probability, p_mode, seed, threshold, favor, modifier="A", violation="NZ",
-             increase_mode="E", dba_infinity=10000, max_distance=50, restarts=1):
+             increase_mode="E", dba_infinity=10000, max_distance=50, restarts=1, draws="fixed"):
     if algo == "dba":
         return dict(infinity=dba_infinity, max_distance=max_distance, seed=seed)
     if algo == "gdba":
@@ -68,6 +68,8 @@ def _algo_kw(algo, variant, probability, p_mode, seed, threshold, favor, modifie
         return dict(variant=variant, probability=probability, p_mode=p_mode, seed=seed, replicas=int(restarts))
     if algo == "mgm2":
         return dict(threshold=threshold, favor=favor, seed=seed)
+    if algo == "mgm" and draws != "fixed":
+        return dict(draws=draws, seed=seed, replicas=int(restarts))
     return None
 
 
@@ -86,11 +88,17 @@ def _run_and_trace(eng, algo: str, cycles: int, cost_every: int, infinity: float
     return curve
 
 
-def _check_restarts(algo, restarts, best_every):
+def _check_restarts(algo, restarts, best_every, draws="fixed"):
     if int(restarts) < 1 or int(best_every) < 0:
         raise ValueError("restarts must be at least 1 and best_every at least 0")
-    if algo != "dsa" and (int(restarts) != 1 or int(best_every) != 0):
-        raise ValueError("restarts / best_every: algo=\"dsa\" only")
+    if draws not in ("fixed", "keyed"):
+        raise ValueError("draws must be \"fixed\" or \"keyed\"")
+    if draws != "fixed" and algo != "mgm":
+        raise ValueError("draws: algo=\"mgm\" only (the other local searches always key their draws on `seed`)")
+    if int(restarts) != 1 and not (algo == "dsa" or (algo == "mgm" and draws == "keyed")):
+        raise ValueError("restarts: algo=\"dsa\", or algo=\"mgm\" with draws=\"keyed\"")
+    if algo != "dsa" and int(best_every) != 0:
+        raise ValueError("best_every: algo=\"dsa\" only")
 
 
 def _dsa_best(eng, algo, restarts, best_every, infinity):
@@ -104,6 +112,16 @@ def _dsa_best(eng, algo, restarts, best_every, infinity):
     costs, _ = eng.replica_costs(infinity)
     return best["idx"], {"replica": best["replica"], "best_cycle": best["cycle"],
                          "replica_costs": [float(c) for c in costs]}
+
+
+def _mgm_best(eng, algo, restarts, infinity):
+    """algo="mgm" with restarts (keyed draws): (idx of the best replica's final state, the result's extra keys); the
+    device cost only ranks.  Else None."""
+    if algo != "mgm" or int(restarts) == 1:
+        return None
+    best = eng.best(infinity)
+    costs, _ = eng.replica_costs(infinity)
+    return best["idx"], {"replica": best["replica"], "replica_costs": [float(c) for c in costs]}
 
 
 def _dba_end(eng, algo):
@@ -129,7 +147,8 @@ def solve_dcop(dcop, cycles: int = 30, *, damping: float = 0.5, damping_nodes: s
                cost_every: int = 0, lib_path: Optional[str] = None, devices: int = 1, algo: str = "maxsum",
                variant: str = "B", probability: float = 0.7, p_mode: str = "fixed", threshold: float = 0.5,
                favor: str = "unilateral", modifier: str = "A", violation: str = "NZ", increase_mode: str = "E",
-               dba_infinity: int = 10000, max_distance: int = 50, restarts: int = 1, best_every: int = 0) -> Dict:
+               dba_infinity: int = 10000, max_distance: int = 50, restarts: int = 1, best_every: int = 0,
+               draws: str = "fixed") -> Dict:
     """Synchronous Max-Sum for exactly `cycles` cycles; parameters and defaults are those
     of `pydcop.algorithms.maxsum` (maxsum.py:212-220), `infinity` that of
     `pydcop.infrastructure.run.solve` (run.py:49).  `algo`: "amaxsum" (`cycles` = generations of
@@ -152,20 +171,26 @@ def solve_dcop(dcop, cycles: int = 30, *, damping: float = 0.5, damping_nodes: s
     keeps every run's best state seen at cycle 0 and after every k-th cycle, on the device.  The assignment is then
     the best run's (its best record when tracking, else its final state; fewest violations, then cost, ranked on
     the device -- `cost` and `violation` are still `DCOP.solution_cost` of it) and the result gains "replica",
-    "best_cycle" and "replica_costs" (the final states' device costs; `cost_curve` follows replica 0)."""
-    _check_restarts(algo, restarts, best_every)
+    "best_cycle" and "replica_costs" (the final states' device costs; `cost_curve` follows replica 0).
+
+    algo="mgm": `draws` = "fixed" (the default: first domain value at start, first of equally good values) or "keyed"
+    (both draws from the generator DSA uses, keyed on `seed`).  With draws="keyed", `restarts` = R seeded runs (seeds
+    seed .. seed + R - 1) in one engine: the assignment is the best run's final state (fewest violations, then cost,
+    ranked on the device) and the result gains "replica" and "replica_costs".  `best_every` stays DSA's: the sum MGM
+    descends on never rises, so a run's final state is already its best and there is nothing to track."""
+    _check_restarts(algo, restarts, best_every, draws)
     graph = compile_dcop(dcop, noise=noise if algo in ("maxsum", "amaxsum") else 0.0, seed=seed)
     params = Params(mode=dcop.objective, damping=damping, damping_nodes=damping_nodes,
                     stability=stability, start_messages=start_messages, dtype=precision)
     algo_kw = _algo_kw(algo, variant, probability, p_mode, seed, threshold, favor, modifier, violation, increase_mode,
-                       dba_infinity, max_distance, restarts)
+                       dba_infinity, max_distance, restarts, draws)
     with _engine_for(graph, params, device, devices, lib_path, algo, algo_kw) as eng:
         if algo == "dsa" and int(best_every) > 0:
             eng.track_best(int(best_every), infinity)
         curve = _run_and_trace(eng, algo, cycles, cost_every, infinity)
         idx, _ = eng.assignment()
         extra = _dba_end(eng, algo)
-        best = _dsa_best(eng, algo, restarts, best_every, infinity)
+        best = _dsa_best(eng, algo, restarts, best_every, infinity) or _mgm_best(eng, algo, restarts, infinity)
         if best:
             idx, more = best
             extra.update(more)
@@ -181,23 +206,24 @@ def solve_flat(graph: FlatGraph, objective: str = "min", cycles: int = 30, *, da
                lib_path: Optional[str] = None, devices: int = 1, algo: str = "maxsum", variant: str = "B",
                probability: float = 0.7, p_mode: str = "fixed", seed: int = 0, threshold: float = 0.5,
                favor: str = "unilateral", modifier: str = "A", violation: str = "NZ", increase_mode: str = "E",
-               dba_infinity: int = 10000, max_distance: int = 50, restarts: int = 1, best_every: int = 0) -> Dict:
+               dba_infinity: int = 10000, max_distance: int = 50, restarts: int = 1, best_every: int = 0,
+               draws: str = "fixed") -> Dict:
     """`solve_dcop` for an already compiled instance (`FlatGraph`, e.g. loaded from the
     .npz instance format): no pyDCOP import at all.  Cost and violations come from the
     device (`mxs_eval_cost` = DCOP.solution_cost, pydcop/dcop/dcop.py:308-367); noise, if
     wanted, is already folded into `graph.var_cost` by whoever compiled the instance."""
     params = Params(mode=objective, damping=damping, damping_nodes=damping_nodes,
                     stability=stability, start_messages=start_messages, dtype=precision)
-    _check_restarts(algo, restarts, best_every)
+    _check_restarts(algo, restarts, best_every, draws)
     algo_kw = _algo_kw(algo, variant, probability, p_mode, seed, threshold, favor, modifier, violation, increase_mode,
-                       dba_infinity, max_distance, restarts)
+                       dba_infinity, max_distance, restarts, draws)
     with _engine_for(graph, params, device, devices, lib_path, algo, algo_kw) as eng:
         if algo == "dsa" and int(best_every) > 0:
             eng.track_best(int(best_every), infinity)
         curve = _run_and_trace(eng, algo, cycles, cost_every, infinity)
         idx, _ = eng.assignment()
         extra = _dba_end(eng, algo)
-        best = _dsa_best(eng, algo, restarts, best_every, infinity)
+        best = _dsa_best(eng, algo, restarts, best_every, infinity) or _mgm_best(eng, algo, restarts, infinity)
         if best:
             idx, more = best
             extra.update(more)
@@ -282,7 +308,7 @@ def main(argv=None):
              "damping_nodes": str, "start_messages": str, "precision": str, "devices": int,
              "variant": str, "probability": float, "p_mode": str, "threshold": float, "favor": str,
              "modifier": str, "violation": str, "increase_mode": str, "infinity": int, "max_distance": int,
-             "restarts": int, "best_every": int}
+             "restarts": int, "best_every": int, "draws": str}
     kw = {}
     for item in args.algo_params:
         name, _, value = item.partition(":")
@@ -305,7 +331,7 @@ def main(argv=None):
     if len(args.dcop_files) == 1 and args.dcop_files[0].endswith(".npz"):
         graph, header = FlatGraph.load(args.dcop_files[0])
         kw.pop("noise", None)  # folded into the instance when it was compiled
-        if args.algo not in ("dsa", "mgm2", "gdba", "dba"):
+        if args.algo not in ("dsa", "mgm", "mgm2", "gdba", "dba"):
             kw.pop("seed", None)
         if args.algo == "dpop":
             res = solve_flat_dpop(graph, header.get("objective", "min"), infinity=args.infinity,

@@ -15,7 +15,7 @@
 // blockIdx.x (block = replica * blocks_per_replica + block of the replica): whole blocks belong to one
 // replica, everything a kernel derives from the replica is block-uniform (R = 1 runs instantiations without it).  Replica r is bit for bit the
 // single-seed run with seed seeds[r]; mxs_dsa_create is R = 1 of the same path.  Per replica, the solution
-// cost of the current assignment is reduced on the device (k_dsa_cost_partial / k_dsa_cost_final: fixed
+// cost of the current assignment is reduced on the device (replica_cost.h, shared with mgm.hip: fixed
 // shape, no atomics) and the best state seen can be kept on the device (k_dsa_best_copy).
 //
 // The reference draws from Python's unseeded `random` module (initial value, move test, choice
@@ -38,6 +38,7 @@
 #include "../../include/maxsum_gpu.h"
 #include "engine_common.h"
 #include "local_search.h"
+#include "replica_cost.h"
 
 namespace dsa {
 
@@ -79,20 +80,7 @@ struct Dev {
     const double* pack_prob;               // [packed variables] the change probability
 };
 
-// the replica of this block and the block's index inside the replica (block-uniform).  REP = false: the
-// instantiation of the cycle kernels for ONE replica -- nothing is derived from blockIdx.x, the code of a
-// single-seed engine is what it was before there were replicas.
-template <bool REP, typename T>
-__device__ inline int replica_of_block(const Dev<T>& g, int* b) {
-    if constexpr (!REP) {
-        *b = (int)blockIdx.x;
-        return 0;
-    } else {
-        const int r = (int)(blockIdx.x / (unsigned)g.bpr);
-        *b = (int)blockIdx.x - r * g.bpr;
-        return r;
-    }
-}
+using repcost::replica_of_block;   // block = replica * bpr + b (replica_cost.h); REP = false: one replica, nothing derived
 
 template <typename T>
 __device__ T constraint_at(const Dev<T>& g, const int32_t* cur, int f, int v, int x) {
@@ -362,94 +350,14 @@ __global__ void __launch_bounds__(AUX_TPB) k_dsa_init(Dev<T> g, const int32_t* i
     g.cost[at] = iso >= 0 ? iso_cost[v] : (T)0;
 }
 
-// ---- the solution cost of every replica's current assignment (HostGraph::eval_cost = DCOP.solution_cost):
-// the constraints' entries plus the variables' own eval_var_cost, an entry equal to `infinity` counted as a
-// violation instead.  Items = the constraints, then the variables.  FIXED SHAPE: a thread folds COST_RUN
-// consecutive items in index order, the block's COST_TPB sums are combined by one tree in LDS, the block's
-// partial goes to part[r][b]; k_dsa_cost_final adds a replica's partials in index order.  No atomics: the same
-// bits from run to run.  Sums in f64; the tables are the engine's (T): in f32 mode the cost is that of the
-// narrowed tables (eval_var_cost is kept in f64).
-constexpr int COST_TPB = 256, COST_RUN = 4;
-struct CostArgs {
-    const int64_t* coff;     // [n_vars + 1] offsets into evc
-    const double* evc;       // eval_var_cost
-    int32_t n_factors;
-    double infinity;
-    double* part_cost;       // [n_rep][bpr]
-    long long* part_viol;
-};
-template <typename T>
-__global__ void __launch_bounds__(COST_TPB) k_dsa_cost_partial(Dev<T> g, CostArgs a) {
-    __shared__ double s_cost[COST_TPB];
-    __shared__ long long s_viol[COST_TPB];
-    int b;
-    const int r = replica_of_block<true>(g, &b);
-    const int32_t* cur = g.cur + (int64_t)r * g.n_vars;
-    const int t = (int)threadIdx.x;
-    const int64_t n_items = (int64_t)a.n_factors + g.n_vars;
-    const int64_t i0 = ((int64_t)b * COST_TPB + t) * COST_RUN;
-    double soft = 0.0;
-    long long hard = 0;
-    for (int64_t i = i0; i < i0 + COST_RUN && i < n_items; ++i) {
-        double e;
-        if (i < a.n_factors) {
-            e = (double)constraint_at(g, cur, (int)i, -1, 0);
-        } else {
-            const int v = (int)(i - a.n_factors);
-            e = a.evc[a.coff[v] + cur[g.q[v]]];
-        }
-        if (e != a.infinity) soft += e;
-        else hard += 1;
-    }
-    s_cost[t] = soft;
-    s_viol[t] = hard;
-    __syncthreads();
-    for (int s = COST_TPB / 2; s > 0; s >>= 1) {
-        if (t < s) {
-            s_cost[t] += s_cost[t + s];
-            s_viol[t] += s_viol[t + s];
-        }
-        __syncthreads();
-    }
-    if (t == 0) {
-        a.part_cost[(int64_t)r * g.bpr + b] = s_cost[0];
-        a.part_viol[(int64_t)r * g.bpr + b] = s_viol[0];
-    }
-}
+// ---- the solution cost of every replica's current assignment: k_cost_partial / k_cost_final of replica_cost.h (one
+// implementation, shared with mgm.hip); BestRec: the best state a replica has shown (mxs_dsa_track_best)
+using repcost::BestRec;
+using repcost::COST_RUN;
+using repcost::COST_TPB;
+using repcost::CostArgs;
 
-// the best state a replica has shown (mxs_dsa_track_best): the record and the snapshot, in packed order
-struct BestRec {
-    double* cost;          // [n_rep]
-    long long* viol;
-    long long* cycle;
-    int32_t* improved;     // [n_rep] written by k_dsa_cost_final, read by k_dsa_best_copy (the next launch)
-    int32_t* idx;          // [n_rep][n_vars]
-};
-// thread per replica: the partials in index order; mode 0: the costs alone, 1: improved[r] = the current state
-// is STRICTLY better than the record (fewer violations, or as many and a lower -- max: higher -- cost),
-// 2: improved[r] = 1 (the first record).  The record itself is not touched here.
-__global__ void __launch_bounds__(64) k_dsa_cost_final(int n_rep, int n_blocks, int is_max, const double* part_cost,
-                                                       const long long* part_viol, double* cost, long long* viol, int mode,
-                                                       BestRec best) {
-    const int r = (int)(blockIdx.x * blockDim.x + threadIdx.x);
-    if (r >= n_rep) return;
-    double soft = 0.0;
-    long long hard = 0;
-    for (int b = 0; b < n_blocks; ++b) {
-        soft += part_cost[(int64_t)r * n_blocks + b];
-        hard += part_viol[(int64_t)r * n_blocks + b];
-    }
-    cost[r] = soft;
-    viol[r] = hard;
-    if (mode == 2) {
-        best.improved[r] = 1;
-    } else if (mode == 1) {
-        const long long bv = best.viol[r];
-        const double bc = best.cost[r];
-        best.improved[r] = (hard < bv || (hard == bv && (is_max ? soft > bc : soft < bc))) ? 1 : 0;
-    }
-}
-// a launch of its own, after k_dsa_cost_final in stream order: the replicas that improved copy their state
+// a launch of its own, after k_cost_final in stream order: the replicas that improved copy their state
 // and take the new record (nothing in this launch reads a record)
 __global__ void __launch_bounds__(AUX_TPB) k_dsa_best_copy(int n_vars, int bpr, const int32_t* cur, const double* cost,
                                                            const long long* viol, long long cycle, BestRec best) {
@@ -465,7 +373,7 @@ __global__ void __launch_bounds__(AUX_TPB) k_dsa_best_copy(int n_vars, int bpr, 
     }
 }
 
-constexpr int MAX_REPLICAS = 4096;
+using repcost::MAX_REPLICAS;
 
 struct Base {
     virtual ~Base() {}
@@ -507,7 +415,7 @@ struct Engine : Base {
     // the start state of the variables without neighbours (k_dsa_init)
     Buf<int32_t> iso_val;
     Buf<T> iso_cost;
-    // the device cost (k_dsa_cost_partial / k_dsa_cost_final)
+    // the device cost (k_cost_partial / k_cost_final, replica_cost.h)
     Buf<int64_t> coff;
     Buf<double> evc, part_cost, rep_cost;
     Buf<long long> part_viol, rep_viol;
@@ -684,16 +592,15 @@ struct Engine : Base {
         return rc;
     }
 
-    // the costs of the replicas' current assignments into rep_cost / rep_viol, on the stream; mode: k_dsa_cost_final
+    // the costs of the replicas' current assignments into rep_cost / rep_viol, on the stream; mode: k_cost_final
     int launch_costs(double infinity, int mode) {
-        g.cur = cur[which].p;
         g.bpr = cost_blocks;
-        const CostArgs a{coff.p, evc.p, hg.nF, infinity, part_cost.p, part_viol.p};
-        hipLaunchKernelGGL((k_dsa_cost_partial<T>), dim3((unsigned)(cost_blocks * n_rep)), dim3(COST_TPB), 0, stream, g, a);
+        const CostArgs a{cur[which].p, coff.p, evc.p, hg.nF, infinity, part_cost.p, part_viol.p};
+        hipLaunchKernelGGL((repcost::k_cost_partial<Dev<T>>), dim3((unsigned)(cost_blocks * n_rep)), dim3(COST_TPB), 0, stream, g, a);
         MXS_TRY(hipGetLastError());
-        hipLaunchKernelGGL(k_dsa_cost_final, dim3((unsigned)blocks_of(n_rep, 64)), dim3(64), 0, stream, (int)n_rep, cost_blocks,
-                           (int)g.is_max, (const double*)part_cost.p, (const long long*)part_viol.p, rep_cost.p, rep_viol.p,
-                           mode, best_rec());
+        hipLaunchKernelGGL((repcost::k_cost_final<BestRec>), dim3((unsigned)blocks_of(n_rep, 64)), dim3(64), 0, stream, (int)n_rep,
+                           cost_blocks, (int)g.is_max, (const double*)part_cost.p, (const long long*)part_viol.p, rep_cost.p,
+                           rep_viol.p, mode, best_rec());
         MXS_TRY(hipGetLastError());
         return MXS_OK;
     }
@@ -844,16 +751,6 @@ struct Engine : Base {
         return MXS_OK;
     }
 
-    // (violations, cost -- negated in max mode --, index): the lexicographic minimum
-    int best_replica(const std::vector<double>& hc, const std::vector<long long>& hv) const {
-        int best = 0;
-        for (int r = 1; r < n_rep; ++r) {
-            const double a = g.is_max ? -hc[r] : hc[r], b = g.is_max ? -hc[best] : hc[best];
-            if (hv[r] < hv[best] || (hv[r] == hv[best] && a < b)) best = r;
-        }
-        return best;
-    }
-
     int get_best(int32_t r, int32_t* replica, int64_t* cycle, double* cst, int64_t* viol, int32_t* idx) override {
         if (r < -1 || r >= n_rep) return fail(MXS_E_INVALID, "replica out of range");
         if (!tracked) return fail(MXS_E_STATE, "mxs_dsa_get_best before mxs_dsa_track_best");
@@ -868,7 +765,7 @@ struct Engine : Base {
             if (int rc = launch_costs(best_infinity, 0)) return rc;
             if (int rc = fetch_costs(hc, hv, rep_cost.p, rep_viol.p)) return rc;
         }
-        if (r < 0) r = best_replica(hc, hv);
+        if (r < 0) r = repcost::best_replica(n_rep, g.is_max, hc.data(), hv.data());
         if (replica) *replica = r;
         if (cycle) *cycle = (int64_t)hy[r];
         if (cst) *cst = hc[r];

@@ -57,12 +57,15 @@ struct Buf {
 };
 
 // ---- the generator: every draw of the reference's unseeded `random` is a function of (seed, variable, cycle, draw),
-// the splitmix64 finaliser over that key -- oracle/dsa_oracle.c, tests/mgm2_oracle.py, tests/gdba_oracle.py, bit for bit.
+// the splitmix64 finaliser over that key -- oracle/dsa_oracle.c, tests/mgm2_oracle.py, tests/gdba_oracle.py,
+// tests/mgm_keyed_oracle.py, bit for bit.
 // The draw ids in use:
 //   DSA    0 start value, 1 move test, 2 choice among the best values
 //   MGM-2  0 start, 1 offerer test, 2 partner, 3 best unilateral value, 4 the `favor: no` coin, 5 the accepted offer
 //   GDBA   6 start value (cycle 0), 7 one of the best values
 //   DBA    8 start value (cycle 0), 9 one of the best values (at the computation's cycle_count: round - 1)
+//   MGM    10 start value (cycle 0), 11 one of the best values (at the computation's cycle_count: round k, from 1, is k);
+//          mxs_mgm_create_keyed only -- mxs_mgm_create fixes both draws to "first"
 __host__ __device__ inline uint64_t mix64(uint64_t z) {
     z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
     z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;

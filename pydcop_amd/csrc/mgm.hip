@@ -16,23 +16,48 @@
 // are restated as they are and listed in oracle/mgm_oracle.c, whose arithmetic this file follows
 // expression for expression (the oracle is pinned against the reference's own MgmComputation).
 // The reference's draws from the unseeded `random` module are fixed the way the oracle fixes them:
-// first domain value at start, first of equally good values.
+// first domain value at start, first of equally good values (mxs_mgm_create).
+//
+// KEYED DRAWS (mxs_mgm_create_keyed): the two draws come from the counter-based generator of engine_common.h,
+// u = uniform(seeds[r], v, cycle, draw) with v the GRAPH index of the variable (never its packed position):
+//   draw 10  start value of a variable with neighbours and no initial value: int(u * D), cycle 0    (mgm.py:301)
+//   draw 11  one of the best values, when the gain strictly improves: B[int(u * |B|)], B = the values whose
+//            utilities_at equals the optimum exactly (in T), in domain order (find_arg_optimal)      (mgm.py:379)
+// The cycle of draw 11 is the computation's cycle_count when it handles the round's values: the counter starts
+// at 1 and new_cycle() runs after the decision, so engine round k (1-based) is cycle k = rounds + 1 (Dev::round;
+// pinned against the reference's own MgmComputation by tests/test_mgm_keyed_oracle_vs_reference.py).  The
+// random.random() of _send_gain (mgm.py:407) has no effect and gets no draw.
+//
+// REPLICAS: a keyed engine advances R seeded runs with the same launches, as dsa.hip does.  Everything static is
+// stored once; the dynamic state -- cur[2], cost[2], has_cost, grec, vcc[2] -- is [R][n_vars] in packed order, the
+// seeds are a device array.  The replica is folded into blockIdx.x (block = replica * bpr + b, replica_cost.h):
+// whole blocks belong to one replica, which shifts the state pointers of its copy of Dev once (enter_replica).
+// Replica r is bit for bit the keyed single run with seeds[r].  The kernels are templates <REP, KEYED>: the
+// fixed-draw engine runs <false, false> on the plain Dev -- the parent's argument layout and instructions --,
+// a keyed engine <R > 1, true> on DevR.  MGM's own sum never rises, so its final state is its best: no best-state
+// tracking, the final states are ranked (replica_cost.h: the reduction shared with dsa.hip).
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
 #include <cstdlib>
 #include <cstring>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/maxsum_gpu.h"
 #include "engine_common.h"
 #include "local_search.h"
+#include "replica_cost.h"
 
 namespace mgm {
 
 using mxs_host::Buf;
 using mxs_host::fail;
+using mxs_host::uniform;   // draws 10 (start value) and 11 (one of the best values)
+using repcost::replica_of_block;
+
+constexpr int D_START = 10, D_BEST = 11;
 
 constexpr int TPB = 64;  // one wave per block: 100k variables spread over every CU (latency-bound CSR walks)
 
@@ -75,6 +100,39 @@ struct Dev {
     const int32_t* q;
     const int32_t* pack_dom;     // [packed variables] dom_size in packed order
 };
+
+// what a keyed engine's kernels take: Dev plus the replicas and the keys of the draws.  The fixed-draw kernels
+// keep the plain Dev, i.e. their argument layout.  The per-replica arrays of Dev -- cur, cost, cur_out, cost_out,
+// has_cost, grec, vcc, vcc_out -- are [replicas][n_vars]: replica r at + r * n_vars (64-bit).
+template <typename T>
+struct DevR : Dev<T> {
+    int32_t bpr;               // blocks per replica of the launch being made (block = replica * bpr + b)
+    int32_t n_rep;
+    const uint64_t* seeds;     // [replicas]
+    int64_t round;             // the cycle_count of the round being handled: rounds + 1 (the key of draw 11)
+    const int32_t* pack_var;   // [packed variables] graph index of the packed position (the key of draw 11)
+};
+template <typename T, bool REP, bool KEYED>
+using DevOf = typename std::conditional<REP || KEYED, DevR<T>, Dev<T>>::type;
+
+// the replica of this block; REP: the block's copy of Dev (kernel arguments, block-uniform) moves to the
+// replica's slice of the dynamic state, so that nothing below knows about replicas
+template <bool REP, typename G, typename T>
+__device__ inline int enter_replica(G& g, T*& cost_rw, int* b) {
+    const int r = replica_of_block<REP>(g, b);
+    if constexpr (REP) {
+        const int64_t off = (int64_t)r * g.n_vars;
+        g.cur += off, g.cost += off, g.cur_out += off, g.cost_out += off;
+        g.has_cost += off, g.grec += off, g.vcc += off, g.vcc_out += off;
+        if (cost_rw) cost_rw += off;
+    }
+    return r;
+}
+// improving: the gain is strictly better than nothing (mgm.py:376-378)
+template <typename T>
+__device__ inline bool improves(int is_max, T gain) {
+    return (!is_max && gain > (T)0) || (is_max && gain < (T)0);
+}
 
 // c.slice(neighbours' values)(x): the table entry with v at x, every other scope variable at its value
 template <typename T>
@@ -121,9 +179,11 @@ __device__ T add_concerned_costs(const Dev<T>& g, int v, T acc) {
     return acc;
 }
 
-template <typename T>
-__global__ void __launch_bounds__(TPB) k_mgm_gain(Dev<T> g, T* cost_rw) {
-    const int tid = blockIdx.x * blockDim.x + threadIdx.x;
+template <typename T, bool REP, bool KEYED>
+__global__ void __launch_bounds__(TPB) k_mgm_gain(DevOf<T, REP, KEYED> g, T* cost_rw) {
+    int b;
+    [[maybe_unused]] const int r = enter_replica<REP>(g, cost_rw, &b);
+    const int tid = REP ? b * (int)blockDim.x + (int)threadIdx.x : (int)(blockIdx.x * blockDim.x + threadIdx.x);
     if (tid >= g.n_list) return;
     const int v = g.var_list ? g.var_list[tid] : tid;
     if (g.n_neigh[v] == 0) return;
@@ -136,23 +196,42 @@ __global__ void __launch_bounds__(TPB) k_mgm_gain(Dev<T> g, T* cost_rw) {
     }
     T best = (T)0;
     int best_x = -1;
+    [[maybe_unused]] int n_best = 0;  // KEYED: the length of the list
     for (int x = 0; x < g.dom_size[v]; ++x) {  // find_arg_optimal: strictly better starts a new list
-        const T r = utilities_at(g, v, x);
-        if (best_x < 0 || (g.is_max ? best < r : best > r)) {
-            best = r;
+        const T u = utilities_at(g, v, x);
+        if (best_x < 0 || (g.is_max ? best < u : best > u)) {
+            best = u;
             best_x = x;
+            if constexpr (KEYED) n_best = 1;
+        } else if constexpr (KEYED) {
+            if (u == best) n_best += 1;    // equal joins it
         }
     }
     const T val_cost = add_concerned_costs(g, v, best);  // own cost at the CURRENT value (:449-450)
     const T gain = cost - val_cost;
+    if constexpr (KEYED) {  // random.choice(new_values): the j-th of the list, a second pass over the domain
+        if (improves(g.is_max, gain) && n_best > 1) {
+            int j = (int)(uniform(g.seeds[r], v, g.round, D_BEST) * n_best);
+            for (int x = 0; x < g.dom_size[v]; ++x) {
+                if (utilities_at(g, v, x) != best) continue;
+                if (j-- == 0) {
+                    best_x = x;
+                    break;
+                }
+            }
+        }
+    }
     const int nvl = ((!g.is_max && gain > (T)0) || (g.is_max && gain < (T)0)) ? best_x : g.cur[qv];
     g.grec[qv].gain = gain;
     g.grec[qv].newv = nvl;
 }
 
-template <typename T>
-__global__ void __launch_bounds__(TPB) k_mgm_move(Dev<T> g) {
-    const int tid = blockIdx.x * blockDim.x + threadIdx.x;
+template <typename T, bool REP>
+__global__ void __launch_bounds__(TPB) k_mgm_move(DevOf<T, REP, false> g) {
+    int b;
+    T* none = nullptr;
+    enter_replica<REP>(g, none, &b);
+    const int tid = REP ? b * (int)blockDim.x + (int)threadIdx.x : (int)(blockIdx.x * blockDim.x + threadIdx.x);
     if (tid >= g.n_list) return;
     const int v = g.var_list ? g.var_list[tid] : tid;
     const int qv = g.q[v];
@@ -203,9 +282,11 @@ __device__ T add_concerned_costs_listed(const Dev<T>& g, int v, T acc) {
     return acc;
 }
 
-template <typename T, int MAXD>
-__global__ void __launch_bounds__(TPB) k_mgm_gain_slots(Dev<T> g, T* cost_rw) {
-    const int tid = blockIdx.x * blockDim.x + threadIdx.x;
+template <typename T, int MAXD, bool REP, bool KEYED>
+__global__ void __launch_bounds__(TPB) k_mgm_gain_slots(DevOf<T, REP, KEYED> g, T* cost_rw) {
+    int b;
+    [[maybe_unused]] const int r = enter_replica<REP>(g, cost_rw, &b);
+    const int tid = REP ? b * (int)blockDim.x + (int)threadIdx.x : (int)(blockIdx.x * blockDim.x + threadIdx.x);
     if (tid >= g.n_list) return;
     const int v = g.var_list ? g.var_list[tid] : tid;
     if (g.n_neigh[v] == 0) return;
@@ -237,14 +318,36 @@ __global__ void __launch_bounds__(TPB) k_mgm_gain_slots(Dev<T> g, T* cost_rw) {
         }
     const T val_cost = add_concerned_costs_listed(g, v, best);
     const T gain = cost - val_cost;
+    if constexpr (KEYED) {  // random.choice(new_values): the values equal to the optimum, the j-th in domain order
+        if (improves(g.is_max, gain)) {
+            int n_best = 0;
+#pragma unroll
+            for (int x = 0; x < MAXD; ++x) n_best += (x < D && c[x] == best) ? 1 : 0;
+            if (n_best > 1) {
+                int j = (int)(uniform(g.seeds[r], v, g.round, D_BEST) * n_best);
+                bool done = false;
+#pragma unroll
+                for (int x = 0; x < MAXD; ++x)
+                    if (x < D && !done && c[x] == best) {
+                        if (j-- == 0) {
+                            best_x = x;
+                            done = true;
+                        }
+                    }
+            }
+        }
+    }
     const int nvl = ((!g.is_max && gain > (T)0) || (g.is_max && gain < (T)0)) ? best_x : g.cur[qv];
     g.grec[qv].gain = gain;
     g.grec[qv].newv = nvl;
 }
 
-template <typename T>
-__global__ void __launch_bounds__(TPB) k_mgm_move_listed(Dev<T> g) {
-    const int tid = blockIdx.x * blockDim.x + threadIdx.x;
+template <typename T, bool REP>
+__global__ void __launch_bounds__(TPB) k_mgm_move_listed(DevOf<T, REP, false> g) {
+    int b;
+    T* none = nullptr;
+    enter_replica<REP>(g, none, &b);
+    const int tid = REP ? b * (int)blockDim.x + (int)threadIdx.x : (int)(blockIdx.x * blockDim.x + threadIdx.x);
     if (tid >= g.n_list) return;
     const int v = g.var_list ? g.var_list[tid] : tid;
     const int qv = g.q[v];
@@ -322,10 +425,12 @@ __device__ inline T pack_add_concerned(const Dev<T>& g, const PackLane& p, int64
     return acc;
 }
 
-template <typename T, typename TT>
-__global__ void __launch_bounds__(PACK_TPB) k_mgm_gain_pack(Dev<T> g, T* cost_rw) {
+template <typename T, typename TT, bool REP, bool KEYED>
+__global__ void __launch_bounds__(PACK_TPB) k_mgm_gain_pack(DevOf<T, REP, KEYED> g, T* cost_rw) {
     constexpr int MAXD = lsearch::PACK_D;
-    const int64_t pos = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    int b;
+    [[maybe_unused]] const int r = enter_replica<REP>(g, cost_rw, &b);
+    const int64_t pos = (int64_t)(REP ? (unsigned)b : blockIdx.x) * blockDim.x + threadIdx.x;
     if (pos >= g.pack.n_lanes) return;  // whole waves
     const PackLane p = pack_lane(g, pos);
     const int v = p.q, D = g.pack_dom[v], mine = g.cur[v];  // (v: packed position; nb / conc hold positions too)
@@ -349,6 +454,25 @@ __global__ void __launch_bounds__(PACK_TPB) k_mgm_gain_pack(Dev<T> g, T* cost_rw
     }
     const T val_cost = pack_add_concerned(g, p, pos, best);  // own cost at the CURRENT value (mgm.py:449-450)
     const T gain = cost - val_cost;
+    if constexpr (KEYED) {  // random.choice(new_values): every lane of the variable takes the same pick
+        if (improves(g.is_max, gain)) {
+            int n_best = 0;
+#pragma unroll
+            for (int x = 0; x < MAXD; ++x) n_best += (x < D && c[x] == best) ? 1 : 0;
+            if (n_best > 1) {
+                int j = (int)(uniform(g.seeds[r], g.pack_var[v], g.round, D_BEST) * n_best);
+                bool done = false;
+#pragma unroll
+                for (int x = 0; x < MAXD; ++x)
+                    if (x < D && !done && c[x] == best) {
+                        if (j-- == 0) {
+                            best_x = x;
+                            done = true;
+                        }
+                    }
+            }
+        }
+    }
     if (p.has && p.k == 0) {
         if (first_round) {
             cost_rw[v] = cost;
@@ -360,9 +484,12 @@ __global__ void __launch_bounds__(PACK_TPB) k_mgm_gain_pack(Dev<T> g, T* cost_rw
     }
 }
 
-template <typename T>
-__global__ void __launch_bounds__(PACK_TPB) k_mgm_move_pack(Dev<T> g) {
-    const int64_t pos = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+template <typename T, bool REP>
+__global__ void __launch_bounds__(PACK_TPB) k_mgm_move_pack(DevOf<T, REP, false> g) {
+    int b;
+    T* none = nullptr;
+    enter_replica<REP>(g, none, &b);
+    const int64_t pos = (int64_t)(REP ? (unsigned)b : blockIdx.x) * blockDim.x + threadIdx.x;
     if (pos >= g.pack.n_lanes) return;
     const PackLane p = pack_lane(g, pos);
     const int v = p.q;  // packed position (conc / conc_x hold positions too)
@@ -417,27 +544,62 @@ __global__ void __launch_bounds__(PACK_TPB) k_mgm_move_pack(Dev<T> g) {
     }
 }
 
+// the start state of every replica (on_start, mgm.py:279-305): a variable without neighbours takes its
+// optimal_cost_value (iso_val >= 0, the same in every replica) and holds its cost; the others their initial value,
+// else draw 10 of cycle 0 under seeds[r] (keyed) or the first value of the domain (fixed).  Both buffers of cur /
+// cost / vcc: the packed launches write only the variables that have neighbours.
+constexpr int AUX_TPB = 256;
+template <typename T>
+__global__ void __launch_bounds__(AUX_TPB) k_mgm_init(DevR<T> g, int keyed, const int32_t* iso_val, const T* iso_cost,
+                                                      const int32_t* init, int32_t* cur0, int32_t* cur1, T* cost0, T* cost1,
+                                                      T* vcc0, T* vcc1) {
+    int b;
+    const int r = replica_of_block<true>(g, &b);
+    const int v = b * (int)blockDim.x + (int)threadIdx.x;
+    if (v >= g.n_vars) return;
+    const int64_t at = (int64_t)r * g.n_vars + g.q[v];
+    const int iso = iso_val[v];
+    int x = 0;
+    if (iso >= 0) x = iso;
+    else if (init[v] >= 0) x = init[v];
+    else if (keyed) x = (int32_t)(uniform(g.seeds[r], v, 0, D_START) * g.dom_size[v]);
+    const T held = iso >= 0 ? iso_cost[v] : (T)0;
+    const T own = g.var_cost[g.cost_off[v] + x];
+    cur0[at] = x, cur1[at] = x;
+    cost0[at] = held, cost1[at] = held;
+    vcc0[at] = own, vcc1[at] = own;
+    g.has_cost[at] = iso >= 0 ? 1 : 0;
+    g.grec[at] = GainRec<T>{(T)0, x, g.name_rank[v]};  // no gain yet, the "new value" is the initial one
+}
+
+using repcost::MAX_REPLICAS;
+
 struct Base {
     virtual ~Base() {}
-    virtual int init(const mxs_graph& G, const mxs_params& p, const int32_t* rank, int device) = 0;
+    virtual int init(const mxs_graph& G, const mxs_params& p, const int32_t* rank, bool keyed, const uint64_t* seeds,
+                     int n_replicas, int device) = 0;
     virtual int reset() = 0;
     virtual int set_value_rank(const int32_t* rank) = 0;
     virtual int run(int32_t n) = 0;
-    virtual int get_state(int32_t* idx, double* cost, uint8_t* has, double* gain, int32_t* newv) = 0;
+    virtual int get_state(int32_t r, int32_t* idx, double* cost, uint8_t* has, double* gain, int32_t* newv) = 0;
     virtual int eval_cost(const int32_t* idx, double infinity, double* cost, int64_t* viol) = 0;
+    virtual int replica_costs(double infinity, double* cost, int64_t* viol) = 0;
+    virtual int best_replica(double infinity, int32_t* replica, double* cost, int64_t* viol) = 0;
     int64_t rounds = 0;
+    int32_t n_rep = 1;
 };
 
 template <typename T>
 struct Engine : Base {
     int device = 0;
     hipStream_t stream = nullptr;
-    Dev<T> g{};
+    DevR<T> g{};
     int which = 0;
+    bool keyed = false;
     mxs_host::HostGraph hg;
     std::vector<int32_t> h_nn, h_rank, h_q, h_vrank;
     Buf<int32_t> dom_size, factor_rowptr, edge_var, edge_factor, var_rowptr, var_edges, name_rank, n_neigh, qmap;
-    Buf<int32_t> cur[2];
+    Buf<int32_t> cur[2];                    // the dynamic state: [R][n_vars], packed order
     Buf<int64_t> table_off, cost_off;
     Buf<T> tables, var_cost;
     Buf<T> cost[2], vcc[2], vc4;
@@ -446,14 +608,45 @@ struct Engine : Base {
     mxs_host::DevSlots sl;
     mxs_host::DevPack<T> pk;
     Buf<int32_t> pk_conc, pk_conc_x;  // what only MGM keeps per lane (Dev::pack_conc, pack_conc_x)
+    Buf<int32_t> pk_var;              // [packed variables] graph index (DevR::pack_var)
     int max_dom = 0;
+    // the start state (k_mgm_init): the seeds, the initial values, the variables without neighbours
+    Buf<uint64_t> seeds;
+    Buf<int32_t> init_idx, iso_val;
+    Buf<T> iso_cost;
+    // the device cost (replica_cost.h)
+    Buf<double> evc, part_cost, rep_cost;
+    Buf<long long> part_viol, rep_viol;
+    int cost_blocks = 1;
 
     ~Engine() override {
         if (stream) (void)hipStreamDestroy(stream);
     }
 
-    int init(const mxs_graph& G, const mxs_params& p, const int32_t* rank, int dev) override {
+    // an allocation that grows with the number of replicas: its failure is MXS_E_NOMEM (the caller's
+    // destructor frees what was allocated before)
+    template <typename U>
+    static int alloc_rep(Buf<U>& b, size_t count, const char* what) {
+        if (b.alloc(count) != hipSuccess) {
+            (void)hipGetLastError();
+            b.p = nullptr;
+            b.n = 0;
+            return fail(MXS_E_NOMEM, std::string("out of device memory for the replicas' ") + what);
+        }
+        return MXS_OK;
+    }
+
+    static int blocks_of(int64_t n, int per_block) { return (int)((n + per_block - 1) / per_block); }
+
+    int init(const mxs_graph& G, const mxs_params& p, const int32_t* rank, bool kd, const uint64_t* sds, int n_replicas,
+             int dev) override {
         device = dev;
+        keyed = kd;
+        if (n_replicas < 1 || n_replicas > MAX_REPLICAS) return fail(MXS_E_INVALID, "the number of replicas must be in 1 .. 4096");
+        if (keyed && !sds) return fail(MXS_E_INVALID, "null seeds");
+        n_rep = n_replicas;
+        const std::vector<uint64_t> h_seeds = keyed ? std::vector<uint64_t>(sds, sds + n_replicas) : std::vector<uint64_t>(1, 0);
+        const size_t R = (size_t)n_rep;
         if (int rc = mxs_host::open_device(dev, &stream)) return rc;
         if (int rc = hg.load(G, p)) return rc;
         const int nV = hg.nV, nF = hg.nF;
@@ -474,15 +667,24 @@ struct Engine : Base {
         {   // the packed view of the variables it can take (local_search.h)
             lsearch::HostPack hp;
             hp.build(nV, hg.dom, vrow, h_nn, hs, hg.tables);
+            // every launch folds the replica into blockIdx.x: the largest grid must fit
+            cost_blocks = std::max(1, blocks_of((int64_t)nF + nV, repcost::COST_TPB * repcost::COST_RUN));
+            const int64_t most = std::max<int64_t>({blocks_of((int64_t)hp.nb.size(), PACK_TPB), blocks_of(nV, TPB), cost_blocks});
+            if (most * (int64_t)n_rep > INT32_MAX) return fail(MXS_E_INVALID, "too many replicas for an instance of this size");
             h_q = mxs_host::packed_order(hp, nV);
             MXS_TRY(qmap.upload(h_q, stream));
             if (int rc = sl.upload(hs, stream, &h_q, true)) return rc;
             std::vector<T> v4(hp.vars.size() * lsearch::PACK_D, (T)0);
-            for (int v : hp.vars)
+            std::vector<int32_t> pvar(hp.vars.size());
+            for (int v : hp.vars) {
+                pvar[h_q[v]] = v;
                 for (int x = 0; x < hg.dom[v]; ++x) v4[(size_t)h_q[v] * lsearch::PACK_D + x] = vc[hg.coff[v] + x];
+            }
             MXS_TRY(vc4.upload(v4, stream));
+            MXS_TRY(pk_var.upload(pvar, stream));
             g.q = qmap.p;
             g.vc4 = vc4.p;
+            g.pack_var = pk_var.p;
             std::vector<int32_t> conc(hp.nb.size(), -1), conc_x(hp.nb.size(), -1);
             for (size_t i = 0; i < hp.nb.size(); ++i) {
                 const int v = hp.lane_var[i];
@@ -514,16 +716,28 @@ struct Engine : Base {
         MXS_TRY(cost_off.upload(hg.coff, stream));
         MXS_TRY(tables.upload(tt, stream));
         MXS_TRY(var_cost.upload(vc, stream));
+        MXS_TRY(seeds.upload(h_seeds, stream));
+        MXS_TRY(init_idx.upload(hg.init, stream));
+        MXS_TRY(evc.upload(hg.eval_var_cost, stream));
+        MXS_TRY(iso_val.alloc(nV));
+        MXS_TRY(iso_cost.alloc(nV));
         for (int b = 0; b < 2; ++b) {
-            MXS_TRY(cur[b].alloc(nV));
-            MXS_TRY(cost[b].alloc(nV));
-            MXS_TRY(vcc[b].alloc(nV));
+            if (int rc = alloc_rep(cur[b], R * nV, "values")) return rc;
+            if (int rc = alloc_rep(cost[b], R * nV, "held costs")) return rc;
+            if (int rc = alloc_rep(vcc[b], R * nV, "own costs")) return rc;
         }
         h_rank = rk;
-        MXS_TRY(grec.alloc(nV));
-        MXS_TRY(has_cost.alloc(nV));
+        if (int rc = alloc_rep(grec, R * nV, "gain records")) return rc;
+        if (int rc = alloc_rep(has_cost, R * nV, "cost flags")) return rc;
+        if (int rc = alloc_rep(part_cost, R * cost_blocks, "cost partials")) return rc;
+        if (int rc = alloc_rep(part_viol, R * cost_blocks, "cost partials")) return rc;
+        if (int rc = alloc_rep(rep_cost, R, "costs")) return rc;
+        if (int rc = alloc_rep(rep_viol, R, "costs")) return rc;
         g.n_vars = nV;
         g.is_max = p.mode == MXS_MODE_MAX;
+        g.n_rep = n_rep;
+        g.bpr = 1;
+        g.seeds = seeds.p;
         g.dom_size = dom_size.p; g.factor_rowptr = factor_rowptr.p; g.edge_var = edge_var.p;
         g.edge_factor = edge_factor.p; g.var_rowptr = var_rowptr.p; g.var_edges = var_edges.p;
         g.init_idx = nullptr; g.name_rank = name_rank.p; g.n_neigh = n_neigh.p;
@@ -540,38 +754,74 @@ struct Engine : Base {
         return reset();
     }
 
+    // every replica back to its start state (k_mgm_init): what is uploaded does not grow with the replicas
     int reset() override {
         MXS_TRY(hipSetDevice(device));
         const int nV = g.n_vars;
-        std::vector<int32_t> c0(nV);  // (all in packed order, Dev::q)
-        std::vector<T> k0(nV, (T)0), v0(nV, (T)0);
-        std::vector<uint8_t> h0(nV, 0);
-        std::vector<GainRec<T>> gr(nV);  // no gain yet, the "new value" is the initial one
-        for (int v = 0; v < nV; ++v) {
-            const int qv = h_q[v];
+        std::vector<int32_t> v0(nV, -1);
+        std::vector<T> k0(nV, (T)0);
+        for (int v = 0; v < nV; ++v)
             if (h_nn[v] == 0) {  // on_start without neighbours: optimal_cost_value (mgm.py:279-290)
-                const int best = hg.optimal_cost_value<T>(v, g.is_max, h_vrank);
-                c0[qv] = best;
-                k0[qv] = (T)hg.var_cost[hg.coff[v] + best];
-                h0[qv] = 1;
-            } else {  // the initial value, else the first of the domain (random.choice fixed)
-                c0[qv] = hg.init[v] >= 0 ? hg.init[v] : 0;
+                v0[v] = hg.optimal_cost_value<T>(v, g.is_max, h_vrank);
+                k0[v] = (T)hg.var_cost[hg.coff[v] + v0[v]];
             }
-            v0[qv] = (T)hg.var_cost[hg.coff[v] + c0[qv]];
-            gr[qv] = GainRec<T>{(T)0, c0[qv], h_rank[v]};
-        }
         which = 0;
-        if (nV) {
-            for (int b = 0; b < 2; ++b) {  // both buffers: the packed launches write only the variables with neighbours
-                MXS_TRY(hipMemcpyAsync(cur[b].p, c0.data(), 4 * nV, hipMemcpyHostToDevice, stream));
-                MXS_TRY(hipMemcpyAsync(cost[b].p, k0.data(), sizeof(T) * nV, hipMemcpyHostToDevice, stream));
-                MXS_TRY(hipMemcpyAsync(vcc[b].p, v0.data(), sizeof(T) * nV, hipMemcpyHostToDevice, stream));
-            }
-            MXS_TRY(hipMemcpyAsync(has_cost.p, h0.data(), nV, hipMemcpyHostToDevice, stream));
-            MXS_TRY(hipMemcpyAsync(grec.p, gr.data(), sizeof(GainRec<T>) * nV, hipMemcpyHostToDevice, stream));
-            MXS_TRY(hipStreamSynchronize(stream));
-        }
         rounds = 0;
+        if (nV) {
+            MXS_TRY(hipMemcpyAsync(iso_val.p, v0.data(), 4 * (size_t)nV, hipMemcpyHostToDevice, stream));
+            MXS_TRY(hipMemcpyAsync(iso_cost.p, k0.data(), sizeof(T) * (size_t)nV, hipMemcpyHostToDevice, stream));
+            g.bpr = blocks_of(nV, AUX_TPB);
+            const dim3 grid((unsigned)(g.bpr * n_rep)), block(AUX_TPB);
+            hipLaunchKernelGGL((k_mgm_init<T>), grid, block, 0, stream, g, keyed ? 1 : 0, (const int32_t*)iso_val.p,
+                               (const T*)iso_cost.p, (const int32_t*)init_idx.p, cur[0].p, cur[1].p, cost[0].p, cost[1].p,
+                               vcc[0].p, vcc[1].p);
+            MXS_TRY(hipGetLastError());
+            MXS_TRY(hipStreamSynchronize(stream));  // (v0 / k0 leave scope)
+        }
+        return MXS_OK;
+    }
+
+    // the four launches of one round (packed plus rest, or thread per variable alone).  <false, false>: the
+    // fixed-draw engine, kernels on the plain Dev; REP: all replicas, the replica folded into the grid
+    template <bool REP, bool KEYED>
+    int launch_round(bool packed, bool generic) {
+        const int nV = g.n_vars;
+        T* const cw = cost[which].p;
+        g.var_list = packed ? pk.rest.p : nullptr;
+        g.n_list = packed ? pk.n_rest : nV;
+        const int pbpr = blocks_of(g.pack.n_lanes, PACK_TPB), bpr = blocks_of(g.n_list, TPB);
+        const unsigned reps = REP ? (unsigned)n_rep : 1u;
+        const dim3 pgrid((unsigned)pbpr * reps), pblock(PACK_TPB);
+        const dim3 grid((unsigned)bpr * reps), block(TPB);
+        // (a kernel takes its Dev by value: the copy is made at the launch, bpr may change between them)
+        DevOf<T, REP, KEYED>& gg = g;       // what the gain kernels take
+        DevOf<T, REP, false>& gm = g;       // what the move kernels take
+        if (packed) {
+            g.bpr = pbpr;
+            if (pk.int8) hipLaunchKernelGGL((k_mgm_gain_pack<T, int8_t, REP, KEYED>), pgrid, pblock, 0, stream, gg, cw);
+            else hipLaunchKernelGGL((k_mgm_gain_pack<T, T, REP, KEYED>), pgrid, pblock, 0, stream, gg, cw);
+            MXS_TRY(hipGetLastError());
+        }
+        if (g.n_list > 0) {
+            g.bpr = bpr;
+            if (generic || max_dom > 32) hipLaunchKernelGGL((k_mgm_gain<T, REP, KEYED>), grid, block, 0, stream, gg, cw);
+            else if (max_dom <= 4) hipLaunchKernelGGL((k_mgm_gain_slots<T, 4, REP, KEYED>), grid, block, 0, stream, gg, cw);
+            else if (max_dom <= 8) hipLaunchKernelGGL((k_mgm_gain_slots<T, 8, REP, KEYED>), grid, block, 0, stream, gg, cw);
+            else if (max_dom <= 16) hipLaunchKernelGGL((k_mgm_gain_slots<T, 16, REP, KEYED>), grid, block, 0, stream, gg, cw);
+            else hipLaunchKernelGGL((k_mgm_gain_slots<T, 32, REP, KEYED>), grid, block, 0, stream, gg, cw);
+            MXS_TRY(hipGetLastError());
+        }
+        if (packed) {
+            g.bpr = pbpr;
+            hipLaunchKernelGGL((k_mgm_move_pack<T, REP>), pgrid, pblock, 0, stream, gm);
+            MXS_TRY(hipGetLastError());
+        }
+        if (g.n_list > 0) {
+            g.bpr = bpr;
+            if (generic) hipLaunchKernelGGL((k_mgm_move<T, REP>), grid, block, 0, stream, gm);
+            else hipLaunchKernelGGL((k_mgm_move_listed<T, REP>), grid, block, 0, stream, gm);
+            MXS_TRY(hipGetLastError());
+        }
         return MXS_OK;
     }
 
@@ -585,7 +835,6 @@ struct Engine : Base {
         const char* env = std::getenv("MAXSUM_LOCAL_SEARCH_GENERIC");  // =1: the CSR-walk kernels, =2: the slot
         const bool generic = env && env[0] == '1';                     // kernels for every variable (A/B, tests)
         const bool packed = !generic && !(env && env[0] == '2') && g.pack.n_lanes > 0;
-        const dim3 pgrid((unsigned)((g.pack.n_lanes + PACK_TPB - 1) / PACK_TPB)), pblock(PACK_TPB);
         for (int32_t r = 0; r < n; ++r) {
             g.cur = cur[which].p;
             g.cost = cost[which].p;
@@ -593,32 +842,12 @@ struct Engine : Base {
             g.cost_out = cost[which ^ 1].p;
             g.vcc = vcc[which].p;
             g.vcc_out = vcc[which ^ 1].p;
-            T* const cw = cost[which].p;
-            g.var_list = packed ? pk.rest.p : nullptr;
-            g.n_list = packed ? pk.n_rest : nV;
-            const dim3 grid((unsigned)((g.n_list + TPB - 1) / TPB)), block(TPB);
-            if (packed) {
-                if (pk.int8) hipLaunchKernelGGL((k_mgm_gain_pack<T, int8_t>), pgrid, pblock, 0, stream, g, cw);
-                else hipLaunchKernelGGL((k_mgm_gain_pack<T, T>), pgrid, pblock, 0, stream, g, cw);
-                MXS_TRY(hipGetLastError());
-            }
-            if (g.n_list > 0) {
-                if (generic || max_dom > 32) hipLaunchKernelGGL((k_mgm_gain<T>), grid, block, 0, stream, g, cw);
-                else if (max_dom <= 4) hipLaunchKernelGGL((k_mgm_gain_slots<T, 4>), grid, block, 0, stream, g, cw);
-                else if (max_dom <= 8) hipLaunchKernelGGL((k_mgm_gain_slots<T, 8>), grid, block, 0, stream, g, cw);
-                else if (max_dom <= 16) hipLaunchKernelGGL((k_mgm_gain_slots<T, 16>), grid, block, 0, stream, g, cw);
-                else hipLaunchKernelGGL((k_mgm_gain_slots<T, 32>), grid, block, 0, stream, g, cw);
-                MXS_TRY(hipGetLastError());
-            }
-            if (packed) {
-                hipLaunchKernelGGL((k_mgm_move_pack<T>), pgrid, pblock, 0, stream, g);
-                MXS_TRY(hipGetLastError());
-            }
-            if (g.n_list > 0) {
-                if (generic) hipLaunchKernelGGL((k_mgm_move<T>), grid, block, 0, stream, g);
-                else hipLaunchKernelGGL((k_mgm_move_listed<T>), grid, block, 0, stream, g);
-                MXS_TRY(hipGetLastError());
-            }
+            g.round = rounds + 1;  // the reference's cycle_count while it handles this round's values
+            int rc;
+            if (!keyed) rc = launch_round<false, false>(packed, generic);
+            else if (n_rep == 1) rc = launch_round<false, true>(packed, generic);
+            else rc = launch_round<true, true>(packed, generic);
+            if (rc) return rc;
             which ^= 1;
             rounds += 1;
         }
@@ -626,7 +855,8 @@ struct Engine : Base {
         return MXS_OK;
     }
 
-    int get_state(int32_t* idx, double* cst, uint8_t* has, double* gn, int32_t* nv) override {
+    int get_state(int32_t r, int32_t* idx, double* cst, uint8_t* has, double* gn, int32_t* nv) override {
+        if (r < 0 || r >= n_rep) return fail(MXS_E_INVALID, "replica out of range");
         MXS_TRY(hipSetDevice(device));
         const int nV = g.n_vars;
         if (!nV) return MXS_OK;
@@ -634,10 +864,11 @@ struct Engine : Base {
         std::vector<GainRec<T>> hg(nV);
         std::vector<int32_t> hi(nV);
         std::vector<uint8_t> hh(nV);
-        MXS_TRY(hipMemcpyAsync(hi.data(), cur[which].p, 4 * nV, hipMemcpyDeviceToHost, stream));
-        MXS_TRY(hipMemcpyAsync(hh.data(), has_cost.p, nV, hipMemcpyDeviceToHost, stream));
-        MXS_TRY(hipMemcpyAsync(hc.data(), cost[which].p, sizeof(T) * nV, hipMemcpyDeviceToHost, stream));
-        MXS_TRY(hipMemcpyAsync(hg.data(), grec.p, sizeof(GainRec<T>) * nV, hipMemcpyDeviceToHost, stream));
+        const size_t roff = (size_t)r * nV;
+        MXS_TRY(hipMemcpyAsync(hi.data(), cur[which].p + roff, 4 * (size_t)nV, hipMemcpyDeviceToHost, stream));
+        MXS_TRY(hipMemcpyAsync(hh.data(), has_cost.p + roff, nV, hipMemcpyDeviceToHost, stream));
+        MXS_TRY(hipMemcpyAsync(hc.data(), cost[which].p + roff, sizeof(T) * (size_t)nV, hipMemcpyDeviceToHost, stream));
+        MXS_TRY(hipMemcpyAsync(hg.data(), grec.p + roff, sizeof(GainRec<T>) * (size_t)nV, hipMemcpyDeviceToHost, stream));
         MXS_TRY(hipStreamSynchronize(stream));
         for (int v = 0; v < nV; ++v) {  // the state lives in packed order (Dev::q)
             const int qv = h_q[v];
@@ -652,13 +883,55 @@ struct Engine : Base {
 
     int eval_cost(const int32_t* idx, double infinity, double* cst, int64_t* viol) override {
         std::vector<int32_t> c;
-        if (!idx) {
+        if (!idx) {  // replica 0
             c.resize(g.n_vars);
-            int rc = get_state(c.data(), nullptr, nullptr, nullptr, nullptr);
+            int rc = get_state(0, c.data(), nullptr, nullptr, nullptr, nullptr);
             if (rc) return rc;
             idx = c.data();
         }
         return hg.eval_cost(idx, infinity, cst, viol);
+    }
+
+    // the costs of the replicas' current assignments (replica_cost.h), fetched
+    int device_costs(double infinity, std::vector<double>& hc, std::vector<long long>& hv) {
+        MXS_TRY(hipSetDevice(device));
+        g.bpr = cost_blocks;
+        const repcost::CostArgs a{cur[which].p, cost_off.p, evc.p, hg.nF, infinity, part_cost.p, part_viol.p};
+        hipLaunchKernelGGL((repcost::k_cost_partial<DevR<T>>), dim3((unsigned)(cost_blocks * n_rep)), dim3(repcost::COST_TPB), 0,
+                           stream, g, a);
+        MXS_TRY(hipGetLastError());
+        hipLaunchKernelGGL((repcost::k_cost_final<repcost::BestRec>), dim3((unsigned)blocks_of(n_rep, 64)), dim3(64), 0, stream,
+                           (int)n_rep, cost_blocks, (int)g.is_max, (const double*)part_cost.p, (const long long*)part_viol.p,
+                           rep_cost.p, rep_viol.p, 0, repcost::BestRec{});
+        MXS_TRY(hipGetLastError());
+        hc.resize(n_rep), hv.resize(n_rep);
+        MXS_TRY(hipMemcpyAsync(hc.data(), rep_cost.p, 8 * (size_t)n_rep, hipMemcpyDeviceToHost, stream));
+        MXS_TRY(hipMemcpyAsync(hv.data(), rep_viol.p, 8 * (size_t)n_rep, hipMemcpyDeviceToHost, stream));
+        MXS_TRY(hipStreamSynchronize(stream));
+        return MXS_OK;
+    }
+
+    int replica_costs(double infinity, double* cst, int64_t* viol) override {
+        std::vector<double> hc;
+        std::vector<long long> hv;
+        if (int rc = device_costs(infinity, hc, hv)) return rc;
+        for (int r = 0; r < n_rep; ++r) {
+            if (cst) cst[r] = hc[r];
+            if (viol) viol[r] = (int64_t)hv[r];
+        }
+        return MXS_OK;
+    }
+
+    // MGM's own sum never rises: a run's final state is its best, the final states are ranked
+    int best_replica(double infinity, int32_t* replica, double* cst, int64_t* viol) override {
+        std::vector<double> hc;
+        std::vector<long long> hv;
+        if (int rc = device_costs(infinity, hc, hv)) return rc;
+        const int r = repcost::best_replica(n_rep, g.is_max, hc.data(), hv.data());
+        if (replica) *replica = r;
+        if (cst) *cst = hc[r];
+        if (viol) *viol = (int64_t)hv[r];
+        return MXS_OK;
     }
 };
 
@@ -671,7 +944,16 @@ struct mxs_mgm {
 extern "C" {
 
 int mxs_mgm_create(const mxs_graph* g, const mxs_params* p, const int32_t* name_rank, int32_t device, mxs_mgm** out) {
-    return mxs_host::create<mxs_mgm, mgm::Engine>(g, p, out, name_rank, device);
+    return mxs_host::create<mxs_mgm, mgm::Engine>(g, p, out, name_rank, false, (const uint64_t*)nullptr, 1, device);
+}
+int mxs_mgm_create_keyed(const mxs_graph* g, const mxs_params* p, const int32_t* name_rank, const uint64_t* seeds,
+                         int32_t n_replicas, int32_t device, mxs_mgm** out) {
+    return mxs_host::create<mxs_mgm, mgm::Engine>(g, p, out, name_rank, true, seeds, n_replicas, device);
+}
+int mxs_mgm_replicas(const mxs_mgm* e, int32_t* n) {
+    if (!e) return mxs_host::fail(MXS_E_INVALID, "null handle");
+    if (n) *n = e->impl->n_rep;
+    return MXS_OK;
 }
 int mxs_mgm_reset(mxs_mgm* e) { return e ? e->impl->reset() : mxs_host::fail(MXS_E_INVALID, "null handle"); }
 int mxs_mgm_set_value_rank(mxs_mgm* e, const int32_t* value_rank) {
@@ -688,7 +970,17 @@ int mxs_mgm_rounds(const mxs_mgm* e, int64_t* rounds) {
     return MXS_OK;
 }
 int mxs_mgm_get_state(mxs_mgm* e, int32_t* idx, double* cost, uint8_t* has_cost, double* gain, int32_t* new_value) {
-    return e ? e->impl->get_state(idx, cost, has_cost, gain, new_value) : mxs_host::fail(MXS_E_INVALID, "null handle");
+    return e ? e->impl->get_state(0, idx, cost, has_cost, gain, new_value) : mxs_host::fail(MXS_E_INVALID, "null handle");
+}
+int mxs_mgm_get_state_replica(mxs_mgm* e, int32_t r, int32_t* idx, double* cost, uint8_t* has_cost, double* gain,
+                              int32_t* new_value) {
+    return e ? e->impl->get_state(r, idx, cost, has_cost, gain, new_value) : mxs_host::fail(MXS_E_INVALID, "null handle");
+}
+int mxs_mgm_replica_costs(mxs_mgm* e, double infinity, double* cost, int64_t* violations) {
+    return e ? e->impl->replica_costs(infinity, cost, violations) : mxs_host::fail(MXS_E_INVALID, "null handle");
+}
+int mxs_mgm_best_replica(mxs_mgm* e, double infinity, int32_t* replica, double* cost, int64_t* violations) {
+    return e ? e->impl->best_replica(infinity, replica, cost, violations) : mxs_host::fail(MXS_E_INVALID, "null handle");
 }
 int mxs_mgm_eval_cost(mxs_mgm* e, const int32_t* idx, double infinity, double* cost, int64_t* violations) {
     return e ? e->impl->eval_cost(idx, infinity, cost, violations) : mxs_host::fail(MXS_E_INVALID, "null handle");

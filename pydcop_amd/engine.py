@@ -49,6 +49,7 @@ ABI_SYMBOLS = (
     "mxs_amaxsum_eval_cost", "mxs_amaxsum_update_factor_table", "mxs_amaxsum_destroy",
     "mxs_mgm_create", "mxs_mgm_reset", "mxs_mgm_set_value_rank", "mxs_mgm_run", "mxs_mgm_rounds", "mxs_mgm_get_state",
     "mxs_mgm_eval_cost", "mxs_mgm_destroy",
+    "mxs_mgm_create_keyed", "mxs_mgm_replicas", "mxs_mgm_get_state_replica", "mxs_mgm_replica_costs", "mxs_mgm_best_replica",
     "mxs_dsa_create", "mxs_dsa_reset", "mxs_dsa_set_value_rank", "mxs_dsa_run", "mxs_dsa_cycles", "mxs_dsa_get_state",
     "mxs_dsa_eval_cost", "mxs_dsa_destroy",
     "mxs_dsa_create_replicas", "mxs_dsa_replicas", "mxs_dsa_get_state_replica", "mxs_dsa_replica_costs",
@@ -262,6 +263,20 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
         fn = getattr(lib, name)  # AttributeError if the library misses a symbol
         fn.argtypes = argtypes
         fn.restype = restype
+    # added without a new mxs_version: a library built from older sources still loads, MgmEngine(draws="keyed")
+    # then says what is missing (pydcop_amd/mgm.py)
+    later = {
+        "mxs_mgm_create_keyed": ([C.POINTER(CGraph), C.POINTER(CParams), vp, vp, i32, i32, C.POINTER(vp)], C.c_int),
+        "mxs_mgm_replicas": ([vp, C.POINTER(i32)], C.c_int),
+        "mxs_mgm_get_state_replica": ([vp, i32, vp, vp, vp, vp, vp], C.c_int),
+        "mxs_mgm_replica_costs": ([vp, C.c_double, vp, vp], C.c_int),
+        "mxs_mgm_best_replica": ([vp, C.c_double, C.POINTER(i32), C.POINTER(C.c_double), C.POINTER(i64)], C.c_int),
+    }
+    for name, (argtypes, restype) in later.items():
+        fn = getattr(lib, name, None)
+        if fn is not None:
+            fn.argtypes = argtypes
+            fn.restype = restype
     _libs[path] = lib
     return lib
 

@@ -2,13 +2,17 @@
 (include/maxsum_gpu.h; device code: pydcop_amd/csrc/mgm.hip) on the same FlatGraph as the Max-Sum
 engine -- factors are the constraints, variables the MGM computations.  No CPU fallback."""
 import ctypes as C
-from typing import Optional, Tuple
+from typing import Dict, Optional, Sequence, Tuple
 
 import numpy as np
 
 from ._binding import EngineBinding
-from .engine import load_library
+from .engine import MaxSumGpuError, load_library
 from .graph import FlatGraph, Params
+
+DRAWS = ("fixed", "keyed")
+KEYED_SYMBOLS = ("mxs_mgm_create_keyed", "mxs_mgm_replicas", "mxs_mgm_get_state_replica", "mxs_mgm_replica_costs",
+                 "mxs_mgm_best_replica")
 
 
 def name_ranks(names) -> np.ndarray:
@@ -24,21 +28,52 @@ class MgmEngine(EngineBinding):
     """>>> eng = MgmEngine(graph, Params(mode="min"))   # every computation started
     >>> eng.run(30)                                    # 30 rounds (= the reference's stop_cycle 31)
     >>> idx, cost = eng.assignment()
+
+    `draws="fixed"` (the default) fixes the reference's two draws from the unseeded `random`: first domain value at
+    start, first of equally good values.  `draws="keyed"` takes them from the counter-based generator DSA uses, keyed
+    on (seed, variable, cycle, draw): draw 10 the start value of a variable that has no initial value, draw 11 one of
+    the best values when the gain improves.  `replicas=R` (keyed only): R seeded runs of the instance in one engine
+    (seeds `seed + r` modulo 2**64, or `seeds`), advanced by the same launches over one copy of the tables; replica
+    r is bit for bit the keyed engine with that seed.  MGM's own sum never rises, so a run's final state is its best.
+    >>> eng = MgmEngine(graph, draws="keyed", replicas=8, seed=5)
+    >>> eng.run(30)
+    >>> eng.best(infinity=10000)                       # the best replica's final state
     """
     PREFIX = "mxs_mgm"
     COUNTER = "rounds"
 
     def __init__(self, graph: FlatGraph, params: Optional[Params] = None, device: int = 0,
-                 lib_path: Optional[str] = None):
+                 lib_path: Optional[str] = None, draws: str = "fixed", seed: int = 0,
+                 seeds: Optional[Sequence[int]] = None, replicas: int = 1):
+        if draws not in DRAWS:
+            raise ValueError(f"Invalid value {draws!r} for parameter draws, must be one of {list(DRAWS)}")
+        if draws == "fixed" and (int(replicas) != 1 or seeds is not None):
+            raise ValueError("replicas / seeds need draws=\"keyed\": with the fixed draws every run is the same run")
+        if seeds is None:
+            seeds = [int(seed) + r for r in range(int(replicas))]
+        elif replicas not in (1, len(seeds)):
+            raise ValueError(f"{len(seeds)} seeds for {replicas} replicas")
         self._lib = load_library(lib_path)
         self.graph = graph
         self.params = params or Params()
+        self.draws = draws
+        self.seeds = [int(x) & (2 ** 64 - 1) for x in seeds]
+        self.replicas = len(self.seeds)
         cg, cp = graph.to_c(), self.params.to_c()
         self._rank = name_ranks(graph.var_names) if graph.var_names else None
+        rank = None if self._rank is None else self._rank.ctypes.data
         h = C.c_void_p()
-        self._check(self._lib.mxs_mgm_create(C.byref(cg), C.byref(cp),
-                                             None if self._rank is None else self._rank.ctypes.data,
-                                             int(device), C.byref(h)))
+        if draws == "fixed":
+            self._check(self._lib.mxs_mgm_create(C.byref(cg), C.byref(cp), rank, int(device), C.byref(h)))
+        else:
+            missing = [n for n in KEYED_SYMBOLS if not hasattr(self._lib, n)]
+            if missing:
+                raise MaxSumGpuError(
+                    f"{self._lib._name} was built from sources without MGM's keyed draws (no {', '.join(missing)}): "
+                    "rebuild the library, draws=\"keyed\" needs them")
+            sd = np.array(self.seeds, dtype=np.uint64)
+            self._check(self._lib.mxs_mgm_create_keyed(C.byref(cg), C.byref(cp), rank, sd.ctypes.data, self.replicas,
+                                                       int(device), C.byref(h)))
         self._h = h
         # cost ties of a variable without neighbours break on the domain VALUE (relations.py:1661-1665):
         # only needed when some domain is not written in ascending order
@@ -52,13 +87,39 @@ class MgmEngine(EngineBinding):
     def run(self, n_rounds: int):
         self._call("run", int(n_rounds))
 
-    def state(self) -> dict:
+    def state(self, replica: int = 0) -> dict:
         n = self.graph.n_vars
         out = {"idx": np.empty(n, dtype=np.int32), "cost": np.empty(n), "has_cost": np.empty(n, dtype=np.uint8),
                "gain": np.empty(n), "new": np.empty(n, dtype=np.int32)}
-        self._call("get_state", *[out[k].ctypes.data for k in ("idx", "cost", "has_cost", "gain", "new")])
+        ptrs = [out[k].ctypes.data for k in ("idx", "cost", "has_cost", "gain", "new")]
+        if int(replica) == 0:       # (the call every version of the library has)
+            self._call("get_state", *ptrs)
+        else:
+            self._call("get_state_replica", int(replica), *ptrs)
         return out
 
-    def assignment(self) -> Tuple[np.ndarray, np.ndarray]:
-        s = self.state()
+    def assignment(self, replica: int = 0) -> Tuple[np.ndarray, np.ndarray]:
+        s = self.state(replica)
         return s["idx"], s["cost"]
+
+    def _keyed_only(self, what):
+        if self.draws != "keyed":
+            raise ValueError(f"{what} needs draws=\"keyed\"")
+
+    def replica_costs(self, infinity: float = float("inf")) -> Tuple[np.ndarray, np.ndarray]:
+        """(cost[R], violations[R]) of the replicas' current assignments, reduced on the device: what
+        `eval_cost(assignment(r)[0], infinity)` gives, in a fixed summation order of its own."""
+        self._keyed_only("replica_costs")
+        cost = np.empty(self.replicas)
+        viol = np.empty(self.replicas, dtype=np.int64)
+        self._call("replica_costs", float(infinity), cost.ctypes.data, viol.ctypes.data)
+        return cost, viol
+
+    def best(self, infinity: float = float("inf")) -> Dict:
+        """The best replica's current state -- fewest violations, then best cost, then lowest index, ranked on the
+        device: {"replica", "cost", "violations", "idx"}."""
+        self._keyed_only("best")
+        r, cost, viol = C.c_int32(0), C.c_double(0), C.c_int64(0)
+        self._call("best_replica", float(infinity), C.byref(r), C.byref(cost), C.byref(viol))
+        return {"replica": int(r.value), "cost": float(cost.value), "violations": int(viol.value),
+                "idx": self.state(int(r.value))["idx"]}

@@ -25,6 +25,13 @@ device cost reduction (`replica_costs`) against R host `eval_cost` calls with th
 is this library's engine ("baseline": "this") or, with `--baseline-lib PATH`, the `mxs_dsa_create` of another build
 of the library -- e.g. the parent commit's, built from `git archive <commit> pydcop_amd/csrc include` with the
 csrc Makefile -- loaded beside this one ("baseline": its mxs_version).
+`--replica-algos` (default: dsa mgm) chooses whose rows are printed.  The MGM rows ("algo": "mgm", MgmEngine(draws="keyed",
+replicas=R), mgm.hip) follow the same protocol, the single side being the fixed-draw engine (`mxs_mgm_create` of this
+library or of `--baseline-lib`: a keyed single run costs the same per round); before them, per size, two rows without
+replicas: "fixed_vs_baseline" (this library's fixed-draw engine against the single side: the same kernel
+instantiations) and "keyed_vs_fixed" (the keyed one-replica engine against the fixed-draw one: what the draw code
+costs; MGM reaches its fixed point after a few rounds, where draw 11 is no longer made, so the row also times the
+first 12 rounds after reset(), "fresh_us_per_round").
 """
 import argparse
 import json
@@ -105,6 +112,33 @@ class BaselineDsa:
         self._lib.mxs_dsa_destroy(self._h)
 
 
+class BaselineMgm:
+    """The fixed-draw MGM engine of ANOTHER build of the library (--baseline-lib): mxs_mgm_create / _run / _destroy."""
+
+    def __init__(self, path, g, p):
+        import ctypes as C
+        from pydcop_amd.engine import load_library
+        load_library()                       # (the HIP runtime first: the libraries are linked without it)
+        self._lib = C.CDLL(os.path.abspath(path))
+        self._lib.mxs_version.restype = C.c_int32
+        self.version = int(self._lib.mxs_version())
+        self._lib.mxs_mgm_create.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]
+        self._lib.mxs_mgm_run.argtypes = [C.c_void_p, C.c_int32]
+        self._lib.mxs_mgm_destroy.argtypes = [C.c_void_p]
+        self._g, self._p = g.to_c(), p.to_c()      # (kept alive)
+        self._h = C.c_void_p()
+        rc = self._lib.mxs_mgm_create(C.byref(self._g), C.byref(self._p), None, 0, C.byref(self._h))
+        if rc:
+            raise RuntimeError(f"mxs_mgm_create of {path}: {rc}")
+
+    def run(self, n):
+        if self._lib.mxs_mgm_run(self._h, int(n)):
+            raise RuntimeError("mxs_mgm_run of the baseline library failed")
+
+    def close(self):
+        self._lib.mxs_mgm_destroy(self._h)
+
+
 def timed_us(eng, cycles):
     t0 = time.perf_counter()
     eng.run(cycles)
@@ -163,6 +197,80 @@ def replica_rows(a):
             single.close()
 
 
+def alternated(a, left, right):
+    """both engines warmed up, then `repeats` alternated windows: (us per round of left, of right)"""
+    n_left, n_right = cycles_for(left, a.window, a.warmup), cycles_for(right, a.window, a.warmup)
+    one, other = [], []
+    for _ in range(a.repeats):
+        one.append(round(timed_us(left, n_left), 2))
+        other.append(round(timed_us(right, n_right), 2))
+    return one, other
+
+
+def median(xs):
+    return sorted(xs)[len(xs) // 2]
+
+
+def mgm_replica_rows(a):
+    for n_vars in a.replica_sizes:
+        g = G.random_coloring(n_vars, seed=0, names=False)
+        p = Params()
+
+        def single_side():
+            if a.baseline_lib:
+                e = BaselineMgm(a.baseline_lib, g, p)
+                return e, f"mxs_version {e.version}"
+            return MgmEngine(g, p, lib_path=a.lib), "this"
+
+        base = {"algo": "mgm", "instance": f"coloring_{n_vars}", "dtype": "f64", "n_vars": n_vars}
+        # the fixed-draw engine of this library against the single side
+        single, baseline = single_side()
+        fixed = MgmEngine(g, p, lib_path=a.lib)
+        one, mine = alternated(a, single, fixed)
+        print(json.dumps(dict(base, row="fixed_vs_baseline", baseline=baseline, single_us_per_round=one,
+                              fixed_us_per_round=mine, ratio_fixed_to_single=round(median(mine) / median(one), 4))), flush=True)
+        single.close()
+        # the keyed one-replica engine against the fixed-draw one
+        keyed = MgmEngine(g, p, draws="keyed", seed=1, lib_path=a.lib)
+        f_us, k_us = alternated(a, fixed, keyed)
+        fresh = {}
+        for name, eng in (("fixed", fixed), ("keyed", keyed)):
+            ts = []
+            for _ in range(a.repeats):
+                total = 0.0
+                for _ in range(40):
+                    eng.reset()
+                    t0 = time.perf_counter()
+                    eng.run(12)
+                    total += time.perf_counter() - t0
+                ts.append(round(1e6 * total / (40 * 12), 2))
+            fresh[name] = ts
+        print(json.dumps(dict(base, row="keyed_vs_fixed", fixed_us_per_round=f_us, keyed_us_per_round=k_us,
+                              ratio_keyed_to_fixed=round(median(k_us) / median(f_us), 4),
+                              fresh_us_per_round=fresh)), flush=True)
+        fixed.close(), keyed.close()
+        for R in a.replicas:
+            single, baseline = single_side()
+            eng = MgmEngine(g, p, draws="keyed", seed=1, replicas=R, lib_path=a.lib)
+            one, many = alternated(a, single, eng)
+            row = dict(base, row="replicas", replicas=R, baseline=baseline, single_us_per_round=one,
+                       replicas_us_per_round=many, ratio_R_singles_to_replicas=round(R * median(one) / median(many), 2))
+            reps = max(3, int(0.2 * a.window * 1e6 / max(many[0], 1.0)))
+            t0 = time.perf_counter()
+            for _ in range(reps):
+                dev = eng.replica_costs()
+            row["replica_costs_us"] = round(1e6 * (time.perf_counter() - t0) / reps, 1)
+            reps = max(1, min(reps, 2000 // R))
+            t0 = time.perf_counter()
+            for _ in range(reps):
+                host = [eng.eval_cost(eng.assignment(r)[0]) for r in range(R)]
+            row["host_eval_cost_us"] = round(1e6 * (time.perf_counter() - t0) / reps, 1)
+            assert all(abs(dev[0][r] - host[r][0]) <= 1e-9 * max(1.0, abs(host[r][0])) for r in range(R))
+            print(json.dumps(row), flush=True)
+            eng.close()
+            single.close()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--cycles", type=int, default=500)
@@ -172,16 +280,21 @@ def main():
     ap.add_argument("--mgm2-rounds", type=int, default=200, help="0: no MGM-2 rows")
     ap.add_argument("--gdba-rounds", type=int, default=200, help="0: no GDBA rows")
     ap.add_argument("--dba-rounds", type=int, default=0, help="> 0: only the DBA / GDBA-T / MGM rows on the hard colouring")
-    ap.add_argument("--replicas", type=int, nargs="*", default=[], help="the DSA replica rows only: R values")
+    ap.add_argument("--replicas", type=int, nargs="*", default=[], help="the replica rows only (DSA, MGM): R values")
     ap.add_argument("--replica-sizes", type=int, nargs="*", default=[1000, 10_000, 100_000])
     ap.add_argument("--window", type=float, default=1.0, help="seconds per timed window of the replica rows")
     ap.add_argument("--repeats", type=int, default=3)
     ap.add_argument("--warmup", type=float, default=0.5, help="seconds of warm-up per engine of the replica rows")
     ap.add_argument("--baseline-lib", default=None,
                     help="replica rows: the single-seed side from this other build of the library (mxs_dsa_create)")
+    ap.add_argument("--replica-algos", nargs="*", default=["dsa", "mgm"], choices=["dsa", "mgm"])
     a = ap.parse_args()
     if a.replicas:
-        return replica_rows(a)
+        if "dsa" in a.replica_algos:
+            replica_rows(a)
+        if "mgm" in a.replica_algos:
+            mgm_replica_rows(a)
+        return
     if a.dba_rounds > 0:
         return dba_rows(a)
     instances = [("coloring_100k", lambda: G.random_coloring(100_000, seed=0, names=False), Params()),
