@@ -1,7 +1,7 @@
 """What the ctypes bindings of the `mxs_dsa_*`, `mxs_mgm_*`, `mxs_mgm2_*`, `mxs_gdba_*`, `mxs_dba_*` and `mxs_dpop_*` entry points
 (include/maxsum_gpu.h) share: the handle, the error check, `eval_cost`, the cycle counter and the life cycle."""
 import ctypes as C
-from typing import Tuple
+from typing import Optional, Sequence, Tuple
 
 import numpy as np
 
@@ -54,3 +54,32 @@ class EngineBinding:
 
     def __exit__(self, *exc):
         self.close()
+
+
+class ReplicaBinding(EngineBinding):
+    """What the bindings of the replica engines (`DsaEngine`, `MgmEngine`: R seeded runs in one engine) share."""
+
+    def _set_seeds(self, seed: int, seeds: Optional[Sequence[int]], replicas: int) -> np.ndarray:
+        """`self.seeds` (`seed + r` modulo 2**64, or `seeds`) and `self.replicas`; the array `<PREFIX>_create_*` takes"""
+        if seeds is None:
+            seeds = [int(seed) + r for r in range(int(replicas))]
+        elif replicas not in (1, len(seeds)):
+            raise ValueError(f"{len(seeds)} seeds for {replicas} replicas")
+        self.seeds = [int(x) & (2 ** 64 - 1) for x in seeds]
+        self.replicas = len(self.seeds)
+        return np.array(self.seeds, dtype=np.uint64)
+
+    def _set_value_rank(self):
+        """cost ties of a variable without neighbours break on the domain VALUE (relations.py:1661-1665):
+        only needed when some domain is not written in ascending order"""
+        self._vrank = self.graph.value_rank()
+        if self._vrank is not None:
+            self._call("set_value_rank", self._vrank.ctypes.data)
+
+    def replica_costs(self, infinity: float = float("inf")) -> Tuple[np.ndarray, np.ndarray]:
+        """(cost[R], violations[R]) of the replicas' current assignments, reduced on the device: what
+        `eval_cost(assignment(r)[0], infinity)` gives, in a fixed summation order of its own."""
+        cost = np.empty(self.replicas)
+        viol = np.empty(self.replicas, dtype=np.int64)
+        self._call("replica_costs", float(infinity), cost.ctypes.data, viol.ctypes.data)
+        return cost, viol

@@ -16,7 +16,10 @@
 // replica, everything a kernel derives from the replica is block-uniform (R = 1 runs instantiations without it).  Replica r is bit for bit the
 // single-seed run with seed seeds[r]; mxs_dsa_create is R = 1 of the same path.  Per replica, the solution
 // cost of the current assignment is reduced on the device (replica_cost.h, shared with mgm.hip: fixed
-// shape, no atomics) and the best state seen can be kept on the device (k_dsa_best_copy).
+// shape, no atomics) and the best state seen can be kept on the device (k_dsa_best_copy).  The host side that does
+// not depend on the algorithm -- set-up, views, uploads, start values, the cost launches -- is rephost::Host
+// (replica_host.h, shared with mgm.hip); this file keeps the kernels, Dev, the per-lane extras, the cycle's
+// launches and the best-state tracking.
 //
 // The reference draws from Python's unseeded `random` module (initial value, move test, choice
 // among the best values).  Here every draw comes from a counter-based generator keyed on (seed,
@@ -39,6 +42,7 @@
 #include "engine_common.h"
 #include "local_search.h"
 #include "replica_cost.h"
+#include "replica_host.h"
 
 namespace dsa {
 
@@ -350,12 +354,10 @@ __global__ void __launch_bounds__(AUX_TPB) k_dsa_init(Dev<T> g, const int32_t* i
     g.cost[at] = iso >= 0 ? iso_cost[v] : (T)0;
 }
 
-// ---- the solution cost of every replica's current assignment: k_cost_partial / k_cost_final of replica_cost.h (one
-// implementation, shared with mgm.hip); BestRec: the best state a replica has shown (mxs_dsa_track_best)
+// ---- the solution cost of every replica's current assignment: k_cost_partial / k_cost_final of replica_cost.h,
+// launched by replica_host.h (one implementation, shared with mgm.hip); BestRec: the best state a replica has
+// shown (mxs_dsa_track_best)
 using repcost::BestRec;
-using repcost::COST_RUN;
-using repcost::COST_TPB;
-using repcost::CostArgs;
 
 // a launch of its own, after k_cost_final in stream order: the replicas that improved copy their state
 // and take the new record (nothing in this launch reads a record)
@@ -373,8 +375,6 @@ __global__ void __launch_bounds__(AUX_TPB) k_dsa_best_copy(int n_vars, int bpr, 
     }
 }
 
-using repcost::MAX_REPLICAS;
-
 struct Base {
     virtual ~Base() {}
     virtual int init(const mxs_graph& G, const mxs_params& p, int variant, double probability, int arity_mode,
@@ -391,35 +391,23 @@ struct Base {
     int32_t n_rep = 1;
 };
 
+using rephost::alloc_rep;
+using rephost::blocks_of;
+static_assert(TPB == rephost::VAR_TPB && PACK_TPB == rephost::PACK_TPB && AUX_TPB == rephost::AUX_TPB,
+              "replica_host.h sizes its grid refusal by these");
+
 template <typename T>
 struct Engine : Base {
-    int device = 0;
-    hipStream_t stream = nullptr;
+    // the stream, the graph, the views, the CSR arrays, the seeds, the start values, the device cost (replica_host.h)
+    rephost::Host<T> rh;
     Dev<T> g{};
     int which = 0;
-    std::vector<uint64_t> h_seeds;
-    mxs_host::HostGraph hg;
-    std::vector<int32_t> h_nn, h_q, h_vrank;
-    Buf<int32_t> dom_size, factor_rowptr, edge_var, edge_factor, var_rowptr, var_edges, n_neigh, qmap;
     Buf<int32_t> cur[2];    // [R][n_vars]
-    Buf<int64_t> table_off;
-    Buf<T> tables, f_opt, cost;
+    Buf<T> f_opt, cost;
     Buf<double> prob;
-    Buf<uint64_t> seeds;
-    mxs_host::DevSlots sl;
-    mxs_host::DevPack<T> pk;
     Buf<uint64_t> pk_key;   // what only DSA keeps per packed variable / lane (Dev::pack_key, pack_prob, pack_fopt)
     Buf<double> pk_prob;
     Buf<T> pk_fopt;
-    int max_dom = 0;
-    // the start state of the variables without neighbours (k_dsa_init)
-    Buf<int32_t> iso_val;
-    Buf<T> iso_cost;
-    // the device cost (k_cost_partial / k_cost_final, replica_cost.h)
-    Buf<int64_t> coff;
-    Buf<double> evc, part_cost, rep_cost;
-    Buf<long long> part_viol, rep_viol;
-    int cost_blocks = 1;
     // the best state (track_best): `tracked`: track_best was called, `every` > 0: records are kept
     bool tracked = false;
     int32_t every = 0;
@@ -428,191 +416,98 @@ struct Engine : Base {
     Buf<long long> best_viol, best_cycle;
     Buf<int32_t> best_improved, best_idx;
 
-    ~Engine() override {
-        if (stream) (void)hipStreamDestroy(stream);
-    }
-
-    // an allocation that grows with the number of replicas: its failure is MXS_E_NOMEM (the caller's
-    // destructor frees what was allocated before)
-    template <typename U>
-    static int alloc_rep(Buf<U>& b, size_t count, const char* what) {
-        if (b.alloc(count) != hipSuccess) {
-            (void)hipGetLastError();
-            b.p = nullptr;
-            b.n = 0;
-            return fail(MXS_E_NOMEM, std::string("out of device memory for the replicas' ") + what);
-        }
-        return MXS_OK;
-    }
-
-    static int blocks_of(int64_t n, int per_block) { return (int)((n + per_block - 1) / per_block); }
-
     int init(const mxs_graph& G, const mxs_params& p, int variant, double probability, int arity_mode,
              const uint64_t* sds, int n_replicas, int dev) override {
-        device = dev;
-        if (n_replicas < 1 || n_replicas > MAX_REPLICAS) return fail(MXS_E_INVALID, "the number of replicas must be in 1 .. 4096");
-        if (!sds) return fail(MXS_E_INVALID, "null seeds");
-        n_rep = n_replicas;
-        h_seeds.assign(sds, sds + n_replicas);
-        if (int rc = mxs_host::open_device(dev, &stream)) return rc;
+        if (int rc = rh.open(sds, n_replicas, dev, true)) return rc;
+        n_rep = rh.n_rep;
         if (variant < 0 || variant > 2) return fail(MXS_E_INVALID, "variant must be 0 (A), 1 (B) or 2 (C)");
-        if (int rc = hg.load(G, p)) return rc;  // (init_idx is not read: the reference's DSA ignores initial values)
+        if (int rc = rh.hg.load(G, p)) return rc;  // (init_idx is not read: the reference's DSA ignores initial values)
+        const mxs_host::HostGraph& hg = rh.hg;
+        const hipStream_t stream = rh.stream;
         const int nV = hg.nV, nF = hg.nF;
         const size_t R = (size_t)n_rep;
-        const std::vector<int32_t> &efac = hg.efac, &vrow = hg.vrow, &vedges = hg.vedges;
-        h_nn.assign(nV, 0);
         std::vector<int64_t> n_count(nV, 0);
-        for (int f = 0; f < nF; ++f) {
-            const int ar = hg.frow[f + 1] - hg.frow[f];
-            for (int e = hg.frow[f]; e < hg.frow[f + 1]; ++e) {
-                if (ar > 1) h_nn[hg.evar[e]] = 1;
-                n_count[hg.evar[e]] += ar - 1;
-            }
-        }
+        for (int f = 0; f < nF; ++f)
+            for (int e = hg.frow[f]; e < hg.frow[f + 1]; ++e) n_count[hg.evar[e]] += hg.frow[f + 1] - hg.frow[f] - 1;
         std::vector<double> pr(nV);
         for (int v = 0; v < nV; ++v)  // p_mode arity: 1 / sum(arity - 1) * 1.2 (dsa.py:256-259)
             pr[v] = (arity_mode && n_count[v] > 0) ? 1.0 / (double)n_count[v] * 1.2 : probability;
-        const std::vector<T> tt = mxs_host::narrowed<T>(hg.tables);
         std::vector<T> fo(nF);
-        for (int f = 0; f < nF; ++f) {  // find_optimum (relations.py:1367-1401): variant B
-            T opt = tt[hg.toff[f]];
-            for (int64_t k = hg.toff[f] + 1; k < hg.toff[f + 1]; ++k)
-                if (p.mode == MXS_MODE_MAX ? tt[k] > opt : tt[k] < opt) opt = tt[k];
+        for (int f = 0; f < nF; ++f) {  // find_optimum (relations.py:1367-1401) of the tables in T: variant B
+            T opt = (T)hg.tables[hg.toff[f]];
+            for (int64_t k = hg.toff[f] + 1; k < hg.toff[f + 1]; ++k) {
+                const T x = (T)hg.tables[k];
+                if (hg.is_max ? x > opt : x < opt) opt = x;
+            }
             fo[f] = opt;
         }
         lsearch::HostSlots hs;
-        const std::string bad = hs.build(nV, nF, hg.dom, hg.frow, hg.evar, hg.toff, vrow, vedges);
-        if (!bad.empty()) return fail(MXS_E_INVALID, bad);
-        max_dom = 0;
-        for (int v = 0; v < nV; ++v) max_dom = hg.dom[v] > max_dom ? hg.dom[v] : max_dom;
-        {   // the packed view of the variables it can take (local_search.h); the others -- constraints of
-            // arity > 2, larger domains, degrees above 64 -- stay on the thread-per-variable kernel
-            lsearch::HostPack hp;
-            hp.build(nV, hg.dom, vrow, h_nn, hs, hg.tables);
-            std::vector<T> fopt_lane(hp.slot.size(), (T)0);
-            for (size_t i = 0; i < hp.slot.size(); ++i)
-                if (hp.slot[i] >= 0) fopt_lane[i] = fo[efac[vedges[hp.slot[i]]]];
-            h_q = mxs_host::packed_order(hp, nV);
-            const size_t nP = hp.vars.size();
-            // every launch folds the replica into blockIdx.x: the largest grid must fit
-            const int64_t most = std::max<int64_t>({blocks_of((int64_t)hp.nb.size(), PACK_TPB), blocks_of(nV, TPB), 1});
-            if (most * (int64_t)n_rep > INT32_MAX) return fail(MXS_E_INVALID, "too many replicas for an instance of this size");
-            std::vector<double> pprob(nP);
-            for (int v : hp.vars) pprob[h_q[v]] = pr[v];
-            if (int rc = pk.upload(hp, h_q, hg.dom, stream)) return rc;
-            MXS_TRY(qmap.upload(h_q, stream));
-            MXS_TRY(pk_prob.upload(pprob, stream));
-            MXS_TRY(pk_fopt.upload(fopt_lane, stream));
-            {   // the keys of the packed variables' draws, per replica
-                std::vector<uint64_t> pkey(R * nP);
-                for (size_t r = 0; r < R; ++r)
-                    for (int v : hp.vars) pkey[r * nP + h_q[v]] = uniform_key(h_seeds[r], v);
-                if (int rc = alloc_rep(pk_key, R * nP, "keys")) return rc;
-                if (!pkey.empty())
-                    MXS_TRY(hipMemcpyAsync(pk_key.p, pkey.data(), 8 * pkey.size(), hipMemcpyHostToDevice, stream));
-                MXS_TRY(hipStreamSynchronize(stream));
-            }
-            if (int rc = sl.upload(hs, stream, &h_q, true)) return rc;
-            sl.upload_rows(hs, hp.rest, hg, max_dom, (int)sizeof(T), stream);
-            g.q = qmap.p;
-            g.pack = pk.view();
-            g.n_pack = (int32_t)nP;
-            g.pack_dom = pk.dom.p;
-            g.pack_key = pk_key.p;
-            g.pack_prob = pk_prob.p;
-            g.pack_fopt = pk_fopt.p;
-        }
-        g.slots = sl.view();
-        MXS_TRY(dom_size.upload(hg.dom, stream));
-        MXS_TRY(factor_rowptr.upload(hg.frow, stream));
-        MXS_TRY(edge_var.upload(hg.evar, stream));
-        MXS_TRY(edge_factor.upload(efac, stream));
-        MXS_TRY(var_rowptr.upload(vrow, stream));
-        MXS_TRY(var_edges.upload(vedges, stream));
-        MXS_TRY(n_neigh.upload(h_nn, stream));
-        MXS_TRY(table_off.upload(hg.toff, stream));
-        MXS_TRY(tables.upload(tt, stream));
+        lsearch::HostPack hp;
+        if (int rc = rh.build_views(hs, hp)) return rc;
+        // DSA's extras: per packed lane the optimum of its constraint, per packed variable its probability and, per
+        // replica, the key of its draws
+        const size_t nP = hp.vars.size();
+        const std::vector<int32_t>& h_q = rh.h_q;
+        std::vector<T> fopt_lane(hp.slot.size(), (T)0);
+        for (size_t i = 0; i < hp.slot.size(); ++i)
+            if (hp.slot[i] >= 0) fopt_lane[i] = fo[hg.efac[hg.vedges[hp.slot[i]]]];
+        std::vector<double> pprob(nP);
+        for (int v : hp.vars) pprob[h_q[v]] = pr[v];
+        MXS_TRY(pk_prob.upload(pprob, stream));
+        MXS_TRY(pk_fopt.upload(fopt_lane, stream));
+        std::vector<uint64_t> pkey(R * nP);
+        for (size_t r = 0; r < R; ++r)
+            for (int v : hp.vars) pkey[r * nP + h_q[v]] = uniform_key(rh.h_seeds[r], v);
+        if (int rc = alloc_rep(pk_key, R * nP, "keys")) return rc;
+        if (!pkey.empty())
+            MXS_TRY(hipMemcpyAsync(pk_key.p, pkey.data(), 8 * pkey.size(), hipMemcpyHostToDevice, stream));
+        MXS_TRY(hipStreamSynchronize(stream));
+        if (int rc = rh.upload_views(hs, hp)) return rc;
+        if (int rc = rh.upload_graph()) return rc;
         MXS_TRY(f_opt.upload(fo, stream));
         MXS_TRY(prob.upload(pr, stream));
-        MXS_TRY(seeds.upload(h_seeds, stream));
-        MXS_TRY(coff.upload(hg.coff, stream));
-        MXS_TRY(evc.upload(hg.eval_var_cost, stream));
-        MXS_TRY(iso_val.alloc(nV));
-        MXS_TRY(iso_cost.alloc(nV));
         for (int b = 0; b < 2; ++b)
             if (int rc = alloc_rep(cur[b], R * nV, "values")) return rc;
         if (int rc = alloc_rep(cost, R * nV, "held costs")) return rc;
-        cost_blocks = std::max(1, blocks_of((int64_t)nF + nV, COST_TPB * COST_RUN));
-        if (int rc = alloc_rep(part_cost, R * cost_blocks, "cost partials")) return rc;
-        if (int rc = alloc_rep(part_viol, R * cost_blocks, "cost partials")) return rc;
-        if (int rc = alloc_rep(rep_cost, R, "costs")) return rc;
-        if (int rc = alloc_rep(rep_viol, R, "costs")) return rc;
-        g.n_vars = nV;
-        g.is_max = p.mode == MXS_MODE_MAX;
+        rh.bind(g);
         g.variant = variant;
-        g.seeds = seeds.p;
-        g.dom_size = dom_size.p; g.factor_rowptr = factor_rowptr.p; g.edge_var = edge_var.p;
-        g.edge_factor = edge_factor.p; g.var_rowptr = var_rowptr.p; g.var_edges = var_edges.p;
-        g.n_neigh = n_neigh.p; g.table_off = table_off.p; g.tables = tables.p; g.f_opt = f_opt.p;
-        g.prob = prob.p; g.cost = cost.p;
+        g.n_pack = (int32_t)nP;
+        g.pack_key = pk_key.p;
+        g.pack_prob = pk_prob.p;
+        g.pack_fopt = pk_fopt.p;
+        g.f_opt = f_opt.p; g.prob = prob.p; g.cost = cost.p;
         return reset();
     }
 
-    // the order of every variable's domain values (include/maxsum_gpu.h): cost ties of a variable without
-    // neighbours break on the value, as the reference's optimal_cost_value does
     int set_value_rank(const int32_t* rank) override {
-        if (rank) h_vrank.assign(rank, rank + hg.coff[g.n_vars]);
-        else h_vrank.clear();
+        rh.set_value_rank(rank);
         return reset();
     }
 
     // every replica back to its start state (k_dsa_init); the records of track_best start again
     int reset() override {
-        MXS_TRY(hipSetDevice(device));
-        const int nV = g.n_vars;
-        std::vector<int32_t> v0(nV, -1);
-        std::vector<T> k0(nV, (T)0);
-        for (int v = 0; v < nV; ++v)
-            if (h_nn[v] == 0) {  // optimal_cost_value (dsa.py:278-289)
-                v0[v] = hg.optimal_cost_value<T>(v, g.is_max, h_vrank);
-                k0[v] = (T)hg.var_cost[hg.coff[v] + v0[v]];
-            }
+        if (int rc = rh.start_values()) return rc;  // optimal_cost_value (dsa.py:278-289)
         which = 0;
         cycles = 0;
-        if (nV) {
-            MXS_TRY(hipMemcpyAsync(iso_val.p, v0.data(), 4 * (size_t)nV, hipMemcpyHostToDevice, stream));
-            MXS_TRY(hipMemcpyAsync(iso_cost.p, k0.data(), sizeof(T) * (size_t)nV, hipMemcpyHostToDevice, stream));
-            g.bpr = blocks_of(nV, AUX_TPB);
+        if (g.n_vars) {
+            g.bpr = blocks_of(g.n_vars, AUX_TPB);
             const dim3 grid((unsigned)(g.bpr * n_rep)), block(AUX_TPB);
-            hipLaunchKernelGGL((k_dsa_init<T>), grid, block, 0, stream, g, iso_val.p, iso_cost.p, cur[0].p, cur[1].p);
+            hipLaunchKernelGGL((k_dsa_init<T>), grid, block, 0, rh.stream, g, rh.iso_val.p, rh.iso_cost.p, cur[0].p, cur[1].p);
             MXS_TRY(hipGetLastError());
         }
         const int rc = every > 0 ? record(2) : MXS_OK;
-        MXS_TRY(hipStreamSynchronize(stream));  // (v0 / k0 leave scope: also when record() failed)
+        MXS_TRY(hipStreamSynchronize(rh.stream));  // (also when record() failed)
         return rc;
-    }
-
-    // the costs of the replicas' current assignments into rep_cost / rep_viol, on the stream; mode: k_cost_final
-    int launch_costs(double infinity, int mode) {
-        g.bpr = cost_blocks;
-        const CostArgs a{cur[which].p, coff.p, evc.p, hg.nF, infinity, part_cost.p, part_viol.p};
-        hipLaunchKernelGGL((repcost::k_cost_partial<Dev<T>>), dim3((unsigned)(cost_blocks * n_rep)), dim3(COST_TPB), 0, stream, g, a);
-        MXS_TRY(hipGetLastError());
-        hipLaunchKernelGGL((repcost::k_cost_final<BestRec>), dim3((unsigned)blocks_of(n_rep, 64)), dim3(64), 0, stream, (int)n_rep,
-                           cost_blocks, (int)g.is_max, (const double*)part_cost.p, (const long long*)part_viol.p, rep_cost.p,
-                           rep_viol.p, mode, best_rec());
-        MXS_TRY(hipGetLastError());
-        return MXS_OK;
     }
 
     BestRec best_rec() const { return BestRec{best_cost.p, best_viol.p, best_cycle.p, best_improved.p, best_idx.p}; }
 
     // the current states against the records (mode 1; 2: the first record), three launches in stream order
     int record(int mode) {
-        if (int rc = launch_costs(best_infinity, mode)) return rc;
+        if (int rc = rh.launch_costs(g, cur[which].p, best_infinity, mode, best_rec())) return rc;
         const int bpr = std::max(1, blocks_of(g.n_vars, AUX_TPB));
-        hipLaunchKernelGGL(k_dsa_best_copy, dim3((unsigned)(bpr * n_rep)), dim3(AUX_TPB), 0, stream, (int)g.n_vars, bpr,
-                           (const int32_t*)cur[which].p, (const double*)rep_cost.p, (const long long*)rep_viol.p,
+        hipLaunchKernelGGL(k_dsa_best_copy, dim3((unsigned)(bpr * n_rep)), dim3(AUX_TPB), 0, rh.stream, (int)g.n_vars, bpr,
+                           (const int32_t*)cur[which].p, (const double*)rh.rep_cost.p, (const long long*)rh.rep_viol.p,
                            (long long)cycles, best_rec());
         MXS_TRY(hipGetLastError());
         return MXS_OK;
@@ -621,22 +516,23 @@ struct Engine : Base {
     // the launches of one cycle of all replicas: packed plus rest, or thread per variable alone
     template <bool REP>
     int launch_cycle(bool packed, bool generic) {
+        const hipStream_t stream = rh.stream;
         if (packed) {
             g.bpr = blocks_of(g.pack.n_lanes, PACK_TPB);
             const dim3 pgrid((unsigned)(g.bpr * n_rep)), pblock(PACK_TPB);
-            if (pk.int8) hipLaunchKernelGGL((k_dsa_cycle_pack<T, int8_t, REP>), pgrid, pblock, 0, stream, g);
+            if (rh.pk.int8) hipLaunchKernelGGL((k_dsa_cycle_pack<T, int8_t, REP>), pgrid, pblock, 0, stream, g);
             else hipLaunchKernelGGL((k_dsa_cycle_pack<T, T, REP>), pgrid, pblock, 0, stream, g);
             MXS_TRY(hipGetLastError());
-            g.var_list = pk.rest.p;
-            g.n_list = pk.n_rest;
+            g.var_list = rh.pk.rest.p;
+            g.n_list = rh.pk.n_rest;
         }
         if (g.n_list > 0) {
             g.bpr = blocks_of(g.n_list, TPB);
             const dim3 grid((unsigned)(g.bpr * n_rep)), block(TPB);
-            if (generic || max_dom > 32) hipLaunchKernelGGL((k_dsa_cycle<T, REP>), grid, block, 0, stream, g);
-            else if (max_dom <= 4) hipLaunchKernelGGL((k_dsa_cycle_slots<T, 4, REP>), grid, block, 0, stream, g);
-            else if (max_dom <= 8) hipLaunchKernelGGL((k_dsa_cycle_slots<T, 8, REP>), grid, block, 0, stream, g);
-            else if (max_dom <= 16) hipLaunchKernelGGL((k_dsa_cycle_slots<T, 16, REP>), grid, block, 0, stream, g);
+            if (generic || rh.max_dom > 32) hipLaunchKernelGGL((k_dsa_cycle<T, REP>), grid, block, 0, stream, g);
+            else if (rh.max_dom <= 4) hipLaunchKernelGGL((k_dsa_cycle_slots<T, 4, REP>), grid, block, 0, stream, g);
+            else if (rh.max_dom <= 8) hipLaunchKernelGGL((k_dsa_cycle_slots<T, 8, REP>), grid, block, 0, stream, g);
+            else if (rh.max_dom <= 16) hipLaunchKernelGGL((k_dsa_cycle_slots<T, 16, REP>), grid, block, 0, stream, g);
             else hipLaunchKernelGGL((k_dsa_cycle_slots<T, 32, REP>), grid, block, 0, stream, g);
             MXS_TRY(hipGetLastError());
         }
@@ -644,79 +540,48 @@ struct Engine : Base {
     }
 
     int run(int32_t n) override {
-        MXS_TRY(hipSetDevice(device));
+        MXS_TRY(hipSetDevice(rh.device));
         const int nV = g.n_vars;
-        const char* env = std::getenv("MAXSUM_LOCAL_SEARCH_GENERIC");  // =1: the CSR-walk kernel, =2: the slot
-        const bool generic = env && env[0] == '1';                     // kernel for every variable (A/B, tests)
-        const bool packed = !generic && !(env && env[0] == '2') && g.pack.n_lanes > 0;
+        const rephost::KernelChoice k = rephost::kernel_choice(g.pack.n_lanes > 0);
         for (int32_t c = 0; c < n; ++c) {
             g.cur = cur[which].p;
             g.cur_out = cur[which ^ 1].p;
             g.cycle = cycles;
             g.var_list = nullptr;
             g.n_list = nV;
-            if (int rc = n_rep == 1 ? launch_cycle<false>(packed, generic) : launch_cycle<true>(packed, generic)) return rc;
+            if (int rc = n_rep == 1 ? launch_cycle<false>(k.packed, k.generic) : launch_cycle<true>(k.packed, k.generic)) return rc;
             which ^= 1;
             cycles += 1;
             if (every > 0 && cycles % every == 0)
                 if (int rc = record(1)) return rc;
         }
-        MXS_TRY(hipStreamSynchronize(stream));
+        MXS_TRY(hipStreamSynchronize(rh.stream));
         return MXS_OK;
-    }
-
-    // packed order (Dev::q) -> graph order
-    void unpack(const std::vector<int32_t>& hi, int32_t* idx) const {
-        for (int v = 0; v < g.n_vars; ++v) idx[v] = hi[h_q[v]];
     }
 
     int get_state(int32_t r, int32_t* idx, double* cst) override {
         if (r < 0 || r >= n_rep) return fail(MXS_E_INVALID, "replica out of range");
-        MXS_TRY(hipSetDevice(device));
+        MXS_TRY(hipSetDevice(rh.device));
         const int nV = g.n_vars;
         if (!nV) return MXS_OK;
         std::vector<T> hc(nV);
         std::vector<int32_t> hi(nV);
         const size_t roff = (size_t)r * nV;
-        MXS_TRY(hipMemcpyAsync(hi.data(), cur[which].p + roff, 4 * (size_t)nV, hipMemcpyDeviceToHost, stream));
-        MXS_TRY(hipMemcpyAsync(hc.data(), cost.p + roff, sizeof(T) * (size_t)nV, hipMemcpyDeviceToHost, stream));
-        MXS_TRY(hipStreamSynchronize(stream));
-        if (idx) unpack(hi, idx);
+        MXS_TRY(hipMemcpyAsync(hi.data(), cur[which].p + roff, 4 * (size_t)nV, hipMemcpyDeviceToHost, rh.stream));
+        MXS_TRY(hipMemcpyAsync(hc.data(), cost.p + roff, sizeof(T) * (size_t)nV, hipMemcpyDeviceToHost, rh.stream));
+        MXS_TRY(hipStreamSynchronize(rh.stream));
+        if (idx) rh.unpack(hi, idx);
         for (int v = 0; v < nV; ++v)
-            if (cst) cst[v] = (double)hc[h_q[v]];
+            if (cst) cst[v] = (double)hc[rh.h_q[v]];
         return MXS_OK;
     }
 
     int eval_cost(const int32_t* idx, double infinity, double* cst, int64_t* viol) override {
-        std::vector<int32_t> c;
-        if (!idx) {  // replica 0
-            c.resize(g.n_vars);
-            int rc = get_state(0, c.data(), nullptr);
-            if (rc) return rc;
-            idx = c.data();
-        }
-        return hg.eval_cost(idx, infinity, cst, viol);
-    }
-
-    int fetch_costs(std::vector<double>& hc, std::vector<long long>& hv, const double* dc, const long long* dv) {
-        hc.resize(n_rep), hv.resize(n_rep);
-        MXS_TRY(hipMemcpyAsync(hc.data(), dc, 8 * (size_t)n_rep, hipMemcpyDeviceToHost, stream));
-        MXS_TRY(hipMemcpyAsync(hv.data(), dv, 8 * (size_t)n_rep, hipMemcpyDeviceToHost, stream));
-        MXS_TRY(hipStreamSynchronize(stream));
-        return MXS_OK;
+        return rh.eval_cost(idx, infinity, cst, viol, [&](int32_t* out) { return get_state(0, out, nullptr); });
     }
 
     int replica_costs(double infinity, double* cst, int64_t* viol) override {
-        MXS_TRY(hipSetDevice(device));
-        if (int rc = launch_costs(infinity, 0)) return rc;
-        std::vector<double> hc;
-        std::vector<long long> hv;
-        if (int rc = fetch_costs(hc, hv, rep_cost.p, rep_viol.p)) return rc;
-        for (int r = 0; r < n_rep; ++r) {
-            if (cst) cst[r] = hc[r];
-            if (viol) viol[r] = (int64_t)hv[r];
-        }
-        return MXS_OK;
+        return rh.replica_costs(g, cur[which].p, infinity, cst, viol);
     }
 
     void drop_records() {
@@ -726,7 +591,7 @@ struct Engine : Base {
 
     int track_best(int32_t ev, double infinity) override {
         if (ev < 0) return fail(MXS_E_INVALID, "every must be 0 (off) or positive");
-        MXS_TRY(hipSetDevice(device));
+        MXS_TRY(hipSetDevice(rh.device));
         drop_records();
         if (ev == 0) {
             tracked = true;
@@ -747,23 +612,22 @@ struct Engine : Base {
         best_infinity = infinity;
         every = ev;
         if (int rc2 = record(2)) return rc2;  // the state as it is now: cycle 0 of a fresh engine
-        MXS_TRY(hipStreamSynchronize(stream));
+        MXS_TRY(hipStreamSynchronize(rh.stream));
         return MXS_OK;
     }
 
     int get_best(int32_t r, int32_t* replica, int64_t* cycle, double* cst, int64_t* viol, int32_t* idx) override {
         if (r < -1 || r >= n_rep) return fail(MXS_E_INVALID, "replica out of range");
         if (!tracked) return fail(MXS_E_STATE, "mxs_dsa_get_best before mxs_dsa_track_best");
-        MXS_TRY(hipSetDevice(device));
+        MXS_TRY(hipSetDevice(rh.device));
         std::vector<double> hc;
         std::vector<long long> hv, hy(n_rep, (long long)cycles);
         if (every > 0) {  // the records
-            if (int rc = fetch_costs(hc, hv, best_cost.p, best_viol.p)) return rc;
-            MXS_TRY(hipMemcpyAsync(hy.data(), best_cycle.p, 8 * (size_t)n_rep, hipMemcpyDeviceToHost, stream));
-            MXS_TRY(hipStreamSynchronize(stream));
+            if (int rc = rh.fetch_costs(hc, hv, best_cost.p, best_viol.p)) return rc;
+            MXS_TRY(hipMemcpyAsync(hy.data(), best_cycle.p, 8 * (size_t)n_rep, hipMemcpyDeviceToHost, rh.stream));
+            MXS_TRY(hipStreamSynchronize(rh.stream));
         } else {          // the current states
-            if (int rc = launch_costs(best_infinity, 0)) return rc;
-            if (int rc = fetch_costs(hc, hv, rep_cost.p, rep_viol.p)) return rc;
+            if (int rc = rh.current_costs(g, cur[which].p, best_infinity, hc, hv)) return rc;
         }
         if (r < 0) r = repcost::best_replica(n_rep, g.is_max, hc.data(), hv.data());
         if (replica) *replica = r;
@@ -774,9 +638,9 @@ struct Engine : Base {
             if (every > 0) {
                 std::vector<int32_t> hi(g.n_vars);
                 MXS_TRY(hipMemcpyAsync(hi.data(), best_idx.p + (size_t)r * g.n_vars, 4 * (size_t)g.n_vars,
-                                       hipMemcpyDeviceToHost, stream));
-                MXS_TRY(hipStreamSynchronize(stream));
-                unpack(hi, idx);
+                                       hipMemcpyDeviceToHost, rh.stream));
+                MXS_TRY(hipStreamSynchronize(rh.stream));
+                rh.unpack(hi, idx);
             } else if (int rc = get_state(r, idx, nullptr)) {
                 return rc;
             }

@@ -2,7 +2,7 @@
 // headers mgm.hip includes): error helpers, the device buffer, the counter-based generator, the host copy of an
 // mxs_graph with its checks and DCOP.solution_cost, the device side of the slot and the packed view of
 // local_search.h, and the shell of the mxs_*_create entry points.  Nothing here is a kernel; what only one engine
-// needs stays in that engine.
+// needs stays in that engine, what only the replica engines (dsa.hip, mgm.hip) share is replica_host.h.
 #pragma once
 
 #include <hip/hip_runtime.h>

@@ -35,7 +35,10 @@
 // Replica r is bit for bit the keyed single run with seeds[r].  The kernels are templates <REP, KEYED>: the
 // fixed-draw engine runs <false, false> on the plain Dev -- the parent's argument layout and instructions --,
 // a keyed engine <R > 1, true> on DevR.  MGM's own sum never rises, so its final state is its best: no best-state
-// tracking, the final states are ranked (replica_cost.h: the reduction shared with dsa.hip).
+// tracking, the final states are ranked (replica_cost.h: the reduction shared with dsa.hip).  The host side that does
+// not depend on the algorithm -- set-up, views, uploads, start values, the cost launches -- is rephost::Host
+// (replica_host.h, shared with dsa.hip); this file keeps the kernels, the Dev structs, the per-lane extras and the
+// round's launches.
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
@@ -49,6 +52,7 @@
 #include "engine_common.h"
 #include "local_search.h"
 #include "replica_cost.h"
+#include "replica_host.h"
 
 namespace mgm {
 
@@ -572,8 +576,6 @@ __global__ void __launch_bounds__(AUX_TPB) k_mgm_init(DevR<T> g, int keyed, cons
     g.grec[at] = GainRec<T>{(T)0, x, g.name_rank[v]};  // no gain yet, the "new value" is the initial one
 }
 
-using repcost::MAX_REPLICAS;
-
 struct Base {
     virtual ~Base() {}
     virtual int init(const mxs_graph& G, const mxs_params& p, const int32_t* rank, bool keyed, const uint64_t* seeds,
@@ -589,194 +591,109 @@ struct Base {
     int32_t n_rep = 1;
 };
 
+using rephost::alloc_rep;
+using rephost::blocks_of;
+static_assert(TPB == rephost::VAR_TPB && PACK_TPB == rephost::PACK_TPB && AUX_TPB == rephost::AUX_TPB,
+              "replica_host.h sizes its grid refusal by these");
+
 template <typename T>
 struct Engine : Base {
-    int device = 0;
-    hipStream_t stream = nullptr;
+    // the stream, the graph, the views, the CSR arrays, the seeds, the start values, the device cost (replica_host.h)
+    rephost::Host<T> rh;
     DevR<T> g{};
     int which = 0;
     bool keyed = false;
-    mxs_host::HostGraph hg;
-    std::vector<int32_t> h_nn, h_rank, h_q, h_vrank;
-    Buf<int32_t> dom_size, factor_rowptr, edge_var, edge_factor, var_rowptr, var_edges, name_rank, n_neigh, qmap;
+    Buf<int32_t> name_rank, init_idx;
     Buf<int32_t> cur[2];                    // the dynamic state: [R][n_vars], packed order
-    Buf<int64_t> table_off, cost_off;
-    Buf<T> tables, var_cost;
+    Buf<T> var_cost;
     Buf<T> cost[2], vcc[2], vc4;
     Buf<GainRec<T>> grec;
     Buf<uint8_t> has_cost;
-    mxs_host::DevSlots sl;
-    mxs_host::DevPack<T> pk;
     Buf<int32_t> pk_conc, pk_conc_x;  // what only MGM keeps per lane (Dev::pack_conc, pack_conc_x)
     Buf<int32_t> pk_var;              // [packed variables] graph index (DevR::pack_var)
-    int max_dom = 0;
-    // the start state (k_mgm_init): the seeds, the initial values, the variables without neighbours
-    Buf<uint64_t> seeds;
-    Buf<int32_t> init_idx, iso_val;
-    Buf<T> iso_cost;
-    // the device cost (replica_cost.h)
-    Buf<double> evc, part_cost, rep_cost;
-    Buf<long long> part_viol, rep_viol;
-    int cost_blocks = 1;
-
-    ~Engine() override {
-        if (stream) (void)hipStreamDestroy(stream);
-    }
-
-    // an allocation that grows with the number of replicas: its failure is MXS_E_NOMEM (the caller's
-    // destructor frees what was allocated before)
-    template <typename U>
-    static int alloc_rep(Buf<U>& b, size_t count, const char* what) {
-        if (b.alloc(count) != hipSuccess) {
-            (void)hipGetLastError();
-            b.p = nullptr;
-            b.n = 0;
-            return fail(MXS_E_NOMEM, std::string("out of device memory for the replicas' ") + what);
-        }
-        return MXS_OK;
-    }
-
-    static int blocks_of(int64_t n, int per_block) { return (int)((n + per_block - 1) / per_block); }
 
     int init(const mxs_graph& G, const mxs_params& p, const int32_t* rank, bool kd, const uint64_t* sds, int n_replicas,
              int dev) override {
-        device = dev;
         keyed = kd;
-        if (n_replicas < 1 || n_replicas > MAX_REPLICAS) return fail(MXS_E_INVALID, "the number of replicas must be in 1 .. 4096");
-        if (keyed && !sds) return fail(MXS_E_INVALID, "null seeds");
-        n_rep = n_replicas;
-        const std::vector<uint64_t> h_seeds = keyed ? std::vector<uint64_t>(sds, sds + n_replicas) : std::vector<uint64_t>(1, 0);
+        if (int rc = rh.open(sds, n_replicas, dev, keyed)) return rc;
+        n_rep = rh.n_rep;
+        if (int rc = rh.hg.load(G, p)) return rc;
+        if (int rc = rh.hg.load_init(G)) return rc;
+        const mxs_host::HostGraph& hg = rh.hg;
+        const hipStream_t stream = rh.stream;
+        const int nV = hg.nV;
         const size_t R = (size_t)n_rep;
-        if (int rc = mxs_host::open_device(dev, &stream)) return rc;
-        if (int rc = hg.load(G, p)) return rc;
-        const int nV = hg.nV, nF = hg.nF;
-        const std::vector<int32_t> &efac = hg.efac, &vrow = hg.vrow, &vedges = hg.vedges;
-        h_nn.assign(nV, 0);
-        for (int f = 0; f < nF; ++f)
-            if (hg.frow[f + 1] - hg.frow[f] > 1)
-                for (int e = hg.frow[f]; e < hg.frow[f + 1]; ++e) h_nn[hg.evar[e]] = 1;
         std::vector<int32_t> rk(nV);
         for (int v = 0; v < nV; ++v) rk[v] = rank ? rank[v] : v;
-        if (int rc = hg.load_init(G)) return rc;
-        const std::vector<T> tt = mxs_host::narrowed<T>(hg.tables), vc = mxs_host::narrowed<T>(hg.var_cost);
+        const std::vector<T> vc = mxs_host::narrowed<T>(hg.var_cost);
         lsearch::HostSlots hs;
-        const std::string bad = hs.build(nV, nF, hg.dom, hg.frow, hg.evar, hg.toff, vrow, vedges);
-        if (!bad.empty()) return fail(MXS_E_INVALID, bad);
-        max_dom = 0;
-        for (int v = 0; v < nV; ++v) max_dom = hg.dom[v] > max_dom ? hg.dom[v] : max_dom;
-        {   // the packed view of the variables it can take (local_search.h)
-            lsearch::HostPack hp;
-            hp.build(nV, hg.dom, vrow, h_nn, hs, hg.tables);
-            // every launch folds the replica into blockIdx.x: the largest grid must fit
-            cost_blocks = std::max(1, blocks_of((int64_t)nF + nV, repcost::COST_TPB * repcost::COST_RUN));
-            const int64_t most = std::max<int64_t>({blocks_of((int64_t)hp.nb.size(), PACK_TPB), blocks_of(nV, TPB), cost_blocks});
-            if (most * (int64_t)n_rep > INT32_MAX) return fail(MXS_E_INVALID, "too many replicas for an instance of this size");
-            h_q = mxs_host::packed_order(hp, nV);
-            MXS_TRY(qmap.upload(h_q, stream));
-            if (int rc = sl.upload(hs, stream, &h_q, true)) return rc;
-            std::vector<T> v4(hp.vars.size() * lsearch::PACK_D, (T)0);
-            std::vector<int32_t> pvar(hp.vars.size());
-            for (int v : hp.vars) {
-                pvar[h_q[v]] = v;
-                for (int x = 0; x < hg.dom[v]; ++x) v4[(size_t)h_q[v] * lsearch::PACK_D + x] = vc[hg.coff[v] + x];
-            }
-            MXS_TRY(vc4.upload(v4, stream));
-            MXS_TRY(pk_var.upload(pvar, stream));
-            g.q = qmap.p;
-            g.vc4 = vc4.p;
-            g.pack_var = pk_var.p;
-            std::vector<int32_t> conc(hp.nb.size(), -1), conc_x(hp.nb.size(), -1);
-            for (size_t i = 0; i < hp.nb.size(); ++i) {
-                const int v = hp.lane_var[i];
-                if (v < 0) continue;
-                const int c0 = hs.conc_rowptr[v], n_conc = hs.conc_rowptr[v + 1] - c0, k = hp.lane_k[i], deg = hp.lane_deg[i];
-                if (n_conc > deg + 1) return fail(MXS_E_STATE, "concerned-variables list longer than the degree + 1");
-                if (k < n_conc) conc[i] = hs.conc_var[c0 + k];
-                if (k == 0 && n_conc > deg) conc_x[i] = hs.conc_var[c0 + deg];
-            }
-            if (int rc = pk.upload(hp, h_q, hg.dom, stream)) return rc;
-            MXS_TRY(pk_conc.upload(mxs_host::remap(conc, h_q), stream));
-            MXS_TRY(pk_conc_x.upload(mxs_host::remap(conc_x, h_q), stream));
-            sl.upload_rows(hs, hp.rest, hg, max_dom, (int)sizeof(T), stream);
-            g.pack = pk.view();
-            g.pack_dom = pk.dom.p;
-            g.pack_conc = pk_conc.p;
-            g.pack_conc_x = pk_conc_x.p;
+        lsearch::HostPack hp;
+        if (int rc = rh.build_views(hs, hp)) return rc;
+        // MGM's extras: per packed variable its own costs and its graph index, per packed lane its elements of the
+        // variable's concerned-variables list
+        const std::vector<int32_t>& h_q = rh.h_q;
+        std::vector<T> v4(hp.vars.size() * lsearch::PACK_D, (T)0);
+        std::vector<int32_t> pvar(hp.vars.size());
+        for (int v : hp.vars) {
+            pvar[h_q[v]] = v;
+            for (int x = 0; x < hg.dom[v]; ++x) v4[(size_t)h_q[v] * lsearch::PACK_D + x] = vc[hg.coff[v] + x];
         }
-        g.slots = sl.view();
-        MXS_TRY(dom_size.upload(hg.dom, stream));
-        MXS_TRY(factor_rowptr.upload(hg.frow, stream));
-        MXS_TRY(edge_var.upload(hg.evar, stream));
-        MXS_TRY(edge_factor.upload(efac, stream));
-        MXS_TRY(var_rowptr.upload(vrow, stream));
-        MXS_TRY(var_edges.upload(vedges, stream));
+        std::vector<int32_t> conc(hp.nb.size(), -1), conc_x(hp.nb.size(), -1);
+        for (size_t i = 0; i < hp.nb.size(); ++i) {
+            const int v = hp.lane_var[i];
+            if (v < 0) continue;
+            const int c0 = hs.conc_rowptr[v], n_conc = hs.conc_rowptr[v + 1] - c0, k = hp.lane_k[i], deg = hp.lane_deg[i];
+            if (n_conc > deg + 1) return fail(MXS_E_STATE, "concerned-variables list longer than the degree + 1");
+            if (k < n_conc) conc[i] = hs.conc_var[c0 + k];
+            if (k == 0 && n_conc > deg) conc_x[i] = hs.conc_var[c0 + deg];
+        }
+        MXS_TRY(vc4.upload(v4, stream));
+        MXS_TRY(pk_var.upload(pvar, stream));
+        MXS_TRY(pk_conc.upload(mxs_host::remap(conc, h_q), stream));
+        MXS_TRY(pk_conc_x.upload(mxs_host::remap(conc_x, h_q), stream));
+        if (int rc = rh.upload_views(hs, hp)) return rc;
+        if (int rc = rh.upload_graph()) return rc;
         MXS_TRY(name_rank.upload(rk, stream));
-        MXS_TRY(n_neigh.upload(h_nn, stream));
-        MXS_TRY(table_off.upload(hg.toff, stream));
-        MXS_TRY(cost_off.upload(hg.coff, stream));
-        MXS_TRY(tables.upload(tt, stream));
         MXS_TRY(var_cost.upload(vc, stream));
-        MXS_TRY(seeds.upload(h_seeds, stream));
         MXS_TRY(init_idx.upload(hg.init, stream));
-        MXS_TRY(evc.upload(hg.eval_var_cost, stream));
-        MXS_TRY(iso_val.alloc(nV));
-        MXS_TRY(iso_cost.alloc(nV));
         for (int b = 0; b < 2; ++b) {
             if (int rc = alloc_rep(cur[b], R * nV, "values")) return rc;
             if (int rc = alloc_rep(cost[b], R * nV, "held costs")) return rc;
             if (int rc = alloc_rep(vcc[b], R * nV, "own costs")) return rc;
         }
-        h_rank = rk;
         if (int rc = alloc_rep(grec, R * nV, "gain records")) return rc;
         if (int rc = alloc_rep(has_cost, R * nV, "cost flags")) return rc;
-        if (int rc = alloc_rep(part_cost, R * cost_blocks, "cost partials")) return rc;
-        if (int rc = alloc_rep(part_viol, R * cost_blocks, "cost partials")) return rc;
-        if (int rc = alloc_rep(rep_cost, R, "costs")) return rc;
-        if (int rc = alloc_rep(rep_viol, R, "costs")) return rc;
-        g.n_vars = nV;
-        g.is_max = p.mode == MXS_MODE_MAX;
+        rh.bind(g);
         g.n_rep = n_rep;
         g.bpr = 1;
-        g.seeds = seeds.p;
-        g.dom_size = dom_size.p; g.factor_rowptr = factor_rowptr.p; g.edge_var = edge_var.p;
-        g.edge_factor = edge_factor.p; g.var_rowptr = var_rowptr.p; g.var_edges = var_edges.p;
-        g.init_idx = nullptr; g.name_rank = name_rank.p; g.n_neigh = n_neigh.p;
-        g.table_off = table_off.p; g.cost_off = cost_off.p; g.tables = tables.p; g.var_cost = var_cost.p;
+        g.init_idx = nullptr; g.name_rank = name_rank.p;
+        g.cost_off = rh.cost_off.p; g.var_cost = var_cost.p;
         g.has_cost = has_cost.p; g.grec = grec.p;
+        g.vc4 = vc4.p;
+        g.pack_var = pk_var.p;
+        g.pack_conc = pk_conc.p;
+        g.pack_conc_x = pk_conc_x.p;
         return reset();
     }
 
-    // the order of every variable's domain values (include/maxsum_gpu.h): cost ties of a variable without
-    // neighbours break on the value, as the reference's optimal_cost_value does
     int set_value_rank(const int32_t* rank) override {
-        if (rank) h_vrank.assign(rank, rank + hg.coff[g.n_vars]);
-        else h_vrank.clear();
+        rh.set_value_rank(rank);
         return reset();
     }
 
     // every replica back to its start state (k_mgm_init): what is uploaded does not grow with the replicas
     int reset() override {
-        MXS_TRY(hipSetDevice(device));
-        const int nV = g.n_vars;
-        std::vector<int32_t> v0(nV, -1);
-        std::vector<T> k0(nV, (T)0);
-        for (int v = 0; v < nV; ++v)
-            if (h_nn[v] == 0) {  // on_start without neighbours: optimal_cost_value (mgm.py:279-290)
-                v0[v] = hg.optimal_cost_value<T>(v, g.is_max, h_vrank);
-                k0[v] = (T)hg.var_cost[hg.coff[v] + v0[v]];
-            }
+        if (int rc = rh.start_values()) return rc;  // on_start without neighbours: optimal_cost_value (mgm.py:279-290)
         which = 0;
         rounds = 0;
-        if (nV) {
-            MXS_TRY(hipMemcpyAsync(iso_val.p, v0.data(), 4 * (size_t)nV, hipMemcpyHostToDevice, stream));
-            MXS_TRY(hipMemcpyAsync(iso_cost.p, k0.data(), sizeof(T) * (size_t)nV, hipMemcpyHostToDevice, stream));
-            g.bpr = blocks_of(nV, AUX_TPB);
+        if (g.n_vars) {
+            g.bpr = blocks_of(g.n_vars, AUX_TPB);
             const dim3 grid((unsigned)(g.bpr * n_rep)), block(AUX_TPB);
-            hipLaunchKernelGGL((k_mgm_init<T>), grid, block, 0, stream, g, keyed ? 1 : 0, (const int32_t*)iso_val.p,
-                               (const T*)iso_cost.p, (const int32_t*)init_idx.p, cur[0].p, cur[1].p, cost[0].p, cost[1].p,
+            hipLaunchKernelGGL((k_mgm_init<T>), grid, block, 0, rh.stream, g, keyed ? 1 : 0, (const int32_t*)rh.iso_val.p,
+                               (const T*)rh.iso_cost.p, (const int32_t*)init_idx.p, cur[0].p, cur[1].p, cost[0].p, cost[1].p,
                                vcc[0].p, vcc[1].p);
             MXS_TRY(hipGetLastError());
-            MXS_TRY(hipStreamSynchronize(stream));  // (v0 / k0 leave scope)
+            MXS_TRY(hipStreamSynchronize(rh.stream));
         }
         return MXS_OK;
     }
@@ -785,10 +702,11 @@ struct Engine : Base {
     // fixed-draw engine, kernels on the plain Dev; REP: all replicas, the replica folded into the grid
     template <bool REP, bool KEYED>
     int launch_round(bool packed, bool generic) {
-        const int nV = g.n_vars;
+        const hipStream_t stream = rh.stream;
+        const int nV = g.n_vars, max_dom = rh.max_dom;
         T* const cw = cost[which].p;
-        g.var_list = packed ? pk.rest.p : nullptr;
-        g.n_list = packed ? pk.n_rest : nV;
+        g.var_list = packed ? rh.pk.rest.p : nullptr;
+        g.n_list = packed ? rh.pk.n_rest : nV;
         const int pbpr = blocks_of(g.pack.n_lanes, PACK_TPB), bpr = blocks_of(g.n_list, TPB);
         const unsigned reps = REP ? (unsigned)n_rep : 1u;
         const dim3 pgrid((unsigned)pbpr * reps), pblock(PACK_TPB);
@@ -798,7 +716,7 @@ struct Engine : Base {
         DevOf<T, REP, false>& gm = g;       // what the move kernels take
         if (packed) {
             g.bpr = pbpr;
-            if (pk.int8) hipLaunchKernelGGL((k_mgm_gain_pack<T, int8_t, REP, KEYED>), pgrid, pblock, 0, stream, gg, cw);
+            if (rh.pk.int8) hipLaunchKernelGGL((k_mgm_gain_pack<T, int8_t, REP, KEYED>), pgrid, pblock, 0, stream, gg, cw);
             else hipLaunchKernelGGL((k_mgm_gain_pack<T, T, REP, KEYED>), pgrid, pblock, 0, stream, gg, cw);
             MXS_TRY(hipGetLastError());
         }
@@ -826,15 +744,13 @@ struct Engine : Base {
     }
 
     int run(int32_t n) override {
-        MXS_TRY(hipSetDevice(device));
+        MXS_TRY(hipSetDevice(rh.device));
         const int nV = g.n_vars;
         if (nV == 0) {
             rounds += n > 0 ? n : 0;
             return MXS_OK;
         }
-        const char* env = std::getenv("MAXSUM_LOCAL_SEARCH_GENERIC");  // =1: the CSR-walk kernels, =2: the slot
-        const bool generic = env && env[0] == '1';                     // kernels for every variable (A/B, tests)
-        const bool packed = !generic && !(env && env[0] == '2') && g.pack.n_lanes > 0;
+        const rephost::KernelChoice k = rephost::kernel_choice(g.pack.n_lanes > 0);
         for (int32_t r = 0; r < n; ++r) {
             g.cur = cur[which].p;
             g.cost = cost[which].p;
@@ -844,20 +760,21 @@ struct Engine : Base {
             g.vcc_out = vcc[which ^ 1].p;
             g.round = rounds + 1;  // the reference's cycle_count while it handles this round's values
             int rc;
-            if (!keyed) rc = launch_round<false, false>(packed, generic);
-            else if (n_rep == 1) rc = launch_round<false, true>(packed, generic);
-            else rc = launch_round<true, true>(packed, generic);
+            if (!keyed) rc = launch_round<false, false>(k.packed, k.generic);
+            else if (n_rep == 1) rc = launch_round<false, true>(k.packed, k.generic);
+            else rc = launch_round<true, true>(k.packed, k.generic);
             if (rc) return rc;
             which ^= 1;
             rounds += 1;
         }
-        MXS_TRY(hipStreamSynchronize(stream));
+        MXS_TRY(hipStreamSynchronize(rh.stream));
         return MXS_OK;
     }
 
     int get_state(int32_t r, int32_t* idx, double* cst, uint8_t* has, double* gn, int32_t* nv) override {
         if (r < 0 || r >= n_rep) return fail(MXS_E_INVALID, "replica out of range");
-        MXS_TRY(hipSetDevice(device));
+        MXS_TRY(hipSetDevice(rh.device));
+        const hipStream_t stream = rh.stream;
         const int nV = g.n_vars;
         if (!nV) return MXS_OK;
         std::vector<T> hc(nV);
@@ -871,7 +788,7 @@ struct Engine : Base {
         MXS_TRY(hipMemcpyAsync(hg.data(), grec.p + roff, sizeof(GainRec<T>) * (size_t)nV, hipMemcpyDeviceToHost, stream));
         MXS_TRY(hipStreamSynchronize(stream));
         for (int v = 0; v < nV; ++v) {  // the state lives in packed order (Dev::q)
-            const int qv = h_q[v];
+            const int qv = rh.h_q[v];
             if (idx) idx[v] = hi[qv];
             if (has) has[v] = hh[qv];
             if (cst) cst[v] = (double)hc[qv];
@@ -882,51 +799,19 @@ struct Engine : Base {
     }
 
     int eval_cost(const int32_t* idx, double infinity, double* cst, int64_t* viol) override {
-        std::vector<int32_t> c;
-        if (!idx) {  // replica 0
-            c.resize(g.n_vars);
-            int rc = get_state(0, c.data(), nullptr, nullptr, nullptr, nullptr);
-            if (rc) return rc;
-            idx = c.data();
-        }
-        return hg.eval_cost(idx, infinity, cst, viol);
-    }
-
-    // the costs of the replicas' current assignments (replica_cost.h), fetched
-    int device_costs(double infinity, std::vector<double>& hc, std::vector<long long>& hv) {
-        MXS_TRY(hipSetDevice(device));
-        g.bpr = cost_blocks;
-        const repcost::CostArgs a{cur[which].p, cost_off.p, evc.p, hg.nF, infinity, part_cost.p, part_viol.p};
-        hipLaunchKernelGGL((repcost::k_cost_partial<DevR<T>>), dim3((unsigned)(cost_blocks * n_rep)), dim3(repcost::COST_TPB), 0,
-                           stream, g, a);
-        MXS_TRY(hipGetLastError());
-        hipLaunchKernelGGL((repcost::k_cost_final<repcost::BestRec>), dim3((unsigned)blocks_of(n_rep, 64)), dim3(64), 0, stream,
-                           (int)n_rep, cost_blocks, (int)g.is_max, (const double*)part_cost.p, (const long long*)part_viol.p,
-                           rep_cost.p, rep_viol.p, 0, repcost::BestRec{});
-        MXS_TRY(hipGetLastError());
-        hc.resize(n_rep), hv.resize(n_rep);
-        MXS_TRY(hipMemcpyAsync(hc.data(), rep_cost.p, 8 * (size_t)n_rep, hipMemcpyDeviceToHost, stream));
-        MXS_TRY(hipMemcpyAsync(hv.data(), rep_viol.p, 8 * (size_t)n_rep, hipMemcpyDeviceToHost, stream));
-        MXS_TRY(hipStreamSynchronize(stream));
-        return MXS_OK;
+        return rh.eval_cost(idx, infinity, cst, viol,
+                            [&](int32_t* out) { return get_state(0, out, nullptr, nullptr, nullptr, nullptr); });
     }
 
     int replica_costs(double infinity, double* cst, int64_t* viol) override {
-        std::vector<double> hc;
-        std::vector<long long> hv;
-        if (int rc = device_costs(infinity, hc, hv)) return rc;
-        for (int r = 0; r < n_rep; ++r) {
-            if (cst) cst[r] = hc[r];
-            if (viol) viol[r] = (int64_t)hv[r];
-        }
-        return MXS_OK;
+        return rh.replica_costs(g, cur[which].p, infinity, cst, viol);
     }
 
     // MGM's own sum never rises: a run's final state is its best, the final states are ranked
     int best_replica(double infinity, int32_t* replica, double* cst, int64_t* viol) override {
         std::vector<double> hc;
         std::vector<long long> hv;
-        if (int rc = device_costs(infinity, hc, hv)) return rc;
+        if (int rc = rh.current_costs(g, cur[which].p, infinity, hc, hv)) return rc;
         const int r = repcost::best_replica(n_rep, g.is_max, hc.data(), hv.data());
         if (replica) *replica = r;
         if (cst) *cst = hc[r];

@@ -8,14 +8,14 @@ from typing import Dict, Optional, Sequence, Tuple
 
 import numpy as np
 
-from ._binding import EngineBinding
+from ._binding import ReplicaBinding
 from .engine import load_library
 from .graph import FlatGraph, Params
 
 VARIANTS = {"A": 0, "B": 1, "C": 2}
 
 
-class DsaEngine(EngineBinding):
+class DsaEngine(ReplicaBinding):
     """>>> eng = DsaEngine(graph, Params(mode="min"), variant="B", probability=0.7, seed=1)
     >>> eng.run(30)                                    # 30 cycles (= the reference's stop_cycle 30)
     >>> idx, cost = eng.assignment()
@@ -41,23 +41,13 @@ class DsaEngine(EngineBinding):
         self.graph = graph
         self.params = params or Params()
         cg, cp = graph.to_c(), self.params.to_c()
-        if seeds is None:
-            seeds = [int(seed) + r for r in range(int(replicas))]
-        elif replicas not in (1, len(seeds)):
-            raise ValueError(f"{len(seeds)} seeds for {replicas} replicas")
-        self.seeds = [int(x) & (2 ** 64 - 1) for x in seeds]
-        self.replicas = len(self.seeds)
-        sd = np.array(self.seeds, dtype=np.uint64)
+        sd = self._set_seeds(seed, seeds, replicas)
         h = C.c_void_p()
         self._check(self._lib.mxs_dsa_create_replicas(C.byref(cg), C.byref(cp), VARIANTS[variant], float(probability),
                                                       1 if p_mode == "arity" else 0, sd.ctypes.data, self.replicas,
                                                       int(device), C.byref(h)))
         self._h = h
-        # cost ties of a variable without neighbours break on the domain VALUE (relations.py:1661-1665):
-        # only needed when some domain is not written in ascending order
-        self._vrank = graph.value_rank()
-        if self._vrank is not None:
-            self._call("set_value_rank", self._vrank.ctypes.data)
+        self._set_value_rank()
 
     def reset(self):
         self._call("reset")
@@ -70,14 +60,6 @@ class DsaEngine(EngineBinding):
         cost = np.empty(self.graph.n_vars)
         self._call("get_state_replica", int(replica), idx.ctypes.data, cost.ctypes.data)
         return idx, cost
-
-    def replica_costs(self, infinity: float = float("inf")) -> Tuple[np.ndarray, np.ndarray]:
-        """(cost[R], violations[R]) of the replicas' current assignments, reduced on the device: what
-        `eval_cost(assignment(r)[0], infinity)` gives, in a fixed summation order of its own."""
-        cost = np.empty(self.replicas)
-        viol = np.empty(self.replicas, dtype=np.int64)
-        self._call("replica_costs", float(infinity), cost.ctypes.data, viol.ctypes.data)
-        return cost, viol
 
     def track_best(self, every: int = 1, infinity: float = float("inf")):
         """Keep, per replica, the best state seen at cycle 0 and after every `every`-th cycle (0: off; the

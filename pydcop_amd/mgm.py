@@ -6,7 +6,7 @@ from typing import Dict, Optional, Sequence, Tuple
 
 import numpy as np
 
-from ._binding import EngineBinding
+from ._binding import ReplicaBinding
 from .engine import MaxSumGpuError, load_library
 from .graph import FlatGraph, Params
 
@@ -24,7 +24,7 @@ def name_ranks(names) -> np.ndarray:
     return rank
 
 
-class MgmEngine(EngineBinding):
+class MgmEngine(ReplicaBinding):
     """>>> eng = MgmEngine(graph, Params(mode="min"))   # every computation started
     >>> eng.run(30)                                    # 30 rounds (= the reference's stop_cycle 31)
     >>> idx, cost = eng.assignment()
@@ -49,16 +49,11 @@ class MgmEngine(EngineBinding):
             raise ValueError(f"Invalid value {draws!r} for parameter draws, must be one of {list(DRAWS)}")
         if draws == "fixed" and (int(replicas) != 1 or seeds is not None):
             raise ValueError("replicas / seeds need draws=\"keyed\": with the fixed draws every run is the same run")
-        if seeds is None:
-            seeds = [int(seed) + r for r in range(int(replicas))]
-        elif replicas not in (1, len(seeds)):
-            raise ValueError(f"{len(seeds)} seeds for {replicas} replicas")
+        sd = self._set_seeds(seed, seeds, replicas)
         self._lib = load_library(lib_path)
         self.graph = graph
         self.params = params or Params()
         self.draws = draws
-        self.seeds = [int(x) & (2 ** 64 - 1) for x in seeds]
-        self.replicas = len(self.seeds)
         cg, cp = graph.to_c(), self.params.to_c()
         self._rank = name_ranks(graph.var_names) if graph.var_names else None
         rank = None if self._rank is None else self._rank.ctypes.data
@@ -71,15 +66,10 @@ class MgmEngine(EngineBinding):
                 raise MaxSumGpuError(
                     f"{self._lib._name} was built from sources without MGM's keyed draws (no {', '.join(missing)}): "
                     "rebuild the library, draws=\"keyed\" needs them")
-            sd = np.array(self.seeds, dtype=np.uint64)
             self._check(self._lib.mxs_mgm_create_keyed(C.byref(cg), C.byref(cp), rank, sd.ctypes.data, self.replicas,
                                                        int(device), C.byref(h)))
         self._h = h
-        # cost ties of a variable without neighbours break on the domain VALUE (relations.py:1661-1665):
-        # only needed when some domain is not written in ascending order
-        self._vrank = graph.value_rank()
-        if self._vrank is not None:
-            self._call("set_value_rank", self._vrank.ctypes.data)
+        self._set_value_rank()
 
     def reset(self):
         self._call("reset")
@@ -107,13 +97,8 @@ class MgmEngine(EngineBinding):
             raise ValueError(f"{what} needs draws=\"keyed\"")
 
     def replica_costs(self, infinity: float = float("inf")) -> Tuple[np.ndarray, np.ndarray]:
-        """(cost[R], violations[R]) of the replicas' current assignments, reduced on the device: what
-        `eval_cost(assignment(r)[0], infinity)` gives, in a fixed summation order of its own."""
         self._keyed_only("replica_costs")
-        cost = np.empty(self.replicas)
-        viol = np.empty(self.replicas, dtype=np.int64)
-        self._call("replica_costs", float(infinity), cost.ctypes.data, viol.ctypes.data)
-        return cost, viol
+        return super().replica_costs(infinity)
 
     def best(self, infinity: float = float("inf")) -> Dict:
         """The best replica's current state -- fewest violations, then best cost, then lowest index, ranked on the
