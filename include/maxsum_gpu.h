@@ -586,6 +586,28 @@ int mxs_mgm2_rounds(const mxs_mgm2 *e, int64_t *rounds);
 int mxs_mgm2_get_state(mxs_mgm2 *e, int32_t *idx, double *cost, uint8_t *has_cost);
 int mxs_mgm2_eval_cost(mxs_mgm2 *e, const int32_t *idx, double infinity, double *cost, int64_t *violations);
 int mxs_mgm2_destroy(mxs_mgm2 *e);
+/* REPLICAS: n_replicas seeded runs of the instance in ONE engine, 1 <= n_replicas <= 4096 (else MXS_E_INVALID; null
+ * seeds: MXS_E_INVALID; a grid of more than 2^31 - 1 blocks -- the largest launch of one run times n_replicas --:
+ * MXS_E_INVALID; device memory that does not suffice: MXS_E_NOMEM, nothing stays allocated).  The slot view, the
+ * tables, the domains, the name ranks and the layout of the offer tables are stored once; the dynamic state is
+ * [replica][variable] and [replica][offer entry] -- n_vars * (53 + sizeof(T))
+ * plus n_entries * (1 + sizeof(T)) bytes per replica, n_entries = sum over the variables of D_v * the largest domain
+ * among v's neighbours --; a round of all replicas is the five launches one run needs.  Replica r is bit for bit
+ * mxs_mgm2_create with seed seeds[r], the start included: a variable with an initial value keeps it in every
+ * replica, the others take draw 0 under their replica's seed.  mxs_mgm2_reset / _run act on all replicas;
+ * mxs_mgm2_get_state and mxs_mgm2_eval_cost(idx = NULL) mean replica 0.  An engine of mxs_mgm2_create has one
+ * replica (its mxs_mgm2_replica_costs is mxs_mgm2_eval_cost of its state). */
+int mxs_mgm2_create_replicas(const mxs_graph *g, const mxs_params *p, const int32_t *name_rank, double threshold,
+                             int32_t favor, const uint64_t *seeds, int32_t n_replicas, int32_t device, mxs_mgm2 **out);
+int mxs_mgm2_replicas(const mxs_mgm2 *e, int32_t *n);
+int mxs_mgm2_get_state_replica(mxs_mgm2 *e, int32_t replica, int32_t *idx, double *cost, uint8_t *has_cost);
+/* DCOP.solution_cost of every replica's current assignment, reduced on the device: as mxs_dsa_replica_costs (the
+ * same kernels) */
+int mxs_mgm2_replica_costs(mxs_mgm2 *e, double infinity, double *cost, int64_t *violations);
+/* The best replica: the lexicographic minimum of (violations, cost, index) over the CURRENT states, the cost negated
+ * with MXS_MODE_MAX -- the rule of mxs_mgm_best_replica.  MGM-2's sum stops improving at a local optimum; no best
+ * state is tracked.  Any out pointer may be NULL. */
+int mxs_mgm2_best_replica(mxs_mgm2 *e, double infinity, int32_t *replica, double *cost, int64_t *violations);
 
 /* ---- DPOP (pydcop/algorithms/dpop.py) on the same flat arrays: the exact optimum -------------------
  * The caller gives the pseudo-tree: parent[v] (-1: a root) and every node's children in order
@@ -697,8 +719,10 @@ int mxs_dba_eval_cost(mxs_dba *e, const int32_t *idx, double infinity, double *c
 int mxs_dba_destroy(mxs_dba *e);
 
 /* Library/ABI version (major*100+minor).  270 also covers the MGM additions made after it was set -- mxs_mgm_create_keyed,
- * mxs_mgm_replicas, mxs_mgm_get_state_replica, mxs_mgm_replica_costs, mxs_mgm_best_replica: a binding that needs them
- * looks the symbols up instead of comparing versions (pydcop_amd/mgm.py does, and says so when they are missing). */
+ * mxs_mgm_replicas, mxs_mgm_get_state_replica, mxs_mgm_replica_costs, mxs_mgm_best_replica -- and the MGM-2 additions
+ * after those -- mxs_mgm2_create_replicas, mxs_mgm2_replicas, mxs_mgm2_get_state_replica, mxs_mgm2_replica_costs,
+ * mxs_mgm2_best_replica: a binding that needs them looks the symbols up instead of comparing versions (pydcop_amd/mgm.py
+ * and pydcop_amd/mgm2.py do, and say so when they are missing). */
 int32_t mxs_version(void);
 
 /* What this binary is: 1 = the product, compiled by hipcc for gfx950; 0 = the host

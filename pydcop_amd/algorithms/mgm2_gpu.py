@@ -9,7 +9,10 @@ Extra parameter `seed` (default 0): every stochastic choice -- start value, offe
 best unilateral value, the `favor: no` coin, the accepted offer -- comes from the counter-based
 generator of dsa_gpu keyed on (seed, variable, round, draw) over canonically ordered sequences, where
 the reference draws from Python's unseeded `random`: a run is reproducible, and bit for bit the
-reference's own Mgm2Computation under the same generator.
+reference's own Mgm2Computation under the same generator.  `restarts: R` (default 1) runs R seeded replicas (seeds
+seed .. seed + R - 1) in the one engine and publishes the best replica's values and held costs -- fewest entries equal
+to infinity, then the best solution cost, evaluated on the device; the ranking takes no `infinity` (the module has no
+such parameter: every table entry, however large, is a cost).  With the defaults the module is the single run above.
 """
 from types import SimpleNamespace
 
@@ -31,6 +34,7 @@ algo_params = [
     AlgoParameterDef("precision", "str", ["f64", "f32"], "f64"),
     AlgoParameterDef("seed", "int", None, 0),
     AlgoParameterDef("chunk", "int", None, 10),
+    AlgoParameterDef("restarts", "int", None, 1),
 ]
 
 
@@ -80,13 +84,17 @@ class _RoundEngine:
     def __init__(self, graph, params, p):
         from pydcop_amd.mgm2 import Mgm2Engine
         self.graph = graph
-        self._e = Mgm2Engine(graph, params, threshold=p["threshold"], favor=p["favor"], seed=int(p["seed"]))
+        self._many = int(p["restarts"]) > 1
+        self._e = Mgm2Engine(graph, params, threshold=p["threshold"], favor=p["favor"], seed=int(p["seed"]),
+                             replicas=int(p["restarts"]))
 
     def run(self, n: int):
         self._e.run(int(n))
 
     def assignment(self):
-        return self._e.assignment()
+        if not self._many:
+            return self._e.assignment()
+        return self._e.assignment(self._e.best()["replica"])     # the best replica's values and held costs
 
     @property
     def cycle_count(self) -> int:

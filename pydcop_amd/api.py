@@ -67,7 +67,8 @@ def _algo_kw(algo, variant, probability, p_mode, seed, threshold, favor, modifie
     if algo == "dsa":
         return dict(variant=variant, probability=probability, p_mode=p_mode, seed=seed, replicas=int(restarts))
     if algo == "mgm2":
-        return dict(threshold=threshold, favor=favor, seed=seed)
+        kw = dict(threshold=threshold, favor=favor, seed=seed)
+        return dict(kw, replicas=int(restarts)) if int(restarts) != 1 else kw     # (one run: mxs_mgm2_create, as ever)
     if algo == "mgm" and draws != "fixed":
         return dict(draws=draws, seed=seed, replicas=int(restarts))
     return None
@@ -95,8 +96,8 @@ def _check_restarts(algo, restarts, best_every, draws="fixed"):
         raise ValueError("draws must be \"fixed\" or \"keyed\"")
     if draws != "fixed" and algo != "mgm":
         raise ValueError("draws: algo=\"mgm\" only (the other local searches always key their draws on `seed`)")
-    if int(restarts) != 1 and not (algo == "dsa" or (algo == "mgm" and draws == "keyed")):
-        raise ValueError("restarts: algo=\"dsa\", or algo=\"mgm\" with draws=\"keyed\"")
+    if int(restarts) != 1 and not (algo in ("dsa", "mgm2") or (algo == "mgm" and draws == "keyed")):
+        raise ValueError("restarts: algo=\"dsa\" or \"mgm2\", or algo=\"mgm\" with draws=\"keyed\"")
     if algo != "dsa" and int(best_every) != 0:
         raise ValueError("best_every: algo=\"dsa\" only")
 
@@ -115,9 +116,9 @@ def _dsa_best(eng, algo, restarts, best_every, infinity):
 
 
 def _mgm_best(eng, algo, restarts, infinity):
-    """algo="mgm" with restarts (keyed draws): (idx of the best replica's final state, the result's extra keys); the
-    device cost only ranks.  Else None."""
-    if algo != "mgm" or int(restarts) == 1:
+    """algo="mgm" (keyed draws) or "mgm2" with restarts: (idx of the best replica's final state, the result's extra
+    keys); the device cost only ranks.  Else None."""
+    if algo not in ("mgm", "mgm2") or int(restarts) == 1:
         return None
     best = eng.best(infinity)
     costs, _ = eng.replica_costs(infinity)
@@ -177,7 +178,10 @@ def solve_dcop(dcop, cycles: int = 30, *, damping: float = 0.5, damping_nodes: s
     (both draws from the generator DSA uses, keyed on `seed`).  With draws="keyed", `restarts` = R seeded runs (seeds
     seed .. seed + R - 1) in one engine: the assignment is the best run's final state (fewest violations, then cost,
     ranked on the device) and the result gains "replica" and "replica_costs".  `best_every` stays DSA's: the sum MGM
-    descends on never rises, so a run's final state is already its best and there is nothing to track."""
+    descends on never rises, so a run's final state is already its best and there is nothing to track.
+
+    algo="mgm2": `restarts` = R seeded runs (seeds seed .. seed + R - 1) in one engine, the same way: the assignment is
+    the best run's final state and the result gains "replica" and "replica_costs"."""
     _check_restarts(algo, restarts, best_every, draws)
     graph = compile_dcop(dcop, noise=noise if algo in ("maxsum", "amaxsum") else 0.0, seed=seed)
     params = Params(mode=dcop.objective, damping=damping, damping_nodes=damping_nodes,

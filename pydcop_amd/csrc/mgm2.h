@@ -19,6 +19,15 @@
 // (seed, variable, round, draw); the sequences a draw picks from are in canonical order (tests/mgm2_oracle.py).
 // All cost sums run over the variable's constraints in the reference's order, starting from 0
 // (assignment_cost, relations.py:1513-1531), through the slot view of local_search.h.
+//
+// REPLICAS (mxs_mgm2_create_replicas): R seeded runs advance with the same five launches, as in mgm.hip.  The five
+// phases are __device__ bodies (value_phase .. decide_phase) with two sets of __global__ entry points: k_mgm2_* on
+// the plain Dev -- what mxs_mgm2_create launches, argument layout and grid as before -- and k_mgm2r_* on DevR, where
+// the replica is folded into blockIdx.x (block = r * bpr + b, replica_cost.h) and the block's copy of the argument
+// moves once to replica r's slice of the dynamic state and takes seeds[r] (enter_replica).  Everything static is
+// stored once; the state is [R][n_vars] / [R][n_entries] in GRAPH order (there is no packed order here).  The start
+// state is drawn on the device (k_mgm2r_init), the solution costs are reduced by replica_cost.h's kernels, the
+// refusals, the allocations that grow with R and the cost launches are replica_host.h's.
 #pragma once
 
 namespace mgm2 {
@@ -66,6 +75,32 @@ struct Dev {
     uint8_t* offer_ok;              // the entry improves on the local cost
 };
 
+// what the replica engine's kernels take: Dev plus the replicas.  The single-run kernels keep the plain Dev, i.e.
+// their argument layout.  The per-replica arrays of Dev -- cur, cost, has_cost, uni, recv -- are [replicas][n_vars],
+// offer and offer_ok [replicas][n_entries]; `seed` is filled per block from seeds[r] (enter_replica).
+template <typename T>
+struct DevR : Dev<T> {
+    int32_t bpr;               // blocks per replica of the launch being made (block = replica * bpr + b)
+    int32_t n_rep;
+    const uint64_t* seeds;     // [replicas]
+    // what k_cost_partial (replica_cost.h) reads of its G: the constraints' CSR and q, here the identity -- the
+    // state is in graph order
+    const int32_t *dom_size, *factor_rowptr, *edge_var, *q;
+    const int64_t* table_off;
+};
+
+// the replica of this block: the block's copy of DevR (kernel arguments, block-uniform) moves to the replica's slice
+// of the dynamic state and takes its seed, so that nothing below knows about replicas
+template <typename T>
+__device__ inline int enter_replica(DevR<T>& g, int* b) {
+    const int r = repcost::replica_of_block<true>(g, b);
+    const int64_t off = (int64_t)r * g.n_vars, eoff = (int64_t)r * g.n_entries;
+    g.cur += off, g.cost += off, g.has_cost += off, g.uni += off, g.recv += off;
+    g.offer += eoff, g.offer_ok += eoff;
+    g.seed = g.seeds[r];
+    return r;
+}
+
 // assignment_cost over v's constraints in the reference's order, from 0: v at x, variable u at y (u < 0:
 // none), every other variable at its current value; skip_u: only the constraints WITHOUT u
 // (_find_best_offer's `concerned`, :575-582)
@@ -87,8 +122,7 @@ __device__ inline T slot_sum(const Dev<T>& g, int v, int x, int u, int y, bool s
 }
 
 template <typename T>
-__global__ void __launch_bounds__(TPB) k_mgm2_value(Dev<T> g) {
-    const int v = blockIdx.x * blockDim.x + threadIdx.x;
+__device__ __forceinline__ void value_phase(const Dev<T>& g, const int v) {
     if (v >= g.n_vars || !g.has_nb[v]) return;
     const int D = g.dom[v], cv = g.cur[v];
     const T lcost = slot_sum(g, v, cv, -1, 0, false);  // _current_local_cost -> __cost__
@@ -138,8 +172,7 @@ __global__ void __launch_bounds__(TPB) k_mgm2_value(Dev<T> g) {
 // one lane per entry of every variable's table; the lanes of non-offerers and the rows beyond the partner's
 // domain write nothing (nobody reads them this round)
 template <typename T>
-__global__ void __launch_bounds__(OTPB) k_mgm2_offers(Dev<T> g) {
-    const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+__device__ __forceinline__ void offers_phase(const Dev<T>& g, const int64_t t) {
     if (t >= g.n_entries) return;
     const int v = g.ent_var[t];
     const Rec<T> r = g.uni[v];
@@ -155,8 +188,7 @@ __global__ void __launch_bounds__(OTPB) k_mgm2_offers(Dev<T> g) {
 }
 
 template <typename T>
-__global__ void __launch_bounds__(TPB) k_mgm2_receive(Dev<T> g) {
-    const int v = blockIdx.x * blockDim.x + threadIdx.x;
+__device__ __forceinline__ void receive_phase(const Dev<T>& g, const int v) {
     if (v >= g.n_vars || !g.has_nb[v]) return;
     const Rec<T> me = g.uni[v];
     Rec<T> out;
@@ -231,8 +263,7 @@ __global__ void __launch_bounds__(TPB) k_mgm2_receive(Dev<T> g) {
 }
 
 template <typename T>
-__global__ void __launch_bounds__(TPB) k_mgm2_resolve(Dev<T> g) {
-    const int v = blockIdx.x * blockDim.x + threadIdx.x;
+__device__ __forceinline__ void resolve_phase(const Dev<T>& g, const int v) {
     if (v >= g.n_vars || !g.has_nb[v]) return;
     Rec<T> me = g.uni[v];
     if (me.flags & F_OFFERER) {
@@ -270,8 +301,7 @@ __device__ inline bool can_move(const Dev<T>& g, int a, int partner, T gain) {
 }
 
 template <typename T>
-__global__ void __launch_bounds__(TPB) k_mgm2_decide(Dev<T> g) {
-    const int v = blockIdx.x * blockDim.x + threadIdx.x;
+__device__ __forceinline__ void decide_phase(const Dev<T>& g, const int v) {
     if (v >= g.n_vars || !g.has_nb[v]) return;
     const Rec<T> me = g.uni[v];
     if (me.gain == (T)0) return;  // nothing to do this round; the held cost stays the local cost
@@ -303,15 +333,174 @@ __global__ void __launch_bounds__(TPB) k_mgm2_decide(Dev<T> g) {
     }
 }
 
+// ---- the entry points.  The single-run kernels: the plain Dev, the thread's index from blockIdx.x alone -- what
+// mxs_mgm2_create has always launched.
+template <typename T>
+__global__ void __launch_bounds__(TPB) k_mgm2_value(Dev<T> g) {
+    const int v = blockIdx.x * blockDim.x + threadIdx.x;
+    value_phase(g, v);
+}
+template <typename T>
+__global__ void __launch_bounds__(OTPB) k_mgm2_offers(Dev<T> g) {
+    const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    offers_phase(g, t);
+}
+template <typename T>
+__global__ void __launch_bounds__(TPB) k_mgm2_receive(Dev<T> g) {
+    const int v = blockIdx.x * blockDim.x + threadIdx.x;
+    receive_phase(g, v);
+}
+template <typename T>
+__global__ void __launch_bounds__(TPB) k_mgm2_resolve(Dev<T> g) {
+    const int v = blockIdx.x * blockDim.x + threadIdx.x;
+    resolve_phase(g, v);
+}
+template <typename T>
+__global__ void __launch_bounds__(TPB) k_mgm2_decide(Dev<T> g) {
+    const int v = blockIdx.x * blockDim.x + threadIdx.x;
+    decide_phase(g, v);
+}
+
+// The replica kernels (mxs_mgm2_create_replicas): R runs per launch, whole blocks belong to one replica
+// (block = r * bpr + b); below enter_replica the phase code is the single run's.
+template <typename T>
+__global__ void __launch_bounds__(TPB) k_mgm2r_value(DevR<T> g) {
+    int b;
+    enter_replica(g, &b);
+    value_phase<T>(g, b * (int)blockDim.x + (int)threadIdx.x);
+}
+template <typename T>
+__global__ void __launch_bounds__(OTPB) k_mgm2r_offers(DevR<T> g) {
+    int b;
+    enter_replica(g, &b);
+    offers_phase<T>(g, (int64_t)b * blockDim.x + threadIdx.x);
+}
+template <typename T>
+__global__ void __launch_bounds__(TPB) k_mgm2r_receive(DevR<T> g) {
+    int b;
+    enter_replica(g, &b);
+    receive_phase<T>(g, b * (int)blockDim.x + (int)threadIdx.x);
+}
+template <typename T>
+__global__ void __launch_bounds__(TPB) k_mgm2r_resolve(DevR<T> g) {
+    int b;
+    enter_replica(g, &b);
+    resolve_phase<T>(g, b * (int)blockDim.x + (int)threadIdx.x);
+}
+template <typename T>
+__global__ void __launch_bounds__(TPB) k_mgm2r_decide(DevR<T> g) {
+    int b;
+    enter_replica(g, &b);
+    decide_phase<T>(g, b * (int)blockDim.x + (int)threadIdx.x);
+}
+
+// the start state of every replica (on_start, :460-495), thread per (replica, variable): a variable with neighbours
+// keeps its initial value (the same in every replica) or takes int(u * D_v); one without neighbours takes the k-th of
+// its best own-constraint values (best_val[best_off[v] ..], uploaded once) and holds their cost.  u: draw 0 of
+// cycle 0 under seeds[r].
+constexpr int AUX_TPB = rephost::AUX_TPB;
+template <typename T>
+__global__ void __launch_bounds__(AUX_TPB) k_mgm2r_init(DevR<T> g, const int32_t* init, const int64_t* best_off,
+                                                        const int32_t* best_val, const T* best_cost) {
+    int b;
+    enter_replica(g, &b);
+    const int v = b * (int)blockDim.x + (int)threadIdx.x;
+    if (v >= g.n_vars) return;
+    const double u = uniform(g.seed, v, 0, D_START);
+    int x;
+    if (g.has_nb[v]) {
+        x = init[v] >= 0 ? init[v] : (int)(u * g.dom[v]);
+    } else {
+        const int64_t b0 = best_off[v];
+        x = best_val[b0 + (int64_t)(u * (double)(best_off[v + 1] - b0))];
+    }
+    g.cur[v] = x;
+    g.cost[v] = g.has_nb[v] ? (T)0 : best_cost[v];
+    g.has_cost[v] = g.has_nb[v] ? 0 : 1;
+}
+
+// ---- the host side the two engines share
+inline int check_params(double threshold, int32_t favor) {
+    if (!(threshold >= 0.0 && threshold <= 1.0)) return fail(MXS_E_INVALID, "threshold must be in [0, 1]");
+    if (favor < 0 || favor > 2) return fail(MXS_E_INVALID, "favor must be 0 (unilateral), 1 (no) or 2 (coordinated)");
+    return MXS_OK;
+}
+
+// max() over NaN gains depends on message arrival in the reference: no defined result
+inline int check_tables(const mxs_host::HostGraph& hg) {
+    for (double t : hg.tables)
+        if (!std::isfinite(t)) return fail(MXS_E_INVALID, "mgm2: constraint tables must be finite (no inf / NaN entries)");
+    return MXS_OK;
+}
+
+// who has neighbours (the other variables of v's constraints: the concerned list holds v itself once) and the
+// offer tables: D_v rows of P_v = the largest domain among v's neighbours
+struct Layout {
+    std::vector<int32_t> has_nb, width, ent_var;
+    std::vector<int64_t> off;
+    int build(const mxs_host::HostGraph& hg, const lsearch::HostSlots& hs) {
+        const int nV = hg.nV;
+        has_nb.assign(nV, 0);
+        width.assign(nV, 0);
+        off.assign(nV + 1, 0);
+        for (int v = 0; v < nV; ++v) {
+            int P = 0;
+            for (int k = hs.conc_rowptr[v]; k < hs.conc_rowptr[v + 1]; ++k)
+                if (hs.conc_var[k] != v) P = std::max(P, hg.dom[hs.conc_var[k]]);
+            has_nb[v] = P > 0;
+            width[v] = P;
+            off[v + 1] = off[v] + (int64_t)hg.dom[v] * P;
+        }
+        if (off[nV] > INT32_MAX) return fail(MXS_E_INVALID, "mgm2: offer tables larger than 2^31 entries");
+        ent_var.resize((size_t)off[nV]);
+        for (int v = 0; v < nV; ++v)
+            for (int64_t i = off[v]; i < off[v + 1]; ++i) ent_var[(size_t)i] = v;
+        return MXS_OK;
+    }
+};
+
+// on_start of a variable without neighbours (:460-470): the best values of its own constraints, in domain order
+// (strictly better starts a new list, equal joins it), and their cost
+template <typename T>
+T best_own_values(const mxs_host::HostGraph& hg, const lsearch::HostSlots& hs, int v, std::vector<int32_t>& vals) {
+    T best = (T)0;
+    vals.clear();
+    for (int x = 0; x < hg.dom[v]; ++x) {
+        T acc = (T)0;
+        for (int s = hg.vrow[v]; s < hg.vrow[v + 1]; ++s) acc += (T)hg.tables[hs.base[s] + (int64_t)x * hs.stride_v[s]];
+        if (vals.empty() || (hg.is_max ? best < acc : best > acc)) {
+            best = acc;
+            vals.assign(1, x);
+        } else if (best == acc) {
+            vals.push_back(x);
+        }
+    }
+    return best;
+}
+
+inline std::vector<int32_t> ranks_or_index(const int32_t* rk, int nV) {
+    std::vector<int32_t> h(nV);
+    for (int v = 0; v < nV; ++v) h[v] = rk ? rk[v] : v;
+    return h;
+}
+
 struct Base {
     virtual ~Base() = default;
-    virtual int init(const mxs_graph& g, const mxs_params& p, const int32_t* rank, double threshold, int32_t favor,
-                     uint64_t seed, int device) = 0;
+    // mxs_mgm2_create (Engine) / mxs_mgm2_create_replicas (ReplicaEngine)
+    virtual int init(const mxs_graph&, const mxs_params&, const int32_t*, double, int32_t, uint64_t, int) {
+        return fail(MXS_E_STATE, "mgm2: not the single-run engine");
+    }
+    virtual int init(const mxs_graph&, const mxs_params&, const int32_t*, double, int32_t, const uint64_t*, int32_t, int) {
+        return fail(MXS_E_STATE, "mgm2: not the replica engine");
+    }
     virtual int reset() = 0;
     virtual int run(int32_t n) = 0;
-    virtual int get_state(int32_t* idx, double* cost, uint8_t* has_cost) = 0;
+    virtual int get_state(int32_t r, int32_t* idx, double* cost, uint8_t* has_cost) = 0;
     virtual int eval_cost(const int32_t* idx, double infinity, double* cost, int64_t* viol) = 0;
+    virtual int replica_costs(double infinity, double* cost, int64_t* viol) = 0;
+    virtual int best_replica(double infinity, int32_t* replica, double* cost, int64_t* viol) = 0;
     int64_t rounds = 0;
+    int32_t n_rep = 1;
 };
 
 template <typename T>
@@ -337,34 +526,19 @@ struct Engine : Base {
              int dev) override {
         device = dev;
         if (int rc = mxs_host::open_device(dev, &stream)) return rc;
-        if (!(threshold >= 0.0 && threshold <= 1.0)) return fail(MXS_E_INVALID, "threshold must be in [0, 1]");
-        if (favor < 0 || favor > 2) return fail(MXS_E_INVALID, "favor must be 0 (unilateral), 1 (no) or 2 (coordinated)");
+        if (int rc = check_params(threshold, favor)) return rc;
         if (int rc = hg.load(G, p)) return rc;
         const int nV = hg.nV, nF = hg.nF;
-        // max() over NaN gains depends on message arrival in the reference: no defined result
-        for (double t : hg.tables)
-            if (!std::isfinite(t)) return fail(MXS_E_INVALID, "mgm2: constraint tables must be finite (no inf / NaN entries)");
+        if (int rc = check_tables(hg)) return rc;
         if (int rc = hg.load_init(G)) return rc;
         const std::string bad = hs.build(nV, nF, hg.dom, hg.frow, hg.evar, hg.toff, hg.vrow, hg.vedges);
         if (!bad.empty()) return fail(MXS_E_INVALID, bad);
-        // neighbours: the other variables of v's constraints (the concerned list holds v itself once)
-        h_nb.assign(nV, 0);
-        std::vector<int32_t> h_w(nV, 0), h_ent;
-        std::vector<int64_t> h_off(nV + 1, 0);
-        for (int v = 0; v < nV; ++v) {
-            int P = 0;
-            for (int k = hs.conc_rowptr[v]; k < hs.conc_rowptr[v + 1]; ++k)
-                if (hs.conc_var[k] != v) P = std::max(P, hg.dom[hs.conc_var[k]]);
-            h_nb[v] = P > 0;
-            h_w[v] = P;
-            h_off[v + 1] = h_off[v] + (int64_t)hg.dom[v] * P;
-        }
-        if (h_off[nV] > INT32_MAX) return fail(MXS_E_INVALID, "mgm2: offer tables larger than 2^31 entries");
-        h_ent.resize((size_t)h_off[nV]);
-        for (int v = 0; v < nV; ++v)
-            for (int64_t i = h_off[v]; i < h_off[v + 1]; ++i) h_ent[(size_t)i] = v;
-        std::vector<int32_t> h_rank(nV);
-        for (int v = 0; v < nV; ++v) h_rank[v] = rk ? rk[v] : v;
+        Layout lay;
+        if (int rc = lay.build(hg, hs)) return rc;
+        h_nb = lay.has_nb;
+        const std::vector<int32_t>&h_w = lay.width, &h_ent = lay.ent_var;
+        const std::vector<int64_t>& h_off = lay.off;
+        const std::vector<int32_t> h_rank = ranks_or_index(rk, nV);
         if (int rc = sl.upload(hs, stream, nullptr, false)) return rc;  // no first-neighbour arrays, no rows
         MXS_TRY(dom.upload(hg.dom, stream));
         MXS_TRY(var_rowptr.upload(hg.vrow, stream));
@@ -414,33 +588,15 @@ struct Engine : Base {
         std::vector<int32_t> c0(nV);
         std::vector<T> k0(nV, (T)0);
         std::vector<uint8_t> h0(nV, 0);
+        std::vector<int32_t> vals;
         for (int v = 0; v < nV; ++v) {
             const double u = uniform(g.seed, v, 0, D_START);
             if (h_nb[v]) {
                 c0[v] = hg.init[v] >= 0 ? hg.init[v] : (int)(u * hg.dom[v]);
                 continue;
             }
-            std::vector<T> c(hg.dom[v]);
-            T best = (T)0;
-            int n_best = 0;
-            for (int x = 0; x < hg.dom[v]; ++x) {
-                T acc = (T)0;
-                for (int s = hg.vrow[v]; s < hg.vrow[v + 1]; ++s) acc += (T)hg.tables[hs.base[s] + (int64_t)x * hs.stride_v[s]];
-                c[x] = acc;
-                if (n_best == 0 || (g.is_max ? best < acc : best > acc)) {
-                    best = acc;
-                    n_best = 1;
-                } else if (best == acc) {
-                    ++n_best;
-                }
-            }
-            int k = (int)(u * n_best);
-            for (int x = 0; x < hg.dom[v]; ++x)
-                if (c[x] == best && k-- == 0) {
-                    c0[v] = x;
-                    break;
-                }
-            k0[v] = best;
+            k0[v] = best_own_values<T>(hg, hs, v, vals);
+            c0[v] = vals[(size_t)(int)(u * (int)vals.size())];
             h0[v] = 1;
         }
         if (nV) {
@@ -482,7 +638,8 @@ struct Engine : Base {
         return MXS_OK;
     }
 
-    int get_state(int32_t* idx, double* cst, uint8_t* has) override {
+    int get_state(int32_t r, int32_t* idx, double* cst, uint8_t* has) override {
+        if (r != 0) return fail(MXS_E_INVALID, "replica out of range");
         MXS_TRY(hipSetDevice(device));
         const int nV = g.n_vars;
         if (!nV) return MXS_OK;
@@ -506,11 +663,205 @@ struct Engine : Base {
         std::vector<int32_t> c;
         if (!idx) {
             c.resize(g.n_vars);
-            int rc = get_state(c.data(), nullptr, nullptr);
+            int rc = get_state(0, c.data(), nullptr, nullptr);
             if (rc) return rc;
             idx = c.data();
         }
         return hg.eval_cost(idx, infinity, cst, viol);
+    }
+
+    // one run: its cost is eval_cost's, and it is the best replica
+    int replica_costs(double infinity, double* cst, int64_t* viol) override { return eval_cost(nullptr, infinity, cst, viol); }
+    int best_replica(double infinity, int32_t* replica, double* cst, int64_t* viol) override {
+        if (replica) *replica = 0;
+        return eval_cost(nullptr, infinity, cst, viol);
+    }
+};
+
+// R seeded runs of the instance with the launches one run needs (mxs_mgm2_create_replicas).  The slot view, the
+// tables, dom, rank and the offer tables' layout are stored once; cur, cost, has_cost, uni, recv are [R][n_vars],
+// offer and offer_ok [R][n_entries]; the seeds are a device array.  The refusals, the allocations that grow with R
+// and the cost launches are rephost::Host's (replica_host.h, shared with dsa.hip and mgm.hip); MGM-2 keeps its
+// variables in graph order, so Host's q is the identity (graph_order).  MGM-2's sum stops improving at a local
+// optimum and is not tracked: the CURRENT states are ranked (repcost::best_replica).
+template <typename T>
+struct ReplicaEngine : Base {
+    rephost::Host<T> rh;
+    DevR<T> g{};
+    mxs_host::DevSlots sl;
+    Buf<int32_t> rank, off_w, ent_var, init_idx, best_val;
+    Buf<int64_t> off_off, best_off;
+    Buf<T> best_cost;
+    Buf<int32_t> cur;                 // the dynamic state: [R][n_vars], graph order
+    Buf<T> cost, offer;
+    Buf<uint8_t> has_cost, offer_ok;
+    Buf<Rec<T>> uni, recv;
+
+    int init(const mxs_graph& G, const mxs_params& p, const int32_t* rk, double threshold, int32_t favor,
+             const uint64_t* sds, int32_t n_replicas, int dev) override {
+        if (int rc = rh.open(sds, n_replicas, dev, true)) return rc;
+        n_rep = rh.n_rep;
+        if (int rc = check_params(threshold, favor)) return rc;
+        if (int rc = rh.hg.load(G, p)) return rc;
+        if (int rc = check_tables(rh.hg)) return rc;
+        if (int rc = rh.hg.load_init(G)) return rc;
+        const mxs_host::HostGraph& hg = rh.hg;
+        const hipStream_t stream = rh.stream;
+        const int nV = hg.nV;
+        lsearch::HostSlots hs;
+        const std::string bad = hs.build(nV, hg.nF, hg.dom, hg.frow, hg.evar, hg.toff, hg.vrow, hg.vedges);
+        if (!bad.empty()) return fail(MXS_E_INVALID, bad);
+        Layout lay;
+        if (int rc = lay.build(hg, hs)) return rc;
+        const int64_t nE = lay.off[nV];
+        if (int rc = rh.graph_order(lay.has_nb, std::max<int64_t>(rephost::blocks_of(nV, TPB), rephost::blocks_of(nE, OTPB))))
+            return rc;
+        // the start of the variables without neighbours: their best values and the cost, whatever the replicas
+        std::vector<int64_t> b_off(nV + 1, 0);
+        std::vector<int32_t> b_val, vals;
+        std::vector<T> b_cost(nV, (T)0);
+        for (int v = 0; v < nV; ++v) {
+            if (!lay.has_nb[v]) {
+                b_cost[v] = best_own_values<T>(hg, hs, v, vals);
+                b_val.insert(b_val.end(), vals.begin(), vals.end());
+            }
+            b_off[v + 1] = (int64_t)b_val.size();
+        }
+        if (int rc = sl.upload(hs, stream, nullptr, false)) return rc;  // no first-neighbour arrays, no rows
+        if (int rc = rh.upload_order()) return rc;
+        if (int rc = rh.upload_graph()) return rc;
+        MXS_TRY(rank.upload(ranks_or_index(rk, nV), stream));
+        MXS_TRY(off_w.upload(lay.width, stream));
+        MXS_TRY(off_off.upload(lay.off, stream));
+        MXS_TRY(ent_var.upload(lay.ent_var, stream));
+        MXS_TRY(init_idx.upload(hg.init, stream));
+        MXS_TRY(best_off.upload(b_off, stream));
+        MXS_TRY(best_val.upload(b_val, stream));
+        MXS_TRY(best_cost.upload(b_cost, stream));
+        const size_t R = (size_t)n_rep;
+        if (int rc = rephost::alloc_rep(cur, R * nV, "values")) return rc;
+        if (int rc = rephost::alloc_rep(cost, R * nV, "held costs")) return rc;
+        if (int rc = rephost::alloc_rep(has_cost, R * nV, "cost flags")) return rc;
+        if (int rc = rephost::alloc_rep(uni, R * nV, "move records")) return rc;
+        if (int rc = rephost::alloc_rep(recv, R * nV, "receiver records")) return rc;
+        if (int rc = rephost::alloc_rep(offer, R * (size_t)nE, "offer tables")) return rc;
+        if (int rc = rephost::alloc_rep(offer_ok, R * (size_t)nE, "offer tables")) return rc;
+        g.slots = sl.view();
+        g.n_vars = nV;
+        g.is_max = hg.is_max;
+        g.favor = favor;
+        g.threshold = threshold;
+        g.seed = 0;  // per block: seeds[r]
+        g.dom = rh.dom_size.p;
+        g.var_rowptr = rh.var_rowptr.p;
+        g.has_nb = rh.n_neigh.p;
+        g.rank = rank.p;
+        g.off_off = off_off.p;
+        g.off_w = off_w.p;
+        g.ent_var = ent_var.p;
+        g.n_entries = nE;
+        g.tables = rh.tables.p;
+        g.cur = cur.p;
+        g.cost = cost.p;
+        g.has_cost = has_cost.p;
+        g.uni = uni.p;
+        g.recv = recv.p;
+        g.offer = offer.p;
+        g.offer_ok = offer_ok.p;
+        g.bpr = 1;
+        g.n_rep = n_rep;
+        g.seeds = rh.seeds.p;
+        g.dom_size = rh.dom_size.p;
+        g.factor_rowptr = rh.factor_rowptr.p;
+        g.edge_var = rh.edge_var.p;
+        g.q = rh.qmap.p;
+        g.table_off = rh.table_off.p;
+        return reset();
+    }
+
+    // every replica back to its start state (k_mgm2r_init): nothing is uploaded
+    int reset() override {
+        MXS_TRY(hipSetDevice(rh.device));
+        rounds = 0;
+        if (g.n_vars) {
+            g.bpr = rephost::blocks_of(g.n_vars, AUX_TPB);
+            hipLaunchKernelGGL((k_mgm2r_init<T>), dim3((unsigned)(g.bpr * n_rep)), dim3(AUX_TPB), 0, rh.stream, g,
+                               (const int32_t*)init_idx.p, (const int64_t*)best_off.p, (const int32_t*)best_val.p,
+                               (const T*)best_cost.p);
+            MXS_TRY(hipGetLastError());
+            MXS_TRY(hipStreamSynchronize(rh.stream));
+        }
+        return MXS_OK;
+    }
+
+    int run(int32_t n) override {
+        MXS_TRY(hipSetDevice(rh.device));
+        const hipStream_t stream = rh.stream;
+        const int nV = g.n_vars;
+        if (nV == 0) {
+            rounds += n > 0 ? n : 0;
+            return MXS_OK;
+        }
+        const int vbpr = rephost::blocks_of(nV, TPB), obpr = rephost::blocks_of(g.n_entries, OTPB);
+        const dim3 grid((unsigned)vbpr * (unsigned)n_rep), block(TPB);
+        const dim3 ogrid((unsigned)obpr * (unsigned)n_rep), oblock(OTPB);
+        for (int32_t r = 0; r < n; ++r) {
+            g.round = rounds + 1;
+            g.bpr = vbpr;  // (a kernel takes its DevR by value: the copy is made at the launch)
+            hipLaunchKernelGGL((k_mgm2r_value<T>), grid, block, 0, stream, g);
+            MXS_TRY(hipGetLastError());
+            if (g.n_entries > 0) {
+                g.bpr = obpr;
+                hipLaunchKernelGGL((k_mgm2r_offers<T>), ogrid, oblock, 0, stream, g);
+                MXS_TRY(hipGetLastError());
+                g.bpr = vbpr;
+            }
+            hipLaunchKernelGGL((k_mgm2r_receive<T>), grid, block, 0, stream, g);
+            MXS_TRY(hipGetLastError());
+            hipLaunchKernelGGL((k_mgm2r_resolve<T>), grid, block, 0, stream, g);
+            MXS_TRY(hipGetLastError());
+            hipLaunchKernelGGL((k_mgm2r_decide<T>), grid, block, 0, stream, g);
+            MXS_TRY(hipGetLastError());
+            rounds += 1;
+        }
+        MXS_TRY(hipStreamSynchronize(stream));
+        return MXS_OK;
+    }
+
+    int get_state(int32_t r, int32_t* idx, double* cst, uint8_t* has) override {
+        if (r < 0 || r >= n_rep) return fail(MXS_E_INVALID, "replica out of range");
+        MXS_TRY(hipSetDevice(rh.device));
+        const hipStream_t stream = rh.stream;
+        const int nV = g.n_vars;
+        if (!nV) return MXS_OK;
+        std::vector<T> hc(nV);
+        std::vector<uint8_t> hh(nV);
+        const size_t roff = (size_t)r * nV;
+        if (idx) MXS_TRY(hipMemcpyAsync(idx, cur.p + roff, 4 * (size_t)nV, hipMemcpyDeviceToHost, stream));
+        if (has) MXS_TRY(hipMemcpyAsync(has, has_cost.p + roff, nV, hipMemcpyDeviceToHost, stream));
+        if (cst) MXS_TRY(hipMemcpyAsync(hc.data(), cost.p + roff, sizeof(T) * (size_t)nV, hipMemcpyDeviceToHost, stream));
+        MXS_TRY(hipStreamSynchronize(stream));
+        for (int v = 0; cst && v < nV; ++v) cst[v] = (double)hc[v];
+        return MXS_OK;
+    }
+
+    int eval_cost(const int32_t* idx, double infinity, double* cst, int64_t* viol) override {
+        return rh.eval_cost(idx, infinity, cst, viol, [&](int32_t* out) { return get_state(0, out, nullptr, nullptr); });
+    }
+
+    int replica_costs(double infinity, double* cst, int64_t* viol) override {
+        return rh.replica_costs(g, cur.p, infinity, cst, viol);
+    }
+
+    int best_replica(double infinity, int32_t* replica, double* cst, int64_t* viol) override {
+        std::vector<double> hc;
+        std::vector<long long> hv;
+        if (int rc = rh.current_costs(g, cur.p, infinity, hc, hv)) return rc;
+        const int r = repcost::best_replica(n_rep, g.is_max, hc.data(), hv.data());
+        if (replica) *replica = r;
+        if (cst) *cst = hc[r];
+        if (viol) *viol = (int64_t)hv[r];
+        return MXS_OK;
     }
 };
 
@@ -526,6 +877,15 @@ int mxs_mgm2_create(const mxs_graph* g, const mxs_params* p, const int32_t* name
                     uint64_t seed, int32_t device, mxs_mgm2** out) {
     return mxs_host::create<mxs_mgm2, mgm2::Engine>(g, p, out, name_rank, threshold, favor, seed, device);
 }
+int mxs_mgm2_create_replicas(const mxs_graph* g, const mxs_params* p, const int32_t* name_rank, double threshold,
+                             int32_t favor, const uint64_t* seeds, int32_t n_replicas, int32_t device, mxs_mgm2** out) {
+    return mxs_host::create<mxs_mgm2, mgm2::ReplicaEngine>(g, p, out, name_rank, threshold, favor, seeds, n_replicas, device);
+}
+int mxs_mgm2_replicas(const mxs_mgm2* e, int32_t* n) {
+    if (!e) return mxs_host::fail(MXS_E_INVALID, "null handle");
+    if (n) *n = e->impl->n_rep;
+    return MXS_OK;
+}
 int mxs_mgm2_reset(mxs_mgm2* e) { return e ? e->impl->reset() : mxs_host::fail(MXS_E_INVALID, "null handle"); }
 int mxs_mgm2_run(mxs_mgm2* e, int32_t n_rounds) {
     if (!e) return mxs_host::fail(MXS_E_INVALID, "null handle");
@@ -538,7 +898,16 @@ int mxs_mgm2_rounds(const mxs_mgm2* e, int64_t* rounds) {
     return MXS_OK;
 }
 int mxs_mgm2_get_state(mxs_mgm2* e, int32_t* idx, double* cost, uint8_t* has_cost) {
-    return e ? e->impl->get_state(idx, cost, has_cost) : mxs_host::fail(MXS_E_INVALID, "null handle");
+    return e ? e->impl->get_state(0, idx, cost, has_cost) : mxs_host::fail(MXS_E_INVALID, "null handle");
+}
+int mxs_mgm2_get_state_replica(mxs_mgm2* e, int32_t replica, int32_t* idx, double* cost, uint8_t* has_cost) {
+    return e ? e->impl->get_state(replica, idx, cost, has_cost) : mxs_host::fail(MXS_E_INVALID, "null handle");
+}
+int mxs_mgm2_replica_costs(mxs_mgm2* e, double infinity, double* cost, int64_t* violations) {
+    return e ? e->impl->replica_costs(infinity, cost, violations) : mxs_host::fail(MXS_E_INVALID, "null handle");
+}
+int mxs_mgm2_best_replica(mxs_mgm2* e, double infinity, int32_t* replica, double* cost, int64_t* violations) {
+    return e ? e->impl->best_replica(infinity, replica, cost, violations) : mxs_host::fail(MXS_E_INVALID, "null handle");
 }
 int mxs_mgm2_eval_cost(mxs_mgm2* e, const int32_t* idx, double infinity, double* cost, int64_t* violations) {
     return e ? e->impl->eval_cost(idx, infinity, cost, violations) : mxs_host::fail(MXS_E_INVALID, "null handle");

@@ -1,5 +1,5 @@
 // replica_cost.h -- the DEVICE side of what the engines that advance R seeded runs of one instance in one engine share
-// (dsa.hip, mgm.hip; the host side, which launches these kernels, is replica_host.h): the fold of the replica into
+// (dsa.hip, mgm.hip, mgm2.h; the host side, which launches these kernels, is replica_host.h): the fold of the replica into
 // blockIdx.x, and the solution cost of every replica's current assignment reduced on the device.  G is the engine's Dev: it carries n_vars, bpr (blocks per replica of the launch being made), the CSR arrays
 // of the constraints (factor_rowptr, edge_var, dom_size, table_off, tables) and q (graph index -> position in the
 // dynamic state); the values are passed beside it, [replicas][n_vars] in packed order.

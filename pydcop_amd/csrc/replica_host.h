@@ -1,8 +1,10 @@
 // replica_host.h -- the host side of an engine that advances R seeded runs of one instance with the same launches
-// (dsa.hip, mgm.hip; the device side is replica_cost.h): what such an engine owns whatever its algorithm, and the
-// steps of its life that do not depend on the algorithm.  Host code only: no kernel, no kernel-argument layout.  An
+// (dsa.hip, mgm.hip, mgm2.h; the device side is replica_cost.h): what such an engine owns whatever its algorithm, and
+// the steps of its life that do not depend on the algorithm.  Host code only: no kernel, no kernel-argument layout.  An
 // engine HOLDS a Host<T> and supplies its Dev (the kernels' argument), its per-lane extras (built from the host views
-// between build_views and upload_views), its init kernel (after start_values) and the launches of a cycle.
+// between build_views and upload_views), its init kernel (after start_values) and the launches of a cycle.  MGM-2
+// brings its own view and keeps its state in graph order: it takes open, graph_order / upload_order in place of
+// build_views / upload_views, upload_graph, alloc_rep and the cost launches, and binds its DevR itself.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -106,18 +108,41 @@ struct Host {
         for (int v = 0; v < nV; ++v) max_dom = hg.dom[v] > max_dom ? hg.dom[v] : max_dom;
         hp.build(nV, hg.dom, hg.vrow, h_nn, hs, hg.tables);
         h_q = mxs_host::packed_order(hp, nV);
-        cost_blocks = std::max(1, blocks_of((int64_t)nF + nV, repcost::COST_TPB * repcost::COST_RUN));
-        // every launch folds the replica into blockIdx.x: the largest grid must fit
-        const int64_t most = std::max<int64_t>({blocks_of((int64_t)hp.nb.size(), PACK_TPB), blocks_of(nV, VAR_TPB),
-                                                blocks_of(nV, AUX_TPB), cost_blocks});
+        return fit_grids(std::max<int64_t>(blocks_of((int64_t)hp.nb.size(), PACK_TPB), blocks_of(nV, VAR_TPB)));
+    }
+
+    // the same step of an engine that brings its own view and keeps its state in GRAPH order (mgm2.h): who has
+    // neighbours is the engine's, q is the identity, there is no packed view; most_blocks: the blocks of its largest
+    // launch for ONE replica
+    int graph_order(const std::vector<int32_t>& has_neighbours, int64_t most_blocks) {
+        const int nV = hg.nV;
+        h_nn = has_neighbours;
+        h_q.resize(nV);
+        for (int v = 0; v < nV; ++v) h_q[v] = v;
+        max_dom = 0;
+        for (int v = 0; v < nV; ++v) max_dom = hg.dom[v] > max_dom ? hg.dom[v] : max_dom;
+        return fit_grids(most_blocks);
+    }
+
+    // the grid of the cost reduction, and the one refusal: every launch folds the replica into blockIdx.x, the
+    // largest grid must fit
+    int fit_grids(int64_t most_blocks) {
+        cost_blocks = std::max(1, blocks_of((int64_t)hg.nF + hg.nV, repcost::COST_TPB * repcost::COST_RUN));
+        const int64_t most = std::max<int64_t>({most_blocks, blocks_of(hg.nV, AUX_TPB), cost_blocks});
         if (most * (int64_t)n_rep > INT32_MAX) return fail(MXS_E_INVALID, "too many replicas for an instance of this size");
+        return MXS_OK;
+    }
+
+    // graph index -> position in the dynamic state (k_cost_partial reads the values through it)
+    int upload_order() {
+        MXS_TRY(qmap.upload(h_q, stream));
         return MXS_OK;
     }
 
     // the views on the device, their variable references as packed positions (the engine has built its per-lane
     // extras from hs / hp / h_q by now: upload_rows releases hs.rows)
     int upload_views(lsearch::HostSlots& hs, const lsearch::HostPack& hp) {
-        MXS_TRY(qmap.upload(h_q, stream));
+        if (int rc = upload_order()) return rc;
         if (int rc = sl.upload(hs, stream, &h_q, true)) return rc;
         if (int rc = pk.upload(hp, h_q, hg.dom, stream)) return rc;
         sl.upload_rows(hs, hp.rest, hg, max_dom, (int)sizeof(T), stream);

@@ -66,6 +66,8 @@ ABI_SYMBOLS = (
 MGM2_SYMBOLS = (
     "mxs_mgm2_create", "mxs_mgm2_reset", "mxs_mgm2_run", "mxs_mgm2_rounds", "mxs_mgm2_get_state", "mxs_mgm2_eval_cost",
     "mxs_mgm2_destroy",
+    "mxs_mgm2_create_replicas", "mxs_mgm2_replicas", "mxs_mgm2_get_state_replica", "mxs_mgm2_replica_costs",
+    "mxs_mgm2_best_replica",
 )
 
 
@@ -271,6 +273,13 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
         "mxs_mgm_get_state_replica": ([vp, i32, vp, vp, vp, vp, vp], C.c_int),
         "mxs_mgm_replica_costs": ([vp, C.c_double, vp, vp], C.c_int),
         "mxs_mgm_best_replica": ([vp, C.c_double, C.POINTER(i32), C.POINTER(C.c_double), C.POINTER(i64)], C.c_int),
+        # ... and Mgm2Engine(replicas=R) (pydcop_amd/mgm2.py)
+        "mxs_mgm2_create_replicas": ([C.POINTER(CGraph), C.POINTER(CParams), vp, C.c_double, i32, vp, i32, i32,
+                                      C.POINTER(vp)], C.c_int),
+        "mxs_mgm2_replicas": ([vp, C.POINTER(i32)], C.c_int),
+        "mxs_mgm2_get_state_replica": ([vp, i32, vp, vp, vp], C.c_int),
+        "mxs_mgm2_replica_costs": ([vp, C.c_double, vp, vp], C.c_int),
+        "mxs_mgm2_best_replica": ([vp, C.c_double, C.POINTER(i32), C.POINTER(C.c_double), C.POINTER(i64)], C.c_int),
     }
     for name, (argtypes, restype) in later.items():
         fn = getattr(lib, name, None)

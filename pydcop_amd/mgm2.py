@@ -2,16 +2,18 @@
 (include/maxsum_gpu.h; device code: pydcop_amd/csrc/mgm2.h) on the same FlatGraph as the other
 engines -- factors are the constraints, variables the MGM-2 computations.  No CPU fallback."""
 import ctypes as C
-from typing import Optional, Tuple
+from typing import Dict, Optional, Sequence, Tuple
 
 import numpy as np
 
-from ._binding import EngineBinding
-from .engine import load_library
+from ._binding import ReplicaBinding
+from .engine import MaxSumGpuError, load_library
 from .graph import FlatGraph, Params
 from .mgm import name_ranks
 
 FAVORS = ("unilateral", "no", "coordinated")
+REPLICA_SYMBOLS = ("mxs_mgm2_create_replicas", "mxs_mgm2_replicas", "mxs_mgm2_get_state_replica",
+                   "mxs_mgm2_replica_costs", "mxs_mgm2_best_replica")
 
 
 def check_params(threshold, favor):
@@ -28,29 +30,50 @@ def check_params(threshold, favor):
     return threshold, FAVORS.index(favor)
 
 
-class Mgm2Engine(EngineBinding):
+class Mgm2Engine(ReplicaBinding):
     """>>> eng = Mgm2Engine(graph, Params(mode="min"), threshold=0.5, favor="unilateral", seed=0)
     >>> eng.run(30)                                    # 30 rounds (= the reference's stop_cycle 31)
     >>> idx, cost = eng.assignment()
-    """
+
+    `replicas=R`: R seeded runs of the instance in one engine (seeds `seed + r` modulo 2**64, or `seeds`), advanced
+    by the five launches of one round over one copy of the tables; replica r is bit for bit the engine with that
+    seed.  MGM-2's sum stops improving at a local optimum: run it from many seeds and keep the best.
+    >>> eng = Mgm2Engine(graph, favor="coordinated", replicas=8, seed=5)
+    >>> eng.run(30)
+    >>> eng.best(infinity=10000)                       # the best replica's current state
+    `replicas=1` without `seeds` is the single-run engine (`mxs_mgm2_create`)."""
     PREFIX = "mxs_mgm2"
     COUNTER = "rounds"
 
     def __init__(self, graph: FlatGraph, params: Optional[Params] = None, threshold: float = 0.5,
-                 favor: str = "unilateral", seed: int = 0, device: int = 0, lib_path: Optional[str] = None):
+                 favor: str = "unilateral", seed: int = 0, device: int = 0, lib_path: Optional[str] = None,
+                 seeds: Optional[Sequence[int]] = None, replicas: int = 1):
         self.threshold, favor_code = check_params(threshold, favor)
         self.favor, self.seed = favor, int(seed)
+        single = seeds is None and int(replicas) == 1
+        sd = self._set_seeds(seed, seeds, replicas)     # (no seeds at all: the library refuses 0 replicas)
         self._lib = load_library(lib_path)
         self.graph = graph
         self.params = params or Params()
         cg, cp = graph.to_c(), self.params.to_c()
         self._rank = name_ranks(graph.var_names) if graph.var_names else None
+        rank = None if self._rank is None else self._rank.ctypes.data
         h = C.c_void_p()
-        self._check(self._lib.mxs_mgm2_create(C.byref(cg), C.byref(cp),
-                                              None if self._rank is None else self._rank.ctypes.data,
-                                              self.threshold, favor_code, self.seed & (2 ** 64 - 1), int(device),
-                                              C.byref(h)))
+        if single:
+            self._check(self._lib.mxs_mgm2_create(C.byref(cg), C.byref(cp), rank, self.threshold, favor_code,
+                                                  self.seed & (2 ** 64 - 1), int(device), C.byref(h)))
+        else:
+            self._need_replica_symbols("replicas / seeds need them")
+            self._check(self._lib.mxs_mgm2_create_replicas(C.byref(cg), C.byref(cp), rank, self.threshold, favor_code,
+                                                           sd.ctypes.data, self.replicas, int(device), C.byref(h)))
         self._h = h
+
+    def _need_replica_symbols(self, why):
+        missing = [n for n in REPLICA_SYMBOLS if not hasattr(self._lib, n)]
+        if missing:
+            raise MaxSumGpuError(
+                f"{self._lib._name} was built from sources without MGM-2's replicas (no {', '.join(missing)}): "
+                f"rebuild the library, {why}")
 
     def reset(self):
         self._call("reset")
@@ -58,12 +81,30 @@ class Mgm2Engine(EngineBinding):
     def run(self, n_rounds: int):
         self._call("run", int(n_rounds))
 
-    def state(self) -> dict:
+    def state(self, replica: int = 0) -> dict:
         n = self.graph.n_vars
         out = {"idx": np.empty(n, dtype=np.int32), "cost": np.empty(n), "has_cost": np.empty(n, dtype=np.uint8)}
-        self._call("get_state", *[out[k].ctypes.data for k in ("idx", "cost", "has_cost")])
+        ptrs = [out[k].ctypes.data for k in ("idx", "cost", "has_cost")]
+        if int(replica) == 0:       # (the call every version of the library has)
+            self._call("get_state", *ptrs)
+        else:
+            self._need_replica_symbols("state(replica) needs them")
+            self._call("get_state_replica", int(replica), *ptrs)
         return out
 
-    def assignment(self) -> Tuple[np.ndarray, np.ndarray]:
-        s = self.state()
+    def assignment(self, replica: int = 0) -> Tuple[np.ndarray, np.ndarray]:
+        s = self.state(replica)
         return s["idx"], s["cost"]
+
+    def replica_costs(self, infinity: float = float("inf")) -> Tuple[np.ndarray, np.ndarray]:
+        self._need_replica_symbols("replica_costs needs them")
+        return super().replica_costs(infinity)
+
+    def best(self, infinity: float = float("inf")) -> Dict:
+        """The best replica's current state -- fewest violations, then best cost, then lowest index, ranked on the
+        device: {"replica", "cost", "violations", "idx"}."""
+        self._need_replica_symbols("best needs them")
+        r, cost, viol = C.c_int32(0), C.c_double(0), C.c_int64(0)
+        self._call("best_replica", float(infinity), C.byref(r), C.byref(cost), C.byref(viol))
+        return {"replica": int(r.value), "cost": float(cost.value), "violations": int(viol.value),
+                "idx": self.state(int(r.value))["idx"]}

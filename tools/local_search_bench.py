@@ -31,7 +31,11 @@ library or of `--baseline-lib`: a keyed single run costs the same per round); be
 replicas: "fixed_vs_baseline" (this library's fixed-draw engine against the single side: the same kernel
 instantiations) and "keyed_vs_fixed" (the keyed one-replica engine against the fixed-draw one: what the draw code
 costs; MGM reaches its fixed point after a few rounds, where draw 11 is no longer made, so the row also times the
-first 12 rounds after reset(), "fresh_us_per_round").
+first 12 rounds after reset(), "fresh_us_per_round").  The MGM-2 rows (`--replica-algos mgm2`; "algo": "mgm2",
+Mgm2Engine(replicas=R), mgm2.h) follow the protocol of the MGM rows: the single side is `mxs_mgm2_create` of this
+library or of `--baseline-lib`; per size first "instance_to_instance" (two engines of the single side against each
+other: the spread of the protocol itself) and "single_vs_baseline" (this library's `mxs_mgm2_create` against the single
+side), then one "replicas" row per R.
 """
 import argparse
 import json
@@ -137,6 +141,34 @@ class BaselineMgm:
 
     def close(self):
         self._lib.mxs_mgm_destroy(self._h)
+
+
+class BaselineMgm2:
+    """The MGM-2 engine of ANOTHER build of the library (--baseline-lib): mxs_mgm2_create / _run / _destroy."""
+
+    def __init__(self, path, g, p, seed):
+        import ctypes as C
+        from pydcop_amd.engine import load_library
+        load_library()                       # (the HIP runtime first: the libraries are linked without it)
+        self._lib = C.CDLL(os.path.abspath(path))
+        self._lib.mxs_version.restype = C.c_int32
+        self.version = int(self._lib.mxs_version())
+        self._lib.mxs_mgm2_create.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_int32, C.c_uint64,
+                                              C.c_int32, C.c_void_p]
+        self._lib.mxs_mgm2_run.argtypes = [C.c_void_p, C.c_int32]
+        self._lib.mxs_mgm2_destroy.argtypes = [C.c_void_p]
+        self._g, self._p = g.to_c(), p.to_c()      # (kept alive)
+        self._h = C.c_void_p()
+        rc = self._lib.mxs_mgm2_create(C.byref(self._g), C.byref(self._p), None, 0.5, 0, seed, 0, C.byref(self._h))
+        if rc:
+            raise RuntimeError(f"mxs_mgm2_create of {path}: {rc}")
+
+    def run(self, n):
+        if self._lib.mxs_mgm2_run(self._h, int(n)):
+            raise RuntimeError("mxs_mgm2_run of the baseline library failed")
+
+    def close(self):
+        self._lib.mxs_mgm2_destroy(self._h)
 
 
 def timed_us(eng, cycles):
@@ -271,6 +303,55 @@ def mgm_replica_rows(a):
             single.close()
 
 
+def mgm2_replica_rows(a):
+    for n_vars in a.replica_sizes:
+        g = G.random_coloring(n_vars, seed=0, names=False)
+        p = Params()
+
+        def single_side():
+            if a.baseline_lib:
+                e = BaselineMgm2(a.baseline_lib, g, p, 1)
+                return e, f"mxs_version {e.version}"
+            return Mgm2Engine(g, p, seed=1, lib_path=a.lib), "this"
+
+        base = {"algo": "mgm2", "instance": f"coloring_{n_vars}", "dtype": "f64", "n_vars": n_vars}
+        # two engines of the single side against each other: what the protocol itself spreads
+        left, baseline = single_side()
+        right, _ = single_side()
+        one, other = alternated(a, left, right)
+        print(json.dumps(dict(base, row="instance_to_instance", baseline=baseline, left_us_per_round=one,
+                              right_us_per_round=other, ratio_right_to_left=round(median(other) / median(one), 4))),
+              flush=True)
+        right.close()
+        # this library's mxs_mgm2_create against the single side
+        mine = Mgm2Engine(g, p, seed=1, lib_path=a.lib)
+        one, new = alternated(a, left, mine)
+        print(json.dumps(dict(base, row="single_vs_baseline", baseline=baseline, single_us_per_round=one,
+                              this_us_per_round=new, ratio_this_to_single=round(median(new) / median(one), 4))), flush=True)
+        left.close(), mine.close()
+        for R in a.replicas:
+            single, baseline = single_side()
+            eng = Mgm2Engine(g, p, seed=1, replicas=R, lib_path=a.lib) if R > 1 else \
+                Mgm2Engine(g, p, seeds=[1], replicas=1, lib_path=a.lib)       # (R = 1 through the replica kernels too)
+            one, many = alternated(a, single, eng)
+            row = dict(base, row="replicas", replicas=R, baseline=baseline, single_us_per_round=one,
+                       replicas_us_per_round=many, ratio_R_singles_to_replicas=round(R * median(one) / median(many), 2))
+            reps = max(3, int(0.2 * a.window * 1e6 / max(many[0], 1.0)))
+            t0 = time.perf_counter()
+            for _ in range(reps):
+                dev = eng.replica_costs()
+            row["replica_costs_us"] = round(1e6 * (time.perf_counter() - t0) / reps, 1)
+            reps = max(1, min(reps, 2000 // R))
+            t0 = time.perf_counter()
+            for _ in range(reps):
+                host = [eng.eval_cost(eng.assignment(r)[0]) for r in range(R)]
+            row["host_eval_cost_us"] = round(1e6 * (time.perf_counter() - t0) / reps, 1)
+            assert all(abs(dev[0][r] - host[r][0]) <= 1e-9 * max(1.0, abs(host[r][0])) for r in range(R))
+            print(json.dumps(row), flush=True)
+            eng.close()
+            single.close()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--cycles", type=int, default=500)
@@ -280,20 +361,22 @@ def main():
     ap.add_argument("--mgm2-rounds", type=int, default=200, help="0: no MGM-2 rows")
     ap.add_argument("--gdba-rounds", type=int, default=200, help="0: no GDBA rows")
     ap.add_argument("--dba-rounds", type=int, default=0, help="> 0: only the DBA / GDBA-T / MGM rows on the hard colouring")
-    ap.add_argument("--replicas", type=int, nargs="*", default=[], help="the replica rows only (DSA, MGM): R values")
+    ap.add_argument("--replicas", type=int, nargs="*", default=[], help="the replica rows only (DSA, MGM, MGM-2): R values")
     ap.add_argument("--replica-sizes", type=int, nargs="*", default=[1000, 10_000, 100_000])
     ap.add_argument("--window", type=float, default=1.0, help="seconds per timed window of the replica rows")
     ap.add_argument("--repeats", type=int, default=3)
     ap.add_argument("--warmup", type=float, default=0.5, help="seconds of warm-up per engine of the replica rows")
     ap.add_argument("--baseline-lib", default=None,
                     help="replica rows: the single-seed side from this other build of the library (mxs_dsa_create)")
-    ap.add_argument("--replica-algos", nargs="*", default=["dsa", "mgm"], choices=["dsa", "mgm"])
+    ap.add_argument("--replica-algos", nargs="*", default=["dsa", "mgm"], choices=["dsa", "mgm", "mgm2"])
     a = ap.parse_args()
     if a.replicas:
         if "dsa" in a.replica_algos:
             replica_rows(a)
         if "mgm" in a.replica_algos:
             mgm_replica_rows(a)
+        if "mgm2" in a.replica_algos:
+            mgm2_replica_rows(a)
         return
     if a.dba_rounds > 0:
         return dba_rows(a)
