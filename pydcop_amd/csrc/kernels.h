@@ -34,6 +34,7 @@
 #include <utility>
 
 #include "layout.h"
+#include "send_rule.h"
 
 namespace mxs {
 
@@ -219,19 +220,24 @@ __device__ __forceinline__ T pos_inf() {
 __device__ __forceinline__ double absT(double x) { return fabs(x); }
 __device__ __forceinline__ float absT(float x) { return fabsf(x); }
 
-// approx_match, maxsum.py:688-710, one component (prev is not None).
-template <typename T>
-__device__ __forceinline__ bool comp_match(T c, T prev_c, T stability) {
-    if (prev_c != c) {
-        const T delta = absT(prev_c - c);
-        if (prev_c + c != (T)0) {
-            if (!(((T)2 * delta / absT(prev_c + c)) < stability)) return false;
-        } else {
-            return false;
-        }
-    }
-    return true;
+// min(a, b) as one instruction.  Equal to the reference's `if (best > cur) best = cur`
+// scan for every value but the sign of a zero minimum, which nothing downstream observes.
+// (f64: the instruction itself.  Through __builtin_fmin the compiler first canonicalises every operand it
+// cannot prove canonical -- a `v_max_f64 x, x, x` per value that came out of a lane exchange or a conversion,
+// 120 of the ~1 000 f64 instructions of the n-ary kernel -- to quiet signalling NaNs, which no cost is.)
+__device__ __forceinline__ double min2(double x, double y) {
+#if defined(__HIP_DEVICE_COMPILE__) && MXS_ASM_MIN
+    double r;
+    asm("v_min_f64 %0, %1, %2" : "=v"(r) : "v"(x), "v"(y));
+    return r;
+#else
+    return __builtin_fmin(x, y);
+#endif
 }
+__device__ __forceinline__ float min2(float x, float y) { return __builtin_fminf(x, y); }
+
+// comp_match / msg_match -- approx_match, maxsum.py:688-710, one component / a whole message -- live in
+// send_rule.h: the reference's quotient, divided only where a comparison of products does not settle it.
 
 // apply_damping (maxsum.py:679-685) + the send rule of on_new_cycle
 // (maxsum.py:349-377 / 540-564) on a register-resident message.  On return `m`
@@ -243,10 +249,9 @@ __device__ __forceinline__ uint8_t damp_and_filter(T (&m)[D], const T (&prev)[D]
 #pragma unroll
         for (int d = 0; d < D; ++d) m[d] = damping * prev[d] + ((T)1 - damping) * m[d];
     }
-    bool match = cnt > 0;
-#pragma unroll
-    for (int d = 0; d < D; ++d) match = match && comp_match(m[d], prev[d], stability);
-    if (!match) return 1;                                   // sent (first time)
+    // (no short circuit on cnt: the D decisions are comparisons side by side, not a chain of nested branches)
+    const bool match = (cnt > 0) & msg_match<T, D>(m, prev, stability);
+    if (!match) return 1;                                  // sent (first time)
     if (cnt < SAME_COUNT) return (uint8_t)(cnt + 1);        // sent again
 #pragma unroll
     for (int d = 0; d < D; ++d) m[d] = prev[d];             // not sent: receiver keeps
@@ -436,15 +441,16 @@ __device__ __forceinline__ void factor_binary(const SweepArgs<T>& a, const Class
         if (do0) Msg<T, D>::template load<NT_GATHER>(a.v2f_old + v1, m1);
     }
     T o0[D], o1[D];
+    // The reference's scan `if (best > cur) best = cur` as one min instruction per candidate (min2), the
+    // same bits: a candidate tab + ((T)0 + m) is never -0 (0 + m is not, and a sum is -0 only if both
+    // terms are), `best` starts at +inf and never becomes NaN, and a NaN candidate is ignored both ways.
 #pragma unroll
     for (int x = 0; x < D; ++x) {
         T best0 = pos_inf<T>(), best1 = pos_inf<T>();
 #pragma unroll
         for (int y = 0; y < D; ++y) {
-            const T c0 = tab[x * D + y] + ((T)0 + m1[y]);  // to var 0, value x; other = var 1
-            if (best0 > c0) best0 = c0;
-            const T c1 = tab[y * D + x] + ((T)0 + m0[y]);  // to var 1, value x; other = var 0
-            if (best1 > c1) best1 = c1;
+            best0 = min2(best0, tab[x * D + y] + ((T)0 + m1[y]));  // to var 0, value x; other = var 1
+            best1 = min2(best1, tab[y * D + x] + ((T)0 + m0[y]));  // to var 1, value x; other = var 0
         }
         o0[x] = best0;
         o1[x] = best1;
@@ -566,11 +572,72 @@ __device__ __forceinline__ void factor_generic(const SweepArgs<T>& a, const Clas
 // lane's slot, counter, variable id and previous V->F message are contiguous
 // across lanes (coalesced), then every lane gathers exactly one F->V message --
 // all gathers of the wave are in flight together.  The sums walk the variable's
-// lanes in edge order with cross-lane reads, so the arithmetic order is still the
-// reference's:
+// records in edge order (pack_sums: staged in LDS once, read in chunks), so the
+// arithmetic order is still the reference's:
 //   select_value      maxsum.py:584-620
 //   costs_for_factor  maxsum.py:623-676  (the mean excludes the own cost)
 // ---------------------------------------------------------------------------
+#ifndef MXS_SUM_CHUNK
+#define MXS_SUM_CHUNK 4  // neighbours read per LDS round trip of pack_sums
+#endif
+
+// N neighbours of one component: element j * D of `p` is neighbour j (constant offsets from one
+// address), `own` the position of the lane's own edge among them (anything else: not among them).
+// All N reads are issued before the first addition.  The own edge does not count for `sum_cost` and
+// `md`: it is added as -0.0, the exact additive identity (y + -0.0 == y bit for bit, also for +-0,
+// +-inf and NaN), so the accumulators themselves are never selected.
+template <typename T, int D, int N>
+__device__ __forceinline__ void sum_chunk(const T* p, int own, T& bd, T& md, T& sum_cost) {
+    T x[N];
+#pragma unroll
+    for (int j = 0; j < N; ++j) x[j] = p[j * D];
+#pragma unroll
+    for (int j = 0; j < N; ++j) {
+        bd += x[j];  // select_value: every factor
+        const T others = j == own ? (T)-0.0 : x[j];  // costs_for_factor: every factor but the target
+        sum_cost += others;
+        md += others;
+    }
+}
+
+// The neighbour sums of a packed variable wave: b[d] = c[d] + all F->V messages of the variable,
+// m[d] = c[d] + all but the one of the lane's own edge k, sum_cost = the latter summed over d.  The
+// wave stages its 64 gathered records in its part of g_stage ONCE (the area wave_store_linear
+// uses afterwards; wave barriers separate the uses), then every lane reads the `deg` records of
+// its variable, which start at lane `seg`: whole chunks of MXS_SUM_CHUNK neighbours in a loop, the
+// rest through a wave-uniform choice among fully unrolled bodies -- about deg / chunk LDS round
+// trips per component where a cross-lane read per neighbour paid deg, and no read outside the
+// wave's 64 records (seg + deg <= 64 for a lane with a variable; a padding lane reads its own
+// record).  The order of the additions is the reference's (maxsum.py:607-610, 651-665): d outer,
+// factors inner, `sum_cost` ONE accumulator running through all of it.
+template <typename T, int D>
+__device__ __forceinline__ void pack_sums(const T (&in)[D], const T (&c)[D], int seg, int k, int deg, T (&b)[D],
+                                          T (&m)[D], T& sum_cost) {
+    constexpr int C = MXS_SUM_CHUNK;
+    static_assert(64 * D * sizeof(T) <= STAGE_BYTES_PER_WAVE, "a wave's gathered records fit its staging area");
+    const int w = (int)threadIdx.x >> 6, l = (int)threadIdx.x & 63;
+    T* st = (T*)g_stage[w];
+    __builtin_amdgcn_wave_barrier();  // the previous use of the staging area is over
+#pragma unroll
+    for (int d = 0; d < D; ++d) st[l * D + d] = in[d];
+    __builtin_amdgcn_wave_barrier();
+    const T* first = st + seg * D;
+    sum_cost = (T)0;
+    static_for<D>([&](auto dc) {
+        constexpr int d = decltype(dc)::value;
+        T bd = c[d], md = c[d];
+        const T* p = first + d;
+        int own = k, left = deg;  // `left` is wave-uniform
+        for (; left >= C; left -= C, own -= C, p += C * D) sum_chunk<T, D, C>(p, own, bd, md, sum_cost);
+        static_for<C - 1>([&](auto nc) {
+            constexpr int N = decltype(nc)::value + 1;
+            if (left == N) sum_chunk<T, D, N>(p, own, bd, md, sum_cost);
+        });
+        b[d] = bd;
+        m[d] = md;
+    });
+}
+
 template <typename T, int D, bool P2P = false, int NT = MXS_NT>
 __device__ __forceinline__ void variable_pack(const SweepArgs<T>& a, const ClassInfo& ci, int item) {
     MXS_NT_FLAGS(NT);
@@ -604,23 +671,25 @@ __device__ __forceinline__ void variable_pack(const SweepArgs<T>& a, const Class
     int init = -1;
     if (a.start) init = a.init_idx[v];
     const int seg = l - (has ? k : 0);  // first lane of the variable
-    // d outer / factors inner, as the reference sums (maxsum.py:607-610, 651-665):
-    // sum_cost is ONE accumulator running through all of it
-    T sum_cost = (T)0;
+    T sum_cost;
+#if MXS_SWEEP_SKIP & 1  // (timing experiment: the lane's own record deg times, no staging and no lane crossing)
+    sum_cost = (T)0;
 #pragma unroll
     for (int d = 0; d < D; ++d) {
         T bd = c[d], md = c[d];
         for (int kk = 0; kk < deg; ++kk) {
-            const T x = __shfl(in[d], seg + kk, 64);
-            bd += x;                   // select_value: every factor
-            if (kk != k) {             // costs_for_factor: every factor but the target
-                sum_cost += x;
-                md += x;
+            bd += in[d];
+            if (kk != k) {
+                sum_cost += in[d];
+                md += in[d];
             }
         }
         b[d] = bd;
         m[d] = md;
     }
+#else
+    pack_sums<T, D>(in, c, has ? seg : 0, k, deg, b, m, sum_cost);  // (a padding lane reads variable 0's records)
+#endif
     int best = 0;
     T best_c = b[0];
 #pragma unroll
@@ -1333,22 +1402,6 @@ __device__ __forceinline__ T wave_min(T x) {  // all 64 lanes get the minimum
     }
     return x;
 }
-
-// min(a, b) as one instruction.  Equal to the reference's `if (best > cur) best = cur`
-// scan for every value but the sign of a zero minimum, which nothing downstream observes.
-// (f64: the instruction itself.  Through __builtin_fmin the compiler first canonicalises every operand it
-// cannot prove canonical -- a `v_max_f64 x, x, x` per value that came out of a lane exchange or a conversion,
-// 120 of the ~1 000 f64 instructions of the n-ary kernel -- to quiet signalling NaNs, which no cost is.)
-__device__ __forceinline__ double min2(double x, double y) {
-#if defined(__HIP_DEVICE_COMPILE__) && MXS_ASM_MIN
-    double r;
-    asm("v_min_f64 %0, %1, %2" : "=v"(r) : "v"(x), "v"(y));
-    return r;
-#else
-    return __builtin_fmin(x, y);
-#endif
-}
-__device__ __forceinline__ float min2(float x, float y) { return __builtin_fminf(x, y); }
 
 // Lane moves of the wave reductions below: DPP moves instead of ds_bpermute shuffles, plain VALU moves that do not go
 // through the LDS crossbar (measured: meeting_50k 1168 -> 1099 us, f32 681 -> 655, parity green).  The emulated build
