@@ -9,6 +9,7 @@ import pytest
 from pydcop_amd import generators as G
 from pydcop_amd.dsa import DsaEngine
 from pydcop_amd.graph import Params
+from replica_cost_reference import check_replica_costs
 
 INF = float("inf")
 
@@ -40,7 +41,8 @@ def case_id(c):
 
 def check_costs(eng, replicas, infinity=INF):
     """replica_costs == eval_cost of every replica's assignment (violations exactly, the cost to the bound of
-    compare_dsa: the device folds in another order), and the same bits from call to call"""
+    compare_dsa: the device folds in another order), the same bits from call to call, and both against the plain
+    Python sum of tests/replica_cost_reference.py, to the bound that holds for any summation order"""
     cost, viol = eng.replica_costs(infinity)
     again = eng.replica_costs(infinity)
     assert cost.tobytes() == again[0].tobytes() and viol.tobytes() == again[1].tobytes()
@@ -48,6 +50,7 @@ def check_costs(eng, replicas, infinity=INF):
         c, v = eng.eval_cost(eng.assignment(r)[0], infinity)
         assert viol[r] == v, (r, viol[r], v)
         assert abs(cost[r] - c) <= 1e-9 * max(1.0, abs(c)), (r, cost[r], c)
+    check_replica_costs(eng, replicas, infinity, cost, viol)
     return cost, viol
 
 

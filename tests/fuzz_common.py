@@ -5,7 +5,9 @@ damping_nodes choice, random layout flags) feeds the Max-Sum sweep (`fuzz_maxsum
 DSA and MGM (`fuzz_others`).  `local_instance(seed)` (3..60 or 65..200 variables: a full wave, a second and a
 third block of the thread-per-variable kernels; two or three unequal domain sizes in one graph) feeds MGM-2,
 GDBA and DBA (`fuzz_mgm2`, `fuzz_gdba`, `fuzz_dba`), `dpop_instance(seed)` (4..40 variables, sparse, forests,
-one-value variables, the caller's own tree every fourth seed) feeds DPOP (`fuzz_dpop`).
+one-value variables, the caller's own tree every fourth seed) feeds DPOP (`fuzz_dpop`).  `replica_instance(seed)`
+(local_instance, every third seed 260..520 variables; 1..66 replicas) feeds the replica engines -- DSA, MGM with
+keyed draws, MGM-2 -- with their device costs and their ranking (`fuzz_replicas`).
 `python tests/fuzz_common.py FIRST LAST` runs the seeds FIRST..LAST-1 of every driver on the emulated build;
 tests/test_fuzz_emu.py runs a few of them in the CPU suite, tests/test_gpu_fuzz.py on the GPU."""
 import os
@@ -94,12 +96,14 @@ MAX_TABLE = 16_000                       # entries of one constraint table (and,
 DPOP_MAX_ENTRIES = 300_000
 GDBA_STREAM = 22                         # of the streams 20..35 tried: every GDBA variant raises a modifier and moves within its two GPU seeds
 DPOP_FACTORS = (0.8, 1.8)                # constraints per variable
-GPU_SEEDS = {"mgm2": range(0, 48), "gdba": range(0, 48), "dba": range(0, 48), "dpop": range(0, 40)}   # tests/test_gpu_fuzz.py
+GPU_SEEDS = {"mgm2": range(0, 48), "gdba": range(0, 48), "dba": range(0, 48), "dpop": range(0, 40),
+             "replicas": range(0, 48)}   # tests/test_gpu_fuzz.py
 
 
-def local_instance(seed, dom_set=LOCAL_DOMS, slots=(0.8, 3.2), stream=20):
+def local_instance(seed, dom_set=LOCAL_DOMS, slots=(0.8, 3.2), stream=20, n_vars=None):
     """-> (graph, rng).  Half the seeds 3..60 variables, the other half 65..200 (the halves alternate every 24
-    seeds, so that a seed-indexed choice of period 24 meets both); two or three distinct domain sizes of
+    seeds, so that a seed-indexed choice of period 24 meets both; `n_vars`: a range to draw from, of the seed's own
+    stream, instead); two or three distinct domain sizes of
     `dom_set` in one graph; arities up to 3, up to 4 when every domain is 5 or less, fewer where a table would
     pass MAX_TABLE entries; `slots`: the range of constraints a variable is in, on average (or a function
     of the drawn domain sizes that gives it); `stream`: which random stream of the seed."""
@@ -107,6 +111,8 @@ def local_instance(seed, dom_set=LOCAL_DOMS, slots=(0.8, 3.2), stream=20):
     rng = np.random.default_rng([seed, stream])
     big = (seed + seed // 24) % 2 == 1
     nv = int(rng.integers(65, 201)) if big else int(rng.integers(3, 61))
+    if n_vars is not None:
+        nv = int(np.random.default_rng([seed, stream, 1]).integers(n_vars[0], n_vars[1] + 1))
     doms = tuple(int(x) for x in rng.choice(dom_set, size=int(rng.integers(2, 4)), replace=False))
     top = max(doms)
     max_arity = int(rng.integers(2, 5 if top <= 5 else 4))
@@ -340,12 +346,95 @@ def fuzz_dpop(seed, lib_path):
     compare_dpop(OracleDpop, g, p, lib_path=lib_path, tree=tree)
 
 
+# ---- the replica engines: DSA, MGM with keyed draws, MGM-2, R seeded runs in one engine ----------------------
+REPLICA_STREAM = 23
+REPLICA_COUNTS = (1, 2, 3, 5, 66)        # 66: a second block of the final cost reduction (64 replicas per block)
+REPLICA_LARGE = (260, 520)               # variables: the init and the cost launches span blocks
+REPLICA_STEPS_LARGE = (0, 1, 3)
+
+
+def replica_instance(seed):
+    """-> (graph, Params, R, {engine: kwargs}, compared replicas, steps).  local_instance; every third seed 260..520
+    variables, two replicas compared (the first and the last: the Python oracles dominate) over fewer rounds; else
+    every replica up to five, of 66 the two first and the two last (on either side of the second block of 64)."""
+    from mgm2_oracle import FAVORS
+    large = seed % 3 == 2
+    g, _ = local_instance(seed, stream=REPLICA_STREAM, n_vars=REPLICA_LARGE if large else None)
+    rng = np.random.default_rng([seed, REPLICA_STREAM, 2])
+    p = Params(mode="max" if rng.integers(0, 2) else "min", dtype="f32" if rng.integers(0, 3) == 0 else "f64")
+    replicas = int(rng.choice(REPLICA_COUNTS))
+    kws = {"dsa": dict(variant="ABC"[int(rng.integers(0, 3))], probability=float(rng.choice([0.3, 0.7, 1.0])),
+                       p_mode=["fixed", "arity"][int(rng.integers(0, 2))]),
+           "mgm": {},
+           "mgm2": dict(favor=FAVORS[int(rng.integers(0, 3))], threshold=float(rng.choice([0.0, 0.3, 0.5, 0.6, 1.0])))}
+    if large:
+        compared = sorted({0, replicas - 1})
+    else:
+        compared = list(range(replicas)) if replicas <= 5 else [0, 1, replicas - 2, replicas - 1]
+    return g, p, replicas, kws, compared, REPLICA_STEPS_LARGE if large else STEPS
+
+
+def fuzz_replicas(seed, lib_path):
+    """the three replica engines on replica_instance(seed): every compared replica against its single-seed oracle
+    bit for bit after every step, all replica costs against tests/replica_cost_reference.py, best() against the
+    winner derived from the reference costs (either one where two of them lie within the bound of each other)"""
+    from replica_cost_reference import acceptable_winners, check_replica_costs, is_exact
+    from replica_shapes_common import ENGINES, same_fields
+    g, p, replicas, kws, compared, steps = replica_instance(seed)
+    for name, E in ENGINES.items():
+        kw = kws[name]
+        eng = E["engine"](g, p, kw, seed=seed, seeds=[seed + r for r in range(replicas)], replicas=replicas,
+                          lib_path=lib_path)
+        oras = {r: E["oracle"](g, p, kw, seed + r) for r in compared}
+        done = 0
+        for n in steps:
+            eng.run(n)
+            done += n
+            for o in oras.values():
+                o.run(n)
+            same_fields(E, eng, oras, f"{name} after {done} rounds")
+            refs = check_replica_costs(eng, range(replicas))
+        if name == "dsa":
+            eng.track_best(0)
+        b = eng.best()
+        w, ok = acceptable_winners([refs[r] for r in range(replicas)], p.mode == "max", is_exact(g, p))
+        assert b["replica"] in ok, (name, b["replica"], w, ok)
+        assert b["violations"] == refs[b["replica"]][1]
+        np.testing.assert_array_equal(b["idx"], refs[b["replica"]][4])
+        eng.close()
+        for o in oras.values():
+            o.close()
+
+
+def replica_summary(seed):
+    """what the oracles alone show of fuzz_replicas(seed): DSA's C oracle for EVERY replica (the Python oracles of
+    the other two are too slow for 66 runs), the reference costs of its final states"""
+    from oracle.dsa_oracle import OracleDsa
+    from replica_cost_reference import CHUNK, acceptable_winners, is_exact, reference_cost
+    g, p, replicas, kws, compared, steps = replica_instance(seed)
+    starts, finals, refs = [], [], []
+    for r in range(replicas):
+        o = OracleDsa(g, p, seed=seed + r, **kws["dsa"])
+        starts.append(o.assignment()[0].copy())
+        o.run(sum(steps))
+        finals.append(o.assignment()[0].copy())
+        refs.append(reference_cost(g, p, finals[-1]) + (finals[-1],))
+        o.close()
+    w, ok = acceptable_winners(refs, p.mode == "max", is_exact(g, p))
+    return dict(cost_blocks=-(-(g.n_factors + g.n_vars) // CHUNK), replicas=replicas, n_vars=g.n_vars,
+                f32_float_tables=p.dtype == "f32" and bool((g.tables != g.tables.astype(np.float32)).any()),
+                start_apart=any((s != starts[0]).any() for s in starts), end_apart=any((f != finals[0]).any() for f in finals),
+                ambiguous_winner=len(ok) > 1, compared=compared)
+
+
 # ---- what the oracles alone show of the sweep (tests/test_fuzz_emu.py asserts that it is not vacuous) ----
 def oracle_summary(engine, seed, steps=STEPS):
     from dba_oracle import OracleDba
     from dpop_oracle import OracleDpop
     from gdba_oracle import OracleGdba
     from mgm2_oracle import OracleMgm2
+    if engine == "replicas":
+        return replica_summary(seed)
     if engine == "dba":
         g, p, kw = dba_instance(seed)
         o, failed = OracleDba(g, p, **kw), False
@@ -384,7 +473,7 @@ def small_seeds(make, n=5, max_vars=20, ok=lambda *inst: True):
     return out
 
 
-DRIVERS = (fuzz_maxsum, fuzz_others, fuzz_mgm2, fuzz_gdba, fuzz_dba, fuzz_dpop)
+DRIVERS = (fuzz_maxsum, fuzz_others, fuzz_mgm2, fuzz_gdba, fuzz_dba, fuzz_dpop, fuzz_replicas)
 
 
 if __name__ == "__main__":

@@ -1,7 +1,8 @@
 """A slice of the random-instance sweep of tests/fuzz_common.py (emulated engine build against the
 oracles, bit for bit): the Max-Sum sweep, asynchronous Max-Sum, DSA and MGM on domains 1..17, arities 1..4,
 every mode / precision / start / damping choice; MGM-2, GDBA, DBA and DPOP on the instances of
-`local_instance` / `dpop_instance` and on every constructed instance of tests/edge_shapes.py; and what the
+`local_instance` / `dpop_instance` and on every constructed instance of tests/edge_shapes.py; the replica engines
+(DSA, MGM with keyed draws, MGM-2: replicas, device costs, ranking) on those of `replica_instance`; and what the
 oracles alone must show over the seeds of tests/test_gpu_fuzz.py for that sweep to prove anything."""
 import pytest
 
@@ -58,6 +59,11 @@ def test_fuzz_dpop_emu(seed, emu_lib):
     fuzz_common.fuzz_dpop(seed, emu_lib)
 
 
+@pytest.mark.parametrize("seed", range(0, 12))
+def test_fuzz_replicas_emu(seed, emu_lib, oracle_built):
+    fuzz_common.fuzz_replicas(seed, emu_lib)
+
+
 @pytest.mark.parametrize("edge", edge_shapes.all_edges(), ids=lambda e: e[0])
 def test_edge_shapes_emu(edge, emu_lib, oracle_built):
     edge[1](emu_lib)
@@ -105,6 +111,23 @@ def test_the_sweep_is_not_vacuous(engine, oracle_built):
         moved = sum(r["pair_moves"] > 0 for r in inner)
         print(f"mgm2: {moved} of {len(inner)} seeds with 0 < threshold < 1 see a committed pair move")
         assert inner and 2 * moved >= len(inner)
+    elif engine == "replicas":
+        blocks = [s for s, r in zip(seeds, rows) if r["cost_blocks"] >= 2]
+        init_blocks = [s for s, r in zip(seeds, rows) if r["n_vars"] > 256]
+        many = [s for s, r in zip(seeds, rows) if r["replicas"] == 66]
+        narrowed = [s for s, r in zip(seeds, rows) if r["f32_float_tables"]]
+        apart = [s for s, r in zip(seeds, rows) if r["start_apart"] and r["end_apart"]]
+        ambiguous = [s for s, r in zip(seeds, rows) if r["ambiguous_winner"]]
+        print(f"replicas: {len(blocks)} of {n} seeds with two or more cost blocks {blocks}, {len(init_blocks)} over 256 "
+              f"variables, {len(many)} with 66 replicas {many}, {len(narrowed)} in f32 on tables that are not f32-exact "
+              f"{narrowed}, {len(apart)} whose replicas start apart and end apart, {len(ambiguous)} whose two best "
+              f"reference costs lie within the bound of each other {ambiguous}")
+        assert blocks and many and narrowed and apart
+        assert len(init_blocks) == len([s for s in seeds if s % 3 == 2])
+        assert any(s in blocks for s in many) and any(r["replicas"] > 1 for s, r in zip(seeds, rows) if s in blocks)
+        assert 2 * len(apart) >= len([r for r in rows if r["replicas"] > 1])
+        assert 10 * len(ambiguous) < n
+        assert {r["replicas"] for r in rows} == set(fuzz_common.REPLICA_COUNTS)
     else:
         wide = sum(r["widest"] >= 2 for r in rows)
         ones = sum(r["one_value_in_separator"] for r in rows)

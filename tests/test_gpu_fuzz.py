@@ -2,7 +2,9 @@
 sweep, asynchronous Max-Sum, DSA, MGM, MGM-2, GDBA, DBA, DPOP) against its oracle, bit for bit, on
 instances nobody picked (domains 1..17, arities 1..4, every mode / precision / start / damping choice,
 random layout flags; for the four newer engines up to 200 variables, unequal neighbour domains up to 65
-values and every algorithm parameter), and the constructed edge instances of tests/edge_shapes.py."""
+values and every algorithm parameter; DSA, MGM with keyed draws and MGM-2 as 1..66 replicas of one engine on up
+to 520 variables, with their device costs and their ranking), and the constructed edge instances of
+tests/edge_shapes.py."""
 import pytest
 
 import edge_shapes
@@ -48,6 +50,11 @@ def test_fuzz_dba(seed):
 @pytest.mark.parametrize("seed", fuzz_common.GPU_SEEDS["dpop"])
 def test_fuzz_dpop(seed):
     fuzz_common.fuzz_dpop(seed, None)
+
+
+@pytest.mark.parametrize("seed", fuzz_common.GPU_SEEDS["replicas"])
+def test_fuzz_replicas(seed, oracle_built):
+    fuzz_common.fuzz_replicas(seed, None)
 
 
 @pytest.mark.parametrize("edge", edge_shapes.all_edges(), ids=lambda e: e[0])
