@@ -679,6 +679,10 @@ int mxs_gdba_get_state(mxs_gdba *e, int32_t *idx, double *cost, uint8_t *has_cos
 int mxs_gdba_get_modifiers(mxs_gdba *e, int32_t slot, int32_t *out, int64_t capacity, int64_t *n_entries);
 int mxs_gdba_eval_cost(mxs_gdba *e, const int32_t *idx, double infinity, double *cost, int64_t *violations);
 int mxs_gdba_destroy(mxs_gdba *e);
+/* REPLICAS and BEST STATE: n seeded runs of the instance in one engine (create_replicas, replicas, get_state_replica,
+ * get_modifiers_replica, replica_costs) and every run's best state kept on the device (track_best, get_best) are
+ * declared and documented in maxsum_gpu_gdba_replicas.h, in the style of the MGM-2 block above. */
+#include "maxsum_gpu_gdba_replicas.h"
 
 /* ---- DBA (pydcop/algorithms/dba.py) on the same flat arrays: Distributed Breakout, satisfaction only ----
  * One round = the two phases of DbaComputation for every variable: ok (:366-445: eval(x) = the sum of
@@ -721,8 +725,9 @@ int mxs_dba_destroy(mxs_dba *e);
 /* Library/ABI version (major*100+minor).  270 also covers the MGM additions made after it was set -- mxs_mgm_create_keyed,
  * mxs_mgm_replicas, mxs_mgm_get_state_replica, mxs_mgm_replica_costs, mxs_mgm_best_replica -- and the MGM-2 additions
  * after those -- mxs_mgm2_create_replicas, mxs_mgm2_replicas, mxs_mgm2_get_state_replica, mxs_mgm2_replica_costs,
- * mxs_mgm2_best_replica: a binding that needs them looks the symbols up instead of comparing versions (pydcop_amd/mgm.py
- * and pydcop_amd/mgm2.py do, and say so when they are missing). */
+ * mxs_mgm2_best_replica -- and the GDBA additions of maxsum_gpu_gdba_replicas.h: a binding that needs them looks the
+ * symbols up instead of comparing versions (pydcop_amd/mgm.py, pydcop_amd/mgm2.py and pydcop_amd/gdba.py do, and say so
+ * when they are missing). */
 int32_t mxs_version(void);
 
 /* What this binary is: 1 = the product, compiled by hipcc for gfx950; 0 = the host

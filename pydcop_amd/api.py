@@ -59,11 +59,14 @@ def _engine_for(graph: FlatGraph, params: Params, device: int, devices: int, lib
 
 
 def _algo_kw(algo, variant, probability, p_mode, seed, threshold, favor, modifier="A", violation="NZ",
-             increase_mode="E", dba_infinity=10000, max_distance=50, restarts=1, draws="fixed"):
+             increase_mode="E", dba_infinity=10000, max_distance=50, restarts=1, draws="fixed", best_every=0):
     if algo == "dba":
         return dict(infinity=dba_infinity, max_distance=max_distance, seed=seed)
     if algo == "gdba":
-        return dict(modifier=modifier, violation=violation, increase_mode=increase_mode, seed=seed)
+        kw = dict(modifier=modifier, violation=violation, increase_mode=increase_mode, seed=seed)
+        if int(restarts) != 1 or int(best_every) != 0:      # (else one run: mxs_gdba_create, as ever)
+            kw.update(seeds=[int(seed) + r for r in range(int(restarts))])
+        return kw
     if algo == "dsa":
         return dict(variant=variant, probability=probability, p_mode=p_mode, seed=seed, replicas=int(restarts))
     if algo == "mgm2":
@@ -96,16 +99,19 @@ def _check_restarts(algo, restarts, best_every, draws="fixed"):
         raise ValueError("draws must be \"fixed\" or \"keyed\"")
     if draws != "fixed" and algo != "mgm":
         raise ValueError("draws: algo=\"mgm\" only (the other local searches always key their draws on `seed`)")
-    if int(restarts) != 1 and not (algo in ("dsa", "mgm2") or (algo == "mgm" and draws == "keyed")):
-        raise ValueError("restarts: algo=\"dsa\" or \"mgm2\", or algo=\"mgm\" with draws=\"keyed\"")
-    if algo != "dsa" and int(best_every) != 0:
-        raise ValueError("best_every: algo=\"dsa\" only")
+    # (a GDBA run's final state is usually not its best: restarts without records would rank wandering states)
+    if int(restarts) != 1 and not (algo in ("dsa", "mgm2") or (algo == "mgm" and draws == "keyed")
+                                   or (algo == "gdba" and int(best_every) >= 1)):
+        raise ValueError("restarts: algo=\"dsa\" or \"mgm2\", algo=\"mgm\" with draws=\"keyed\", or algo=\"gdba\" with "
+                         "best_every >= 1")
+    if algo not in ("dsa", "gdba") and int(best_every) != 0:
+        raise ValueError("best_every: algo=\"dsa\" or \"gdba\" only")
 
 
 def _dsa_best(eng, algo, restarts, best_every, infinity):
-    """algo="dsa" with restarts / best_every: (idx of the best replica -- its record when tracking, else its final
-    state --, the result's extra keys); the device cost only ranks.  Else None."""
-    if algo != "dsa" or (int(restarts) == 1 and int(best_every) == 0):
+    """algo="dsa" or "gdba" with restarts / best_every: (idx of the best replica -- its record when tracking, else its
+    final state --, the result's extra keys); the device cost only ranks.  Else None."""
+    if algo not in ("dsa", "gdba") or (int(restarts) == 1 and int(best_every) == 0):
         return None
     if int(best_every) == 0:
         eng.track_best(0, infinity)         # (no records: ranks the final states)
@@ -181,15 +187,20 @@ def solve_dcop(dcop, cycles: int = 30, *, damping: float = 0.5, damping_nodes: s
     descends on never rises, so a run's final state is already its best and there is nothing to track.
 
     algo="mgm2": `restarts` = R seeded runs (seeds seed .. seed + R - 1) in one engine, the same way: the assignment is
-    the best run's final state and the result gains "replica" and "replica_costs"."""
+    the best run's final state and the result gains "replica" and "replica_costs".
+
+    algo="gdba": `best_every` = k > 0 and `restarts` as for DSA, rounds in place of cycles: the assignment is the best
+    record of the best run and the result gains "replica", "best_cycle" and "replica_costs".  A GDBA run is not
+    monotone (the breakout makes the assignment wander, its final state is usually not its best), so `restarts` > 1
+    requires `best_every` >= 1."""
     _check_restarts(algo, restarts, best_every, draws)
     graph = compile_dcop(dcop, noise=noise if algo in ("maxsum", "amaxsum") else 0.0, seed=seed)
     params = Params(mode=dcop.objective, damping=damping, damping_nodes=damping_nodes,
                     stability=stability, start_messages=start_messages, dtype=precision)
     algo_kw = _algo_kw(algo, variant, probability, p_mode, seed, threshold, favor, modifier, violation, increase_mode,
-                       dba_infinity, max_distance, restarts, draws)
+                       dba_infinity, max_distance, restarts, draws, best_every)
     with _engine_for(graph, params, device, devices, lib_path, algo, algo_kw) as eng:
-        if algo == "dsa" and int(best_every) > 0:
+        if algo in ("dsa", "gdba") and int(best_every) > 0:
             eng.track_best(int(best_every), infinity)
         curve = _run_and_trace(eng, algo, cycles, cost_every, infinity)
         idx, _ = eng.assignment()
@@ -220,9 +231,9 @@ def solve_flat(graph: FlatGraph, objective: str = "min", cycles: int = 30, *, da
                     stability=stability, start_messages=start_messages, dtype=precision)
     _check_restarts(algo, restarts, best_every, draws)
     algo_kw = _algo_kw(algo, variant, probability, p_mode, seed, threshold, favor, modifier, violation, increase_mode,
-                       dba_infinity, max_distance, restarts, draws)
+                       dba_infinity, max_distance, restarts, draws, best_every)
     with _engine_for(graph, params, device, devices, lib_path, algo, algo_kw) as eng:
-        if algo == "dsa" and int(best_every) > 0:
+        if algo in ("dsa", "gdba") and int(best_every) > 0:
             eng.track_best(int(best_every), infinity)
         curve = _run_and_trace(eng, algo, cycles, cost_every, infinity)
         idx, _ = eng.assignment()

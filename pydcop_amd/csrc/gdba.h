@@ -18,6 +18,18 @@
 // constraint's own table, always live: one counter per slot.  The increase runs a wave at a time: the lanes of a
 // wave take the entries of one stuck variable's row (R) or slab (C) side by side.
 // Counters are 16 bits wide: a counter grows by at most 1 per round, and run() refuses to go past 65535 rounds.
+//
+// REPLICAS (mxs_gdba_create_replicas): R seeded runs advance with the same two launches, as in mgm2.h.  The two
+// phases are __device__ bodies (eval_phase, decide_phase) with two sets of __global__ entry points: k_gdba_* on the
+// plain Dev -- what mxs_gdba_create launches, argument layout and grid as before -- and k_gdbar_* on DevR, where the
+// replica is folded into blockIdx.x (block = r * bpr + b, replica_cost.h) and the block's copy of the argument moves
+// once to replica r's slices of the dynamic state and takes seeds[r] (enter_replica).  A block is one wave of ONE
+// replica, so the ballot / shuffle loop of the decide phase never mixes replicas.  Everything static is stored once;
+// the state is [R][n_vars] in GRAPH order, viol / slot_vc [R][n_slots], the modifier pool [R][plan.entries] (mod_off
+// stays per slot).  The start state is drawn on the device (k_gdbar_init).  A GDBA run is not monotone -- the breakout
+// makes the assignment wander -- so the best state every replica has shown is kept on the device: the solution costs
+// are reduced by replica_cost.h's kernels, k_gdbar_best_copy takes the snapshot; the refusals, the allocations that
+// grow with R and the cost launches are replica_host.h's.
 #pragma once
 
 namespace gdba {
@@ -65,6 +77,35 @@ struct Dev {
     T* slot_vc;                     // [n_slots] vars_cost after the slot, this round (written and read by the owner only)
 };
 
+// what the replica engine's kernels take: Dev plus the replicas.  The single-run kernels keep the plain Dev, i.e.
+// their argument layout.  The per-replica arrays of Dev -- cur, cost, has_cost, rec -- are [replicas][n_vars], viol and
+// slot_vc [replicas][n_slots], pool [replicas][n_pool]; `seed` is filled per block from seeds[r] (enter_replica).
+template <typename T>
+struct DevR : Dev<T> {
+    int32_t bpr;               // blocks per replica of the launch being made (block = replica * bpr + b)
+    int32_t n_rep;
+    int64_t n_slots, n_pool;   // a replica's share of viol / slot_vc and of the pool
+    const uint64_t* seeds;     // [replicas]
+    // what k_cost_partial (replica_cost.h) reads of its G: the constraints' CSR and q, here the identity -- the
+    // state is in graph order
+    const int32_t *dom_size, *factor_rowptr, *edge_var, *q;
+    const int64_t* table_off;
+};
+
+// the replica of this block: the block's copy of DevR (kernel arguments, block-uniform) moves to the replica's slices
+// of the dynamic state and takes its seed, so that nothing below knows about replicas
+template <typename T>
+__device__ inline int enter_replica(DevR<T>& g, int* b) {
+    const int r = repcost::replica_of_block<true>(g, b);
+    const int64_t off = (int64_t)r * g.n_vars, soff = (int64_t)r * g.n_slots;
+    g.cur += off, g.cost += off, g.has_cost += off, g.rec += off;
+    g.viol += soff;
+    if (g.has_var_cost) g.slot_vc += soff;
+    g.pool += (int64_t)r * g.n_pool;
+    g.seed = g.seeds[r];
+    return r;
+}
+
 // the offset the OTHER scope variables' current values contribute to the slot's table index
 template <typename T>
 __device__ inline int64_t others_offset(const Dev<T>& g, int s) {
@@ -107,8 +148,7 @@ __device__ inline T eval_at(const Dev<T>& g, int v, int x, bool mark) {
 }
 
 template <typename T>
-__global__ void __launch_bounds__(TPB) k_gdba_eval(Dev<T> g) {
-    const int v = blockIdx.x * blockDim.x + threadIdx.x;
+__device__ __forceinline__ void eval_phase(const Dev<T>& g, const int v) {
     if (v >= g.n_vars || !g.has_nb[v]) return;
     const int D = g.dom[v], cv = g.cur[v];
     // vars_cost does not depend on the candidate value: once per slot and round, not once per (value, slot)
@@ -183,9 +223,9 @@ __device__ inline void increase_violated(const Dev<T>& g, int w, int cw, int lan
     }
 }
 
+// (every lane of the wave comes here, the ones past n_vars too: the ballot below is the wave's)
 template <typename T>
-__global__ void __launch_bounds__(TPB) k_gdba_decide(Dev<T> g) {
-    const int v = blockIdx.x * blockDim.x + threadIdx.x;
+__device__ __forceinline__ void decide_phase(const Dev<T>& g, const int v) {
     const int lane = threadIdx.x & 63;
     const bool plays = v < g.n_vars && g.has_nb[v];
     bool stuck = false;
@@ -230,6 +270,76 @@ __global__ void __launch_bounds__(TPB) k_gdba_decide(Dev<T> g) {
     }
 }
 
+// ---- the entry points.  The single-run kernels: the plain Dev, the thread's index from blockIdx.x alone -- what
+// mxs_gdba_create has always launched.
+template <typename T>
+__global__ void __launch_bounds__(TPB) k_gdba_eval(Dev<T> g) {
+    const int v = blockIdx.x * blockDim.x + threadIdx.x;
+    eval_phase(g, v);
+}
+template <typename T>
+__global__ void __launch_bounds__(TPB) k_gdba_decide(Dev<T> g) {
+    const int v = blockIdx.x * blockDim.x + threadIdx.x;
+    decide_phase(g, v);
+}
+
+// The replica kernels (mxs_gdba_create_replicas): R runs per launch, whole blocks (one wave each) belong to one
+// replica (block = r * bpr + b); below enter_replica the phase code is the single run's.
+template <typename T>
+__global__ void __launch_bounds__(TPB) k_gdbar_eval(DevR<T> g) {
+    int b;
+    enter_replica(g, &b);
+    eval_phase<T>(g, b * (int)blockDim.x + (int)threadIdx.x);
+}
+template <typename T>
+__global__ void __launch_bounds__(TPB) k_gdbar_decide(DevR<T> g) {
+    int b;
+    enter_replica(g, &b);
+    decide_phase<T>(g, b * (int)blockDim.x + (int)threadIdx.x);
+}
+
+// the start state of every replica (on_start, :302-333), thread per (replica, variable): a variable with neighbours
+// keeps its initial value (the same in every replica) or takes int(u * D_v), u: draw D_START of cycle 0 under
+// seeds[r]; one without takes iso_val / iso_cost (optimal_cost_value, replica_host.h's start_values) and holds
+// that cost.  The pool and viol are cleared by the host's memsets.
+constexpr int AUX_TPB = rephost::AUX_TPB;
+template <typename T>
+__global__ void __launch_bounds__(AUX_TPB) k_gdbar_init(DevR<T> g, const int32_t* init, const int32_t* iso_val,
+                                                        const T* iso_cost) {
+    int b;
+    enter_replica(g, &b);
+    const int v = b * (int)blockDim.x + (int)threadIdx.x;
+    if (v >= g.n_vars) return;
+    const int iso = iso_val[v];
+    int x = iso;
+    if (iso < 0) x = init[v] >= 0 ? init[v] : (int)(uniform(g.seed, v, 0, D_START) * g.dom[v]);
+    g.cur[v] = x;
+    g.cost[v] = iso >= 0 ? iso_cost[v] : (T)0;
+    g.has_cost[v] = iso >= 0 ? 1 : 0;
+    Rec<T> r;
+    r.improve = (T)0;
+    r.newv = x;
+    g.rec[v] = r;
+}
+
+// the best state a replica has shown (mxs_gdba_track_best): a launch of its own, after k_cost_final in stream order.
+// The replicas that improved copy their state (graph order, as stored) and take the new record; nothing in this
+// launch reads a record.
+using repcost::BestRec;
+__global__ void __launch_bounds__(AUX_TPB) k_gdbar_best_copy(int n_vars, int bpr, const int32_t* cur, const double* cost,
+                                                             const long long* viol, long long round, BestRec best) {
+    const int r = (int)(blockIdx.x / (unsigned)bpr);
+    const int b = (int)blockIdx.x - r * bpr;
+    if (!best.improved[r]) return;
+    const int i = b * (int)blockDim.x + (int)threadIdx.x;
+    if (i < n_vars) best.idx[(int64_t)r * n_vars + i] = cur[(int64_t)r * n_vars + i];
+    if (i == 0) {
+        best.cost[r] = cost[r];
+        best.viol[r] = viol[r];
+        best.cycle[r] = round;
+    }
+}
+
 // The host plan of the modifier pool: which slots are live, where their counters start, how many there are
 struct Plan {
     std::vector<int64_t> mod_off, size;  // per slot: offset (-1: none) and number of counters
@@ -265,16 +375,101 @@ struct Plan {
     }
 };
 
+// ---- the host side the two engines share
+inline int check_params(int32_t modifier, int32_t violation, int32_t increase_mode, int64_t* budget) {
+    if (modifier < 0 || modifier > 1) return fail(MXS_E_INVALID, "gdba: modifier must be 0 (A) or 1 (M)");
+    if (violation < 0 || violation > 2) return fail(MXS_E_INVALID, "gdba: violation must be 0 (NZ), 1 (NM) or 2 (MX)");
+    if (increase_mode < 0 || increase_mode > 3)
+        return fail(MXS_E_INVALID, "gdba: increase_mode must be 0 (E), 1 (R), 2 (C) or 3 (T)");
+    if (*budget < 0) return fail(MXS_E_INVALID, "gdba: negative pool budget");
+    if (*budget == 0) *budget = DEFAULT_POOL_BUDGET;
+    return MXS_OK;
+}
+
+// after hg.load: no empty table, finite tables and variable costs; any_vc: some variable cost is non-zero
+inline int check_graph(const mxs_host::HostGraph& hg, bool* any_vc) {
+    for (int f = 0; f < hg.nF; ++f)
+        if (hg.toff[f + 1] <= hg.toff[f]) return fail(MXS_E_INVALID, "empty table");
+    // maxi over NaN improvements depends on message arrival in the reference: no defined result
+    for (double t : hg.tables)
+        if (!std::isfinite(t)) return fail(MXS_E_INVALID, "gdba: constraint tables must be finite (no inf / NaN entries)");
+    *any_vc = false;
+    for (double c : hg.var_cost) {
+        if (!std::isfinite(c)) return fail(MXS_E_INVALID, "gdba: variable costs must be finite (no inf / NaN entries)");
+        *any_vc |= c != 0.0;
+    }
+    return MXS_OK;
+}
+
+// neighbours: the other variables of v's constraints (the concerned list holds v itself once); the first slot of
+// v's list that holds each concerned variable (v itself: slot 0, every scope holds it)
+inline void neighbourhood(const mxs_host::HostGraph& hg, const lsearch::HostSlots& hs, std::vector<int32_t>& h_nb,
+                          std::vector<int32_t>& h_first) {
+    const int nV = hg.nV;
+    h_nb.assign(nV, 0);
+    h_first.assign(hs.conc_var.size(), 0);
+    for (int v = 0; v < nV; ++v) {
+        const int c0 = hs.conc_rowptr[v], c1 = hs.conc_rowptr[v + 1];
+        h_nb[v] = c1 - c0 > 1;
+        for (int k = c0; k < c1; ++k) {
+            const int u = hs.conc_var[k];
+            int first = 0;
+            if (u != v)
+                for (int s = hg.vrow[v]; s < hg.vrow[v + 1]; ++s) {
+                    bool in = false;
+                    for (int q = hs.nb_rowptr[s]; q < hs.nb_rowptr[s + 1]; ++q) in |= hs.nb_var[q] == u;
+                    if (in) {
+                        first = s - hg.vrow[v];
+                        break;
+                    }
+                }
+            h_first[k] = first;
+        }
+    }
+}
+
+// what a raw entry is compared with (_is_violated, :552-572), per slot: 0 (NZ), min / max over the flattened table
+template <typename T>
+std::vector<T> violation_refs(const mxs_host::HostGraph& hg, size_t n_slots, int32_t violation) {
+    std::vector<T> h_vref(n_slots, (T)0);
+    if (violation == VIO_NZ) return h_vref;
+    std::vector<T> fref(hg.nF);
+    for (int f = 0; f < hg.nF; ++f) {
+        T r = (T)hg.tables[hg.toff[f]];
+        for (int64_t i = hg.toff[f]; i < hg.toff[f + 1]; ++i) {
+            const T t = (T)hg.tables[i];
+            if (violation == VIO_NM ? t < r : t > r) r = t;
+        }
+        fref[f] = r;
+    }
+    for (size_t s = 0; s < n_slots; ++s) h_vref[s] = fref[hg.efac[hg.vedges[s]]];
+    return h_vref;
+}
+
 struct Base {
     virtual ~Base() = default;
-    virtual int init(const mxs_graph& g, const mxs_params& p, const int32_t* rank, const int32_t* vrank, int32_t modifier,
-                     int32_t violation, int32_t increase_mode, uint64_t seed, int64_t budget, int device) = 0;
+    // mxs_gdba_create (Engine) / mxs_gdba_create_replicas (ReplicaEngine)
+    virtual int init(const mxs_graph&, const mxs_params&, const int32_t*, const int32_t*, int32_t, int32_t, int32_t, uint64_t,
+                     int64_t, int) {
+        return fail(MXS_E_STATE, "gdba: not the single-run engine");
+    }
+    virtual int init(const mxs_graph&, const mxs_params&, const int32_t*, const int32_t*, int32_t, int32_t, int32_t,
+                     const uint64_t*, int32_t, int64_t, int) {
+        return fail(MXS_E_STATE, "gdba: not the replica engine");
+    }
     virtual int reset() = 0;
     virtual int run(int32_t n) = 0;
-    virtual int get_state(int32_t* idx, double* cost, uint8_t* has_cost, double* improve, int32_t* newv) = 0;
-    virtual int get_modifiers(int32_t slot, int32_t* out, int64_t capacity, int64_t* n) = 0;
+    virtual int get_state(int32_t r, int32_t* idx, double* cost, uint8_t* has_cost, double* improve, int32_t* newv) = 0;
+    virtual int get_modifiers(int32_t r, int32_t slot, int32_t* out, int64_t capacity, int64_t* n) = 0;
     virtual int eval_cost(const int32_t* idx, double infinity, double* cost, int64_t* viol) = 0;
+    virtual int replica_costs(double infinity, double* cost, int64_t* viol) = 0;
+    // the best state is the replica engine's (mxs_gdba_create_replicas, one replica included)
+    virtual int track_best(int32_t, double) { return fail(MXS_E_STATE, "gdba: the best state is tracked by the replica engine"); }
+    virtual int get_best(int32_t, int32_t*, int64_t*, double*, int64_t*, int32_t*) {
+        return fail(MXS_E_STATE, "mxs_gdba_get_best before mxs_gdba_track_best");
+    }
     int64_t rounds = 0;
+    int32_t n_rep = 1;
 };
 
 template <typename T>
@@ -302,69 +497,23 @@ struct Engine : Base {
              int32_t violation, int32_t increase_mode, uint64_t seed, int64_t budget, int dev) override {
         device = dev;
         if (int rc = mxs_host::open_device(dev, &stream)) return rc;
-        if (modifier < 0 || modifier > 1) return fail(MXS_E_INVALID, "gdba: modifier must be 0 (A) or 1 (M)");
-        if (violation < 0 || violation > 2) return fail(MXS_E_INVALID, "gdba: violation must be 0 (NZ), 1 (NM) or 2 (MX)");
-        if (increase_mode < 0 || increase_mode > 3)
-            return fail(MXS_E_INVALID, "gdba: increase_mode must be 0 (E), 1 (R), 2 (C) or 3 (T)");
-        if (budget < 0) return fail(MXS_E_INVALID, "gdba: negative pool budget");
-        if (budget == 0) budget = DEFAULT_POOL_BUDGET;
+        if (int rc = check_params(modifier, violation, increase_mode, &budget)) return rc;
         if (int rc = hg.load(G, p)) return rc;
-        const int nV = hg.nV, nF = hg.nF;
-        for (int f = 0; f < nF; ++f)
-            if (hg.toff[f + 1] <= hg.toff[f]) return fail(MXS_E_INVALID, "empty table");
-        // maxi over NaN improvements depends on message arrival in the reference: no defined result
-        for (double t : hg.tables)
-            if (!std::isfinite(t)) return fail(MXS_E_INVALID, "gdba: constraint tables must be finite (no inf / NaN entries)");
+        const int nV = hg.nV;
         bool any_vc = false;
-        for (double c : hg.var_cost) {
-            if (!std::isfinite(c)) return fail(MXS_E_INVALID, "gdba: variable costs must be finite (no inf / NaN entries)");
-            any_vc |= c != 0.0;
-        }
+        if (int rc = check_graph(hg, &any_vc)) return rc;
         if (vrk) h_vrank.assign(vrk, vrk + hg.coff[nV]);
         if (int rc = hg.load_init(G)) return rc;
-        const std::string bad = hs.build(nV, nF, hg.dom, hg.frow, hg.evar, hg.toff, hg.vrow, hg.vedges);
+        const std::string bad = hs.build(nV, hg.nF, hg.dom, hg.frow, hg.evar, hg.toff, hg.vrow, hg.vedges);
         if (!bad.empty()) return fail(MXS_E_INVALID, bad);
-        // neighbours: the other variables of v's constraints (the concerned list holds v itself once); the
-        // first slot of v's list that holds each concerned variable (v itself: slot 0, every scope holds it)
-        h_nb.assign(nV, 0);
-        std::vector<int32_t> h_first(hs.conc_var.size(), 0);
-        for (int v = 0; v < nV; ++v) {
-            const int c0 = hs.conc_rowptr[v], c1 = hs.conc_rowptr[v + 1];
-            h_nb[v] = c1 - c0 > 1;
-            for (int k = c0; k < c1; ++k) {
-                const int u = hs.conc_var[k];
-                int first = 0;
-                if (u != v)
-                    for (int s = hg.vrow[v]; s < hg.vrow[v + 1]; ++s) {
-                        bool in = false;
-                        for (int q = hs.nb_rowptr[s]; q < hs.nb_rowptr[s + 1]; ++q) in |= hs.nb_var[q] == u;
-                        if (in) {
-                            first = s - hg.vrow[v];
-                            break;
-                        }
-                    }
-                h_first[k] = first;
-            }
-        }
+        std::vector<int32_t> h_first;
+        neighbourhood(hg, hs, h_nb, h_first);
         // the plan of the modifier pool, checked against the budget before anything is allocated
         plan.build(increase_mode, hg.dom, hg.vrow, h_nb, hs);
         if (plan.entries > budget / (int64_t)sizeof(counter_t))
             return fail(MXS_E_INVALID, "gdba: the modifier tables take " + std::to_string(plan.entries * (int64_t)sizeof(counter_t)) +
                                            " bytes, more than the budget of " + std::to_string(budget));
-        // what a raw entry is compared with (_is_violated, :552-572): min / max over the flattened table
-        std::vector<T> h_vref(hs.base.size(), (T)0);
-        if (violation != VIO_NZ) {
-            std::vector<T> fref(nF);
-            for (int f = 0; f < nF; ++f) {
-                T r = (T)hg.tables[hg.toff[f]];
-                for (int64_t i = hg.toff[f]; i < hg.toff[f + 1]; ++i) {
-                    const T t = (T)hg.tables[i];
-                    if (violation == VIO_NM ? t < r : t > r) r = t;
-                }
-                fref[f] = r;
-            }
-            for (size_t s = 0; s < h_vref.size(); ++s) h_vref[s] = fref[hg.efac[hg.vedges[s]]];
-        }
+        const std::vector<T> h_vref = violation_refs<T>(hg, hs.base.size(), violation);
         std::vector<int32_t> h_rank(nV);
         for (int v = 0; v < nV; ++v) h_rank[v] = rk ? rk[v] : v;
         if (int rc = sl.upload(hs, stream, nullptr, false)) return rc;  // no first-neighbour arrays, no rows
@@ -469,7 +618,8 @@ struct Engine : Base {
         return MXS_OK;
     }
 
-    int get_state(int32_t* idx, double* cst, uint8_t* has, double* imp, int32_t* nv) override {
+    int get_state(int32_t r, int32_t* idx, double* cst, uint8_t* has, double* imp, int32_t* nv) override {
+        if (r != 0) return fail(MXS_E_INVALID, "replica out of range");
         MXS_TRY(hipSetDevice(device));
         const int nV = g.n_vars;
         if (!nV) return MXS_OK;
@@ -494,7 +644,8 @@ struct Engine : Base {
 
     // slot -1: *n = the bytes of the whole pool.  Otherwise *n = the number of modifiers stored for the slot (0:
     // none); with `out`, they are copied (base + counter) -- capacity must hold them
-    int get_modifiers(int32_t slot, int32_t* out, int64_t capacity, int64_t* n) override {
+    int get_modifiers(int32_t r, int32_t slot, int32_t* out, int64_t capacity, int64_t* n) override {
+        if (r != 0) return fail(MXS_E_INVALID, "replica out of range");
         if (slot == -1) {
             if (n) *n = plan.entries * (int64_t)sizeof(counter_t);
             return MXS_OK;
@@ -517,11 +668,302 @@ struct Engine : Base {
         std::vector<int32_t> c;
         if (!idx) {
             c.resize(g.n_vars);
-            int rc = get_state(c.data(), nullptr, nullptr, nullptr, nullptr);
+            int rc = get_state(0, c.data(), nullptr, nullptr, nullptr, nullptr);
             if (rc) return rc;
             idx = c.data();
         }
         return hg.eval_cost(idx, infinity, cst, viol_out);
+    }
+
+    // one run: its cost is eval_cost's
+    int replica_costs(double infinity, double* cst, int64_t* viol_out) override { return eval_cost(nullptr, infinity, cst, viol_out); }
+};
+
+// R seeded runs of the instance with the launches one run needs (mxs_gdba_create_replicas).  The slot view, the
+// tables, vref, mod_off, conc_first, dom, rank and the variable costs are stored once; cur, cost, has_cost, rec are
+// [R][n_vars], viol (and slot_vc where some variable cost is non-zero) [R][n_slots], the pool [R][plan.entries]; the
+// seeds are a device array.  The refusals, the allocations that grow with R, the start values of the variables
+// without neighbours and the cost launches are rephost::Host's (replica_host.h, shared with dsa.hip, mgm.hip and
+// mgm2.h); GDBA keeps its variables in graph order, so Host's q is the identity (graph_order).  A run's final state
+// is usually not its best: track_best keeps every replica's best state on the device, as DSA's does.
+template <typename T>
+struct ReplicaEngine : Base {
+    rephost::Host<T> rh;
+    DevR<T> g{};
+    Plan plan;
+    mxs_host::DevSlots sl;
+    size_t n_slots = 0;
+    Buf<int32_t> rank, conc_first, init_idx;
+    Buf<int64_t> mod_off;
+    Buf<T> vref, var_cost;
+    Buf<int32_t> cur;                 // the dynamic state: [R][n_vars], graph order
+    Buf<T> cost, slot_vc;
+    Buf<counter_t> pool;
+    Buf<uint8_t> has_cost, viol;
+    Buf<Rec<T>> rec;
+    // the best state (track_best): `tracked`: track_best was called, `every` > 0: records are kept
+    bool tracked = false;
+    int32_t every = 0;
+    double best_infinity = INFINITY;
+    Buf<double> best_cost;
+    Buf<long long> best_viol, best_round;
+    Buf<int32_t> best_improved, best_idx;
+
+    int init(const mxs_graph& G, const mxs_params& p, const int32_t* rk, const int32_t* vrk, int32_t modifier,
+             int32_t violation, int32_t increase_mode, const uint64_t* sds, int32_t n_replicas, int64_t budget,
+             int dev) override {
+        if (int rc = rh.open(sds, n_replicas, dev, true)) return rc;
+        n_rep = rh.n_rep;
+        if (int rc = check_params(modifier, violation, increase_mode, &budget)) return rc;
+        if (int rc = rh.hg.load(G, p)) return rc;
+        bool any_vc = false;
+        if (int rc = check_graph(rh.hg, &any_vc)) return rc;
+        if (int rc = rh.hg.load_init(G)) return rc;
+        rh.set_value_rank(vrk);
+        const mxs_host::HostGraph& hg = rh.hg;
+        const hipStream_t stream = rh.stream;
+        const int nV = hg.nV;
+        lsearch::HostSlots hs;
+        const std::string bad = hs.build(nV, hg.nF, hg.dom, hg.frow, hg.evar, hg.toff, hg.vrow, hg.vedges);
+        if (!bad.empty()) return fail(MXS_E_INVALID, bad);
+        std::vector<int32_t> h_nb, h_first;
+        neighbourhood(hg, hs, h_nb, h_first);
+        // the plan of ONE replica's pool; all of them against the budget before anything is allocated
+        plan.build(increase_mode, hg.dom, hg.vrow, h_nb, hs);
+        const int64_t one = plan.entries * (int64_t)sizeof(counter_t);
+        if (plan.entries > budget / (int64_t)sizeof(counter_t) / n_rep)
+            return fail(MXS_E_INVALID, "gdba: the modifier tables of " + std::to_string(n_rep) + " replicas take " +
+                                           std::to_string(one * n_rep) + " bytes (" + std::to_string(one) +
+                                           " per replica), more than the budget of " + std::to_string(budget));
+        if (int rc = rh.graph_order(h_nb, rephost::blocks_of(nV, TPB))) return rc;
+        n_slots = hs.base.size();
+        if (int rc = sl.upload(hs, stream, nullptr, false)) return rc;  // no first-neighbour arrays, no rows
+        if (int rc = rh.upload_order()) return rc;
+        if (int rc = rh.upload_graph()) return rc;
+        MXS_TRY(conc_first.upload(h_first, stream));
+        MXS_TRY(rank.upload(mgm2::ranks_or_index(rk, nV), stream));
+        MXS_TRY(vref.upload(violation_refs<T>(hg, n_slots, violation), stream));
+        MXS_TRY(var_cost.upload(mxs_host::narrowed<T>(hg.var_cost), stream));
+        MXS_TRY(mod_off.upload(plan.mod_off, stream));
+        MXS_TRY(init_idx.upload(hg.init, stream));
+        const size_t R = (size_t)n_rep;
+        if (int rc = rephost::alloc_rep(pool, R * (size_t)plan.entries, "modifier tables")) return rc;
+        if (int rc = rephost::alloc_rep(cur, R * nV, "values")) return rc;
+        if (int rc = rephost::alloc_rep(cost, R * nV, "held costs")) return rc;
+        if (int rc = rephost::alloc_rep(has_cost, R * nV, "cost flags")) return rc;
+        if (int rc = rephost::alloc_rep(rec, R * nV, "improvement records")) return rc;
+        if (int rc = rephost::alloc_rep(viol, R * n_slots, "violation flags")) return rc;
+        if (int rc = rephost::alloc_rep(slot_vc, any_vc ? R * n_slots : 0, "variable-cost sums")) return rc;
+        g.slots = sl.view();
+        g.n_vars = nV;
+        g.is_max = hg.is_max;
+        g.modifier = modifier;
+        g.violation = violation;
+        g.increase_mode = increase_mode;
+        g.has_var_cost = any_vc;
+        g.seed = 0;  // per block: seeds[r]
+        g.dom = rh.dom_size.p;
+        g.var_rowptr = rh.var_rowptr.p;
+        g.has_nb = rh.n_neigh.p;
+        g.rank = rank.p;
+        g.tables = rh.tables.p;
+        g.vref = vref.p;
+        g.mod_off = mod_off.p;
+        g.pool = pool.p;
+        g.conc_first = conc_first.p;
+        g.cost_off = rh.cost_off.p;
+        g.var_cost = var_cost.p;
+        g.cur = cur.p;
+        g.cost = cost.p;
+        g.has_cost = has_cost.p;
+        g.rec = rec.p;
+        g.viol = viol.p;
+        g.slot_vc = slot_vc.p;
+        g.bpr = 1;
+        g.n_rep = n_rep;
+        g.n_slots = (int64_t)n_slots;
+        g.n_pool = plan.entries;
+        g.seeds = rh.seeds.p;
+        g.dom_size = rh.dom_size.p;
+        g.factor_rowptr = rh.factor_rowptr.p;
+        g.edge_var = rh.edge_var.p;
+        g.q = rh.qmap.p;
+        g.table_off = rh.table_off.p;
+        return reset();
+    }
+
+    // every replica back to its start state (k_gdbar_init), the pools and the violation flags cleared; the records
+    // of track_best start again
+    int reset() override {
+        if (int rc = rh.start_values()) return rc;  // optimal_cost_value of the variables without neighbours
+        const hipStream_t stream = rh.stream;
+        const size_t R = (size_t)n_rep;
+        rounds = 0;
+        if (g.n_vars) {
+            g.bpr = rephost::blocks_of(g.n_vars, AUX_TPB);
+            hipLaunchKernelGGL((k_gdbar_init<T>), dim3((unsigned)(g.bpr * n_rep)), dim3(AUX_TPB), 0, stream, g,
+                               (const int32_t*)init_idx.p, (const int32_t*)rh.iso_val.p, (const T*)rh.iso_cost.p);
+            MXS_TRY(hipGetLastError());
+        }
+        if (plan.entries) MXS_TRY(hipMemsetAsync(pool.p, 0, sizeof(counter_t) * R * (size_t)plan.entries, stream));
+        if (n_slots) MXS_TRY(hipMemsetAsync(viol.p, 0, R * n_slots, stream));
+        const int rc = every > 0 ? record(2) : MXS_OK;
+        MXS_TRY(hipStreamSynchronize(stream));  // (also when record() failed)
+        return rc;
+    }
+
+    BestRec best_rec() const { return BestRec{best_cost.p, best_viol.p, best_round.p, best_improved.p, best_idx.p}; }
+
+    // the current states against the records (mode 1; 2: the first record), three launches in stream order
+    int record(int mode) {
+        if (int rc = rh.launch_costs(g, cur.p, best_infinity, mode, best_rec())) return rc;
+        const int bpr = std::max(1, rephost::blocks_of(g.n_vars, AUX_TPB));
+        hipLaunchKernelGGL(k_gdbar_best_copy, dim3((unsigned)(bpr * n_rep)), dim3(AUX_TPB), 0, rh.stream, (int)g.n_vars, bpr,
+                           (const int32_t*)cur.p, (const double*)rh.rep_cost.p, (const long long*)rh.rep_viol.p,
+                           (long long)rounds, best_rec());
+        MXS_TRY(hipGetLastError());
+        return MXS_OK;
+    }
+
+    int run(int32_t n) override {
+        MXS_TRY(hipSetDevice(rh.device));
+        if (rounds + (int64_t)n > MAX_ROUNDS)
+            return fail(MXS_E_INVALID, "gdba: the modifier counters are 16 bits wide, at most 65535 rounds");
+        const hipStream_t stream = rh.stream;
+        const int nV = g.n_vars;
+        if (nV == 0) {
+            rounds += n;
+            return MXS_OK;
+        }
+        const int vbpr = rephost::blocks_of(nV, TPB);
+        const dim3 grid((unsigned)vbpr * (unsigned)n_rep), block(TPB);
+        for (int32_t r = 0; r < n; ++r) {
+            g.round = rounds + 1;
+            g.bpr = vbpr;  // (a kernel takes its DevR by value: the copy is made at the launch; record() sets its own)
+            hipLaunchKernelGGL((k_gdbar_eval<T>), grid, block, 0, stream, g);
+            MXS_TRY(hipGetLastError());
+            hipLaunchKernelGGL((k_gdbar_decide<T>), grid, block, 0, stream, g);
+            MXS_TRY(hipGetLastError());
+            rounds += 1;
+            if (every > 0 && rounds % every == 0)
+                if (int rc = record(1)) return rc;
+        }
+        MXS_TRY(hipStreamSynchronize(stream));
+        return MXS_OK;
+    }
+
+    int get_state(int32_t r, int32_t* idx, double* cst, uint8_t* has, double* imp, int32_t* nv) override {
+        if (r < 0 || r >= n_rep) return fail(MXS_E_INVALID, "replica out of range");
+        MXS_TRY(hipSetDevice(rh.device));
+        const hipStream_t stream = rh.stream;
+        const int nV = g.n_vars;
+        if (!nV) return MXS_OK;
+        std::vector<T> hc(nV);
+        std::vector<Rec<T>> hr(nV);
+        const size_t roff = (size_t)r * nV;
+        if (idx) MXS_TRY(hipMemcpyAsync(idx, cur.p + roff, 4 * (size_t)nV, hipMemcpyDeviceToHost, stream));
+        if (has) MXS_TRY(hipMemcpyAsync(has, has_cost.p + roff, nV, hipMemcpyDeviceToHost, stream));
+        if (cst) MXS_TRY(hipMemcpyAsync(hc.data(), cost.p + roff, sizeof(T) * (size_t)nV, hipMemcpyDeviceToHost, stream));
+        if (imp || nv) MXS_TRY(hipMemcpyAsync(hr.data(), rec.p + roff, sizeof(Rec<T>) * (size_t)nV, hipMemcpyDeviceToHost, stream));
+        MXS_TRY(hipStreamSynchronize(stream));
+        for (int v = 0; v < nV; ++v) {
+            if (cst) cst[v] = (double)hc[v];
+            if (imp) imp[v] = (double)hr[v].improve;
+            if (nv) nv[v] = hr[v].newv;
+        }
+        return MXS_OK;
+    }
+
+    // as Engine::get_modifiers, of replica r; slot -1: the bytes of the whole pool, all replicas
+    int get_modifiers(int32_t r, int32_t slot, int32_t* out, int64_t capacity, int64_t* n) override {
+        if (r < 0 || r >= n_rep) return fail(MXS_E_INVALID, "replica out of range");
+        if (slot == -1) {
+            if (n) *n = plan.entries * (int64_t)sizeof(counter_t) * n_rep;
+            return MXS_OK;
+        }
+        if (slot < 0 || (size_t)slot >= plan.size.size()) return fail(MXS_E_INVALID, "gdba: slot out of range");
+        const int64_t cnt = plan.size[slot];
+        if (n) *n = cnt;
+        if (!out || cnt == 0) return MXS_OK;
+        if (capacity < cnt) return fail(MXS_E_INVALID, "gdba: buffer too small for the slot's modifiers");
+        MXS_TRY(hipSetDevice(rh.device));
+        std::vector<counter_t> h((size_t)cnt);
+        MXS_TRY(hipMemcpyAsync(h.data(), pool.p + (size_t)r * (size_t)plan.entries + plan.mod_off[slot],
+                               sizeof(counter_t) * (size_t)cnt, hipMemcpyDeviceToHost, rh.stream));
+        MXS_TRY(hipStreamSynchronize(rh.stream));
+        for (int64_t i = 0; i < cnt; ++i) out[i] = g.modifier + (int32_t)h[(size_t)i];
+        return MXS_OK;
+    }
+
+    int eval_cost(const int32_t* idx, double infinity, double* cst, int64_t* viol_out) override {
+        return rh.eval_cost(idx, infinity, cst, viol_out,
+                            [&](int32_t* out) { return get_state(0, out, nullptr, nullptr, nullptr, nullptr); });
+    }
+
+    int replica_costs(double infinity, double* cst, int64_t* viol_out) override {
+        return rh.replica_costs(g, cur.p, infinity, cst, viol_out);
+    }
+
+    void drop_records() {
+        best_cost.release(), best_viol.release(), best_round.release(), best_improved.release(), best_idx.release();
+        every = 0;
+    }
+
+    int track_best(int32_t ev, double infinity) override {
+        if (ev < 0) return fail(MXS_E_INVALID, "every must be 0 (off) or positive");
+        MXS_TRY(hipSetDevice(rh.device));
+        drop_records();
+        if (ev == 0) {
+            tracked = true;
+            best_infinity = infinity;
+            return MXS_OK;
+        }
+        const size_t R = (size_t)n_rep;
+        int rc = rephost::alloc_rep(best_cost, R, "records");
+        if (!rc) rc = rephost::alloc_rep(best_viol, R, "records");
+        if (!rc) rc = rephost::alloc_rep(best_round, R, "records");
+        if (!rc) rc = rephost::alloc_rep(best_improved, R, "records");
+        if (!rc) rc = rephost::alloc_rep(best_idx, R * g.n_vars, "best states");
+        if (rc) {  // no records, and get_best keeps what the last successful call set (tracked, best_infinity)
+            drop_records();
+            return rc;
+        }
+        tracked = true;
+        best_infinity = infinity;
+        every = ev;
+        if (int rc2 = record(2)) return rc2;  // the state as it is now: round 0 of a fresh engine
+        MXS_TRY(hipStreamSynchronize(rh.stream));
+        return MXS_OK;
+    }
+
+    int get_best(int32_t r, int32_t* replica, int64_t* round, double* cst, int64_t* viol_out, int32_t* idx) override {
+        if (r < -1 || r >= n_rep) return fail(MXS_E_INVALID, "replica out of range");
+        if (!tracked) return fail(MXS_E_STATE, "mxs_gdba_get_best before mxs_gdba_track_best");
+        MXS_TRY(hipSetDevice(rh.device));
+        std::vector<double> hc;
+        std::vector<long long> hv, hy(n_rep, (long long)rounds);
+        if (every > 0) {  // the records
+            if (int rc = rh.fetch_costs(hc, hv, best_cost.p, best_viol.p)) return rc;
+            MXS_TRY(hipMemcpyAsync(hy.data(), best_round.p, 8 * (size_t)n_rep, hipMemcpyDeviceToHost, rh.stream));
+            MXS_TRY(hipStreamSynchronize(rh.stream));
+        } else {          // the current states
+            if (int rc = rh.current_costs(g, cur.p, best_infinity, hc, hv)) return rc;
+        }
+        if (r < 0) r = repcost::best_replica(n_rep, g.is_max, hc.data(), hv.data());
+        if (replica) *replica = r;
+        if (round) *round = (int64_t)hy[r];
+        if (cst) *cst = hc[r];
+        if (viol_out) *viol_out = (int64_t)hv[r];
+        if (idx && g.n_vars) {
+            if (every > 0) {  // (graph order, as stored)
+                MXS_TRY(hipMemcpyAsync(idx, best_idx.p + (size_t)r * g.n_vars, 4 * (size_t)g.n_vars, hipMemcpyDeviceToHost,
+                                       rh.stream));
+                MXS_TRY(hipStreamSynchronize(rh.stream));
+            } else if (int rc = get_state(r, idx, nullptr, nullptr, nullptr, nullptr)) {
+                return rc;
+            }
+        }
+        return MXS_OK;
     }
 };
 
@@ -539,6 +981,17 @@ int mxs_gdba_create(const mxs_graph* g, const mxs_params* p, const int32_t* name
     return mxs_host::create<mxs_gdba, gdba::Engine>(g, p, out, name_rank, value_rank, modifier, violation, increase_mode, seed,
                                                     pool_budget_bytes, device);
 }
+int mxs_gdba_create_replicas(const mxs_graph* g, const mxs_params* p, const int32_t* name_rank, const int32_t* value_rank,
+                             int32_t modifier, int32_t violation, int32_t increase_mode, const uint64_t* seeds,
+                             int32_t n_replicas, int64_t pool_budget_bytes, int32_t device, mxs_gdba** out) {
+    return mxs_host::create<mxs_gdba, gdba::ReplicaEngine>(g, p, out, name_rank, value_rank, modifier, violation, increase_mode,
+                                                           seeds, n_replicas, pool_budget_bytes, device);
+}
+int mxs_gdba_replicas(const mxs_gdba* e, int32_t* n) {
+    if (!e) return mxs_host::fail(MXS_E_INVALID, "null handle");
+    if (n) *n = e->impl->n_rep;
+    return MXS_OK;
+}
 int mxs_gdba_reset(mxs_gdba* e) { return e ? e->impl->reset() : mxs_host::fail(MXS_E_INVALID, "null handle"); }
 int mxs_gdba_run(mxs_gdba* e, int32_t n_rounds) {
     if (!e) return mxs_host::fail(MXS_E_INVALID, "null handle");
@@ -551,10 +1004,28 @@ int mxs_gdba_rounds(const mxs_gdba* e, int64_t* rounds) {
     return MXS_OK;
 }
 int mxs_gdba_get_state(mxs_gdba* e, int32_t* idx, double* cost, uint8_t* has_cost, double* improve, int32_t* new_value) {
-    return e ? e->impl->get_state(idx, cost, has_cost, improve, new_value) : mxs_host::fail(MXS_E_INVALID, "null handle");
+    return e ? e->impl->get_state(0, idx, cost, has_cost, improve, new_value) : mxs_host::fail(MXS_E_INVALID, "null handle");
+}
+int mxs_gdba_get_state_replica(mxs_gdba* e, int32_t replica, int32_t* idx, double* cost, uint8_t* has_cost, double* improve,
+                               int32_t* new_value) {
+    return e ? e->impl->get_state(replica, idx, cost, has_cost, improve, new_value) : mxs_host::fail(MXS_E_INVALID, "null handle");
 }
 int mxs_gdba_get_modifiers(mxs_gdba* e, int32_t slot, int32_t* out, int64_t capacity, int64_t* n_entries) {
-    return e ? e->impl->get_modifiers(slot, out, capacity, n_entries) : mxs_host::fail(MXS_E_INVALID, "null handle");
+    return e ? e->impl->get_modifiers(0, slot, out, capacity, n_entries) : mxs_host::fail(MXS_E_INVALID, "null handle");
+}
+int mxs_gdba_get_modifiers_replica(mxs_gdba* e, int32_t replica, int32_t slot, int32_t* out, int64_t capacity,
+                                   int64_t* n_entries) {
+    return e ? e->impl->get_modifiers(replica, slot, out, capacity, n_entries) : mxs_host::fail(MXS_E_INVALID, "null handle");
+}
+int mxs_gdba_replica_costs(mxs_gdba* e, double infinity, double* cost, int64_t* violations) {
+    return e ? e->impl->replica_costs(infinity, cost, violations) : mxs_host::fail(MXS_E_INVALID, "null handle");
+}
+int mxs_gdba_track_best(mxs_gdba* e, int32_t every, double infinity) {
+    return e ? e->impl->track_best(every, infinity) : mxs_host::fail(MXS_E_INVALID, "null handle");
+}
+int mxs_gdba_get_best(mxs_gdba* e, int32_t r, int32_t* replica, int64_t* round, double* cost, int64_t* violations,
+                      int32_t* idx) {
+    return e ? e->impl->get_best(r, replica, round, cost, violations, idx) : mxs_host::fail(MXS_E_INVALID, "null handle");
 }
 int mxs_gdba_eval_cost(mxs_gdba* e, const int32_t* idx, double infinity, double* cost, int64_t* violations) {
     return e ? e->impl->eval_cost(idx, infinity, cost, violations) : mxs_host::fail(MXS_E_INVALID, "null handle");

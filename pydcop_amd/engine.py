@@ -70,6 +70,12 @@ MGM2_SYMBOLS = (
     "mxs_mgm2_best_replica",
 )
 
+# ... and GDBA's replicas and best state (include/maxsum_gpu_gdba_replicas.h: a header of their own, the checks of
+# include/maxsum_gpu.h count the names of that file)
+GDBA_REPLICA_SYMBOLS = (
+    "mxs_gdba_create_replicas", "mxs_gdba_replicas", "mxs_gdba_get_state_replica", "mxs_gdba_get_modifiers_replica",
+    "mxs_gdba_replica_costs", "mxs_gdba_track_best", "mxs_gdba_get_best",
+)
 
 MAX_PEERS = 8
 
@@ -280,6 +286,15 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
         "mxs_mgm2_get_state_replica": ([vp, i32, vp, vp, vp], C.c_int),
         "mxs_mgm2_replica_costs": ([vp, C.c_double, vp, vp], C.c_int),
         "mxs_mgm2_best_replica": ([vp, C.c_double, C.POINTER(i32), C.POINTER(C.c_double), C.POINTER(i64)], C.c_int),
+        # ... and GdbaEngine(replicas=R), its best state (pydcop_amd/gdba.py)
+        "mxs_gdba_create_replicas": ([C.POINTER(CGraph), C.POINTER(CParams), vp, vp, i32, i32, i32, vp, i32, i64, i32,
+                                      C.POINTER(vp)], C.c_int),
+        "mxs_gdba_replicas": ([vp, C.POINTER(i32)], C.c_int),
+        "mxs_gdba_get_state_replica": ([vp, i32, vp, vp, vp, vp, vp], C.c_int),
+        "mxs_gdba_get_modifiers_replica": ([vp, i32, i32, vp, i64, C.POINTER(i64)], C.c_int),
+        "mxs_gdba_replica_costs": ([vp, C.c_double, vp, vp], C.c_int),
+        "mxs_gdba_track_best": ([vp, i32, C.c_double], C.c_int),
+        "mxs_gdba_get_best": ([vp, i32, C.POINTER(i32), C.POINTER(i64), C.POINTER(C.c_double), C.POINTER(i64), vp], C.c_int),
     }
     for name, (argtypes, restype) in later.items():
         fn = getattr(lib, name, None)

@@ -35,7 +35,11 @@ first 12 rounds after reset(), "fresh_us_per_round").  The MGM-2 rows (`--replic
 Mgm2Engine(replicas=R), mgm2.h) follow the protocol of the MGM rows: the single side is `mxs_mgm2_create` of this
 library or of `--baseline-lib`; per size first "instance_to_instance" (two engines of the single side against each
 other: the spread of the protocol itself) and "single_vs_baseline" (this library's `mxs_mgm2_create` against the single
-side), then one "replicas" row per R.
+side), then one "replicas" row per R.  The GDBA rows (`--replica-algos gdba`; "algo": "gdba_A_NZ_<mode>",
+GdbaEngine(replicas=R), gdba.h, increase modes `--gdba-modes`) follow the protocol of the MGM-2 rows with `mxs_gdba_create`
+as the single side; every timed window starts from reset() and is capped at 20 000 rounds (the counters allow 65535),
+and a row also has the rounds with the best state tracked every round and every 10th ("best_every_1_us_per_round",
+"best_every_10_us_per_round").
 """
 import argparse
 import json
@@ -352,6 +356,129 @@ def mgm2_replica_rows(a):
             single.close()
 
 
+class BaselineGdba:
+    """The GDBA engine of ANOTHER build of the library (--baseline-lib): mxs_gdba_create / _reset / _run / _destroy."""
+
+    def __init__(self, path, g, p, seed, codes):
+        import ctypes as C
+        from pydcop_amd.engine import load_library
+        load_library()                       # (the HIP runtime first: the libraries are linked without it)
+        self._lib = C.CDLL(os.path.abspath(path))
+        self._lib.mxs_version.restype = C.c_int32
+        self.version = int(self._lib.mxs_version())
+        self._lib.mxs_gdba_create.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32,
+                                              C.c_uint64, C.c_int64, C.c_int32, C.c_void_p]
+        self._lib.mxs_gdba_run.argtypes = [C.c_void_p, C.c_int32]
+        self._lib.mxs_gdba_reset.argtypes = [C.c_void_p]
+        self._lib.mxs_gdba_destroy.argtypes = [C.c_void_p]
+        self._g, self._p = g.to_c(), p.to_c()      # (kept alive)
+        self._h = C.c_void_p()
+        rc = self._lib.mxs_gdba_create(C.byref(self._g), C.byref(self._p), None, None, codes[0], codes[1], codes[2], seed, 0,
+                                       0, C.byref(self._h))
+        if rc:
+            raise RuntimeError(f"mxs_gdba_create of {path}: {rc}")
+
+    def run(self, n):
+        if self._lib.mxs_gdba_run(self._h, int(n)):
+            raise RuntimeError("mxs_gdba_run of the baseline library failed")
+
+    def reset(self):
+        if self._lib.mxs_gdba_reset(self._h):
+            raise RuntimeError("mxs_gdba_reset of the baseline library failed")
+
+    def close(self):
+        self._lib.mxs_gdba_destroy(self._h)
+
+
+GDBA_WINDOW_ROUNDS = 20_000      # (the counters are 16 bits wide: a window starts from reset() and stays below 65535)
+
+
+def gdba_rounds_for(eng, window_s):
+    """the number of rounds that fill the window, at most GDBA_WINDOW_ROUNDS; warms the engine up on the way"""
+    eng.reset()
+    eng.run(20)
+    us = timed_us(eng, 200)
+    return max(50, min(GDBA_WINDOW_ROUNDS, int(window_s * 1e6 / max(us, 1e-3))))
+
+
+def gdba_timed_us(eng, rounds):
+    eng.reset()
+    eng.run(20)
+    return round(timed_us(eng, rounds), 2)
+
+
+def gdba_alternated(a, left, right):
+    n_left, n_right = gdba_rounds_for(left, a.window), gdba_rounds_for(right, a.window)
+    one, other = [], []
+    for _ in range(a.repeats):
+        one.append(gdba_timed_us(left, n_left))
+        other.append(gdba_timed_us(right, n_right))
+    return one, other
+
+
+def gdba_replica_rows(a):
+    """The protocol of the MGM-2 rows for GdbaEngine(replicas=R) (gdba.h), modifier A / violation NZ, increase modes T
+    and C: every timed window starts from reset() plus 20 rounds (the counters allow 65535 rounds) and is capped at
+    GDBA_WINDOW_ROUNDS rounds.  Columns beside the MGM-2 ones: the rounds with track_best(1) and track_best(10)."""
+    from pydcop_amd.gdba import GdbaEngine, check_params
+    for inc in a.gdba_modes:
+        kw = dict(modifier="A", violation="NZ", increase_mode=inc)
+        codes = check_params("A", "NZ", inc)
+        for n_vars in a.replica_sizes:
+            g = G.random_coloring(n_vars, seed=0, names=False)
+            p = Params()
+
+            def single_side():
+                if a.baseline_lib:
+                    e = BaselineGdba(a.baseline_lib, g, p, 1, codes)
+                    return e, f"mxs_version {e.version}"
+                return GdbaEngine(g, p, seed=1, lib_path=a.lib, **kw), "this"
+
+            base = {"algo": f"gdba_A_NZ_{inc}", "instance": f"coloring_{n_vars}", "dtype": "f64", "n_vars": n_vars}
+            # two engines of the single side against each other: what the protocol itself spreads
+            left, baseline = single_side()
+            right, _ = single_side()
+            one, other = gdba_alternated(a, left, right)
+            print(json.dumps(dict(base, row="instance_to_instance", baseline=baseline, left_us_per_round=one,
+                                  right_us_per_round=other, ratio_right_to_left=round(median(other) / median(one), 4))),
+                  flush=True)
+            right.close()
+            # this library's mxs_gdba_create against the single side
+            mine = GdbaEngine(g, p, seed=1, lib_path=a.lib, **kw)
+            one, new = gdba_alternated(a, left, mine)
+            print(json.dumps(dict(base, row="single_vs_baseline", baseline=baseline, single_us_per_round=one,
+                                  this_us_per_round=new, ratio_this_to_single=round(median(new) / median(one), 4))), flush=True)
+            left.close(), mine.close()
+            for R in a.replicas:
+                single, baseline = single_side()
+                eng = GdbaEngine(g, p, seeds=[1 + r for r in range(R)], replicas=R, lib_path=a.lib, **kw)   # (R = 1 too)
+                n_single, n_rep = gdba_rounds_for(single, a.window), gdba_rounds_for(eng, a.window)
+                one, many = [], []
+                for _ in range(a.repeats):
+                    one.append(gdba_timed_us(single, n_single))
+                    many.append(gdba_timed_us(eng, n_rep))
+                row = dict(base, row="replicas", replicas=R, baseline=baseline, single_us_per_round=one,
+                           replicas_us_per_round=many, ratio_R_singles_to_replicas=round(R * median(one) / median(many), 2))
+                for every in (1, 10):
+                    eng.track_best(every, float("inf"))
+                    row[f"best_every_{every}_us_per_round"] = [gdba_timed_us(eng, n_rep) for _ in range(a.repeats)]
+                eng.track_best(0, float("inf"))
+                reps = max(3, min(2000, int(0.2 * a.window * 1e6 / max(many[0], 1.0))))
+                t0 = time.perf_counter()
+                for _ in range(reps):
+                    dev = eng.replica_costs()
+                row["replica_costs_us"] = round(1e6 * (time.perf_counter() - t0) / reps, 1)
+                reps = max(1, min(reps, 2000 // R))
+                t0 = time.perf_counter()
+                for _ in range(reps):
+                    host = [eng.eval_cost(eng.assignment(r)[0]) for r in range(R)]
+                row["host_eval_cost_us"] = round(1e6 * (time.perf_counter() - t0) / reps, 1)
+                assert all(abs(dev[0][r] - host[r][0]) <= 1e-9 * max(1.0, abs(host[r][0])) for r in range(R))
+                print(json.dumps(row), flush=True)
+                eng.close()
+                single.close()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--cycles", type=int, default=500)
@@ -368,7 +495,9 @@ def main():
     ap.add_argument("--warmup", type=float, default=0.5, help="seconds of warm-up per engine of the replica rows")
     ap.add_argument("--baseline-lib", default=None,
                     help="replica rows: the single-seed side from this other build of the library (mxs_dsa_create)")
-    ap.add_argument("--replica-algos", nargs="*", default=["dsa", "mgm"], choices=["dsa", "mgm", "mgm2"])
+    ap.add_argument("--replica-algos", nargs="*", default=["dsa", "mgm"], choices=["dsa", "mgm", "mgm2", "gdba"])
+    ap.add_argument("--gdba-modes", nargs="*", default=["T", "C"], choices=["E", "R", "C", "T"],
+                    help="the increase modes of the GDBA replica rows")
     a = ap.parse_args()
     if a.replicas:
         if "dsa" in a.replica_algos:
@@ -377,6 +506,8 @@ def main():
             mgm_replica_rows(a)
         if "mgm2" in a.replica_algos:
             mgm2_replica_rows(a)
+        if "gdba" in a.replica_algos:
+            gdba_replica_rows(a)
         return
     if a.dba_rounds > 0:
         return dba_rows(a)
