@@ -57,7 +57,35 @@ class EngineBinding:
 
 
 class ReplicaBinding(EngineBinding):
-    """What the bindings of the replica engines (`DsaEngine`, `MgmEngine`: R seeded runs in one engine) share."""
+    """What the bindings of the replica engines (`DsaEngine`, `MgmEngine`, `Mgm2Engine`, `GdbaEngine`: R seeded runs
+    in one engine) share.  A class with `state()` sets STATE_FIELDS, the (key, dtype) pairs of `<PREFIX>_get_state`'s
+    arrays in argument order; one whose replicas came after its first release sets REPLICA_SYMBOLS, the entry points
+    they need, and REPLICA_FEATURE, what the message calls them."""
+    STATE_FIELDS: Tuple[Tuple[str, type], ...] = ()
+    REPLICA_SYMBOLS: Tuple[str, ...] = ()
+    REPLICA_FEATURE = ""
+
+    def _need_replica_symbols(self, why: str):
+        missing = [n for n in self.REPLICA_SYMBOLS if not hasattr(self._lib, n)]
+        if missing:
+            raise MaxSumGpuError(
+                f"{self._lib._name} was built from sources without {self.REPLICA_FEATURE} (no {', '.join(missing)}): "
+                f"rebuild the library, {why}")
+
+    def state(self, replica: int = 0) -> dict:
+        n = self.graph.n_vars
+        out = {key: np.empty(n, dtype=dtype) for key, dtype in self.STATE_FIELDS}
+        ptrs = [a.ctypes.data for a in out.values()]
+        if int(replica) == 0:       # (the call every version of the library has)
+            self._call("get_state", *ptrs)
+        else:
+            self._need_replica_symbols("state(replica) needs them")
+            self._call("get_state_replica", int(replica), *ptrs)
+        return out
+
+    def assignment(self, replica: int = 0) -> Tuple[np.ndarray, np.ndarray]:
+        s = self.state(replica)
+        return s["idx"], s["cost"]
 
     def _set_seeds(self, seed: int, seeds: Optional[Sequence[int]], replicas: int) -> np.ndarray:
         """`self.seeds` (`seed + r` modulo 2**64, or `seeds`) and `self.replicas`; the array `<PREFIX>_create_*` takes"""

@@ -20,9 +20,10 @@
 // Counters are 16 bits wide: a counter grows by at most 1 per round, and run() refuses to go past 65535 rounds.
 //
 // REPLICAS (mxs_gdba_create_replicas): R seeded runs advance with the same two launches, as in mgm2.h.  The two
-// phases are __device__ bodies (eval_phase, decide_phase) with two sets of __global__ entry points: k_gdba_* on the
-// plain Dev -- what mxs_gdba_create launches, argument layout and grid as before -- and k_gdbar_* on DevR, where the
-// replica is folded into blockIdx.x (block = r * bpr + b, replica_cost.h) and the block's copy of the argument moves
+// phases are __device__ bodies (eval_phase, decide_phase) with two sets of __global__ entry points and ONE host
+// engine: k_gdba_* on the plain Dev -- what an engine of mxs_gdba_create launches for its one replica, argument layout
+// and grid as a single run has always had them -- and k_gdbar_* on DevR, where the replica is folded into blockIdx.x
+// (block = r * bpr + b, replica_cost.h) and the block's copy of the argument moves
 // once to replica r's slices of the dynamic state and takes seeds[r] (enter_replica).  A block is one wave of ONE
 // replica, so the ballot / shuffle loop of the decide phase never mixes replicas.  Everything static is stored once;
 // the state is [R][n_vars] in GRAPH order, viol / slot_vc [R][n_slots], the modifier pool [R][plan.entries] (mod_off
@@ -375,7 +376,7 @@ struct Plan {
     }
 };
 
-// ---- the host side the two engines share
+// ---- the host side
 inline int check_params(int32_t modifier, int32_t violation, int32_t increase_mode, int64_t* budget) {
     if (modifier < 0 || modifier > 1) return fail(MXS_E_INVALID, "gdba: modifier must be 0 (A) or 1 (M)");
     if (violation < 0 || violation > 2) return fail(MXS_E_INVALID, "gdba: violation must be 0 (NZ), 1 (NM) or 2 (MX)");
@@ -446,250 +447,39 @@ std::vector<T> violation_refs(const mxs_host::HostGraph& hg, size_t n_slots, int
     return h_vref;
 }
 
+// Engine<T> behind struct mxs_gdba, whatever its T
 struct Base {
     virtual ~Base() = default;
-    // mxs_gdba_create (Engine) / mxs_gdba_create_replicas (ReplicaEngine)
-    virtual int init(const mxs_graph&, const mxs_params&, const int32_t*, const int32_t*, int32_t, int32_t, int32_t, uint64_t,
-                     int64_t, int) {
-        return fail(MXS_E_STATE, "gdba: not the single-run engine");
-    }
-    virtual int init(const mxs_graph&, const mxs_params&, const int32_t*, const int32_t*, int32_t, int32_t, int32_t,
-                     const uint64_t*, int32_t, int64_t, int) {
-        return fail(MXS_E_STATE, "gdba: not the replica engine");
-    }
+    virtual int init(const mxs_graph& G, const mxs_params& p, const int32_t* name_rank, const int32_t* value_rank,
+                     int32_t modifier, int32_t violation, int32_t increase_mode, const uint64_t* seeds, int32_t n_replicas,
+                     bool single, int64_t budget, int dev) = 0;
     virtual int reset() = 0;
     virtual int run(int32_t n) = 0;
     virtual int get_state(int32_t r, int32_t* idx, double* cost, uint8_t* has_cost, double* improve, int32_t* newv) = 0;
     virtual int get_modifiers(int32_t r, int32_t slot, int32_t* out, int64_t capacity, int64_t* n) = 0;
     virtual int eval_cost(const int32_t* idx, double infinity, double* cost, int64_t* viol) = 0;
     virtual int replica_costs(double infinity, double* cost, int64_t* viol) = 0;
-    // the best state is the replica engine's (mxs_gdba_create_replicas, one replica included)
-    virtual int track_best(int32_t, double) { return fail(MXS_E_STATE, "gdba: the best state is tracked by the replica engine"); }
-    virtual int get_best(int32_t, int32_t*, int64_t*, double*, int64_t*, int32_t*) {
-        return fail(MXS_E_STATE, "mxs_gdba_get_best before mxs_gdba_track_best");
-    }
+    virtual int track_best(int32_t every, double infinity) = 0;
+    virtual int get_best(int32_t r, int32_t* replica, int64_t* round, double* cost, int64_t* viol, int32_t* idx) = 0;
     int64_t rounds = 0;
     int32_t n_rep = 1;
 };
 
-template <typename T>
-struct Engine : Base {
-    int device = 0;
-    hipStream_t stream = nullptr;
-    Dev<T> g{};
-    Plan plan;
-    mxs_host::HostGraph hg;
-    std::vector<int32_t> h_nb, h_vrank;
-    lsearch::HostSlots hs;
-    Buf<int32_t> dom, var_rowptr, has_nb, rank, conc_first, cur;
-    Buf<int64_t> mod_off, cost_off;
-    mxs_host::DevSlots sl;
-    Buf<T> tables, vref, var_cost, cost, slot_vc;
-    Buf<counter_t> pool;
-    Buf<uint8_t> has_cost, viol;
-    Buf<Rec<T>> rec;
-
-    ~Engine() override {
-        if (stream) (void)hipStreamDestroy(stream);
-    }
-
-    int init(const mxs_graph& G, const mxs_params& p, const int32_t* rk, const int32_t* vrk, int32_t modifier,
-             int32_t violation, int32_t increase_mode, uint64_t seed, int64_t budget, int dev) override {
-        device = dev;
-        if (int rc = mxs_host::open_device(dev, &stream)) return rc;
-        if (int rc = check_params(modifier, violation, increase_mode, &budget)) return rc;
-        if (int rc = hg.load(G, p)) return rc;
-        const int nV = hg.nV;
-        bool any_vc = false;
-        if (int rc = check_graph(hg, &any_vc)) return rc;
-        if (vrk) h_vrank.assign(vrk, vrk + hg.coff[nV]);
-        if (int rc = hg.load_init(G)) return rc;
-        const std::string bad = hs.build(nV, hg.nF, hg.dom, hg.frow, hg.evar, hg.toff, hg.vrow, hg.vedges);
-        if (!bad.empty()) return fail(MXS_E_INVALID, bad);
-        std::vector<int32_t> h_first;
-        neighbourhood(hg, hs, h_nb, h_first);
-        // the plan of the modifier pool, checked against the budget before anything is allocated
-        plan.build(increase_mode, hg.dom, hg.vrow, h_nb, hs);
-        if (plan.entries > budget / (int64_t)sizeof(counter_t))
-            return fail(MXS_E_INVALID, "gdba: the modifier tables take " + std::to_string(plan.entries * (int64_t)sizeof(counter_t)) +
-                                           " bytes, more than the budget of " + std::to_string(budget));
-        const std::vector<T> h_vref = violation_refs<T>(hg, hs.base.size(), violation);
-        std::vector<int32_t> h_rank(nV);
-        for (int v = 0; v < nV; ++v) h_rank[v] = rk ? rk[v] : v;
-        if (int rc = sl.upload(hs, stream, nullptr, false)) return rc;  // no first-neighbour arrays, no rows
-        MXS_TRY(conc_first.upload(h_first, stream));
-        MXS_TRY(dom.upload(hg.dom, stream));
-        MXS_TRY(var_rowptr.upload(hg.vrow, stream));
-        MXS_TRY(has_nb.upload(h_nb, stream));
-        MXS_TRY(rank.upload(h_rank, stream));
-        MXS_TRY(tables.upload(mxs_host::narrowed<T>(hg.tables), stream));
-        MXS_TRY(vref.upload(h_vref, stream));
-        MXS_TRY(var_cost.upload(mxs_host::narrowed<T>(hg.var_cost), stream));
-        MXS_TRY(cost_off.upload(hg.coff, stream));
-        MXS_TRY(mod_off.upload(plan.mod_off, stream));
-        MXS_TRY(pool.alloc((size_t)plan.entries));
-        MXS_TRY(cur.alloc(nV));
-        MXS_TRY(cost.alloc(nV));
-        MXS_TRY(has_cost.alloc(nV));
-        MXS_TRY(rec.alloc(nV));
-        MXS_TRY(viol.alloc(hs.base.size()));
-        MXS_TRY(slot_vc.alloc(any_vc ? hs.base.size() : 0));
-        g.slots = sl.view();
-        g.n_vars = nV;
-        g.is_max = p.mode == MXS_MODE_MAX;
-        g.modifier = modifier;
-        g.violation = violation;
-        g.increase_mode = increase_mode;
-        g.has_var_cost = any_vc;
-        g.seed = seed;
-        g.dom = dom.p;
-        g.var_rowptr = var_rowptr.p;
-        g.has_nb = has_nb.p;
-        g.rank = rank.p;
-        g.tables = tables.p;
-        g.vref = vref.p;
-        g.mod_off = mod_off.p;
-        g.pool = pool.p;
-        g.conc_first = conc_first.p;
-        g.cost_off = cost_off.p;
-        g.var_cost = var_cost.p;
-        g.cur = cur.p;
-        g.cost = cost.p;
-        g.has_cost = has_cost.p;
-        g.rec = rec.p;
-        g.viol = viol.p;
-        g.slot_vc = slot_vc.p;
-        return reset();
-    }
-
-    // on_start (:302-333): a variable with neighbours takes its initial value or a random one (held cost None);
-    // one without takes optimal_cost_value (min / max over (cost, value) tuples, relations.py:1661-1665)
-    int reset() override {
-        MXS_TRY(hipSetDevice(device));
-        const int nV = g.n_vars;
-        std::vector<int32_t> c0(nV);
-        std::vector<T> k0(nV, (T)0);
-        std::vector<uint8_t> h0(nV, 0);
-        std::vector<Rec<T>> r0(nV);
-        for (int v = 0; v < nV; ++v) {
-            if (h_nb[v]) {
-                c0[v] = hg.init[v] >= 0 ? hg.init[v] : (int)(uniform(g.seed, v, 0, D_START) * hg.dom[v]);
-            } else {
-                const int best = hg.optimal_cost_value<T>(v, g.is_max, h_vrank);
-                c0[v] = best;
-                k0[v] = (T)hg.var_cost[hg.coff[v] + best];
-                h0[v] = 1;
-            }
-            r0[v].improve = (T)0;
-            r0[v].newv = c0[v];
-        }
-        if (nV) {
-            MXS_TRY(hipMemcpyAsync(cur.p, c0.data(), 4 * (size_t)nV, hipMemcpyHostToDevice, stream));
-            MXS_TRY(hipMemcpyAsync(cost.p, k0.data(), sizeof(T) * nV, hipMemcpyHostToDevice, stream));
-            MXS_TRY(hipMemcpyAsync(has_cost.p, h0.data(), nV, hipMemcpyHostToDevice, stream));
-            MXS_TRY(hipMemcpyAsync(rec.p, r0.data(), sizeof(Rec<T>) * nV, hipMemcpyHostToDevice, stream));
-        }
-        if (plan.entries) MXS_TRY(hipMemsetAsync(pool.p, 0, sizeof(counter_t) * (size_t)plan.entries, stream));
-        if (!hs.base.empty()) MXS_TRY(hipMemsetAsync(viol.p, 0, hs.base.size(), stream));
-        MXS_TRY(hipStreamSynchronize(stream));
-        rounds = 0;
-        return MXS_OK;
-    }
-
-    int run(int32_t n) override {
-        MXS_TRY(hipSetDevice(device));
-        if (rounds + (int64_t)n > MAX_ROUNDS)
-            return fail(MXS_E_INVALID, "gdba: the modifier counters are 16 bits wide, at most 65535 rounds");
-        const int nV = g.n_vars;
-        if (nV == 0) {
-            rounds += n;
-            return MXS_OK;
-        }
-        const dim3 grid((unsigned)((nV + TPB - 1) / TPB)), block(TPB);
-        for (int32_t r = 0; r < n; ++r) {
-            g.round = rounds + 1;
-            hipLaunchKernelGGL((k_gdba_eval<T>), grid, block, 0, stream, g);
-            MXS_TRY(hipGetLastError());
-            hipLaunchKernelGGL((k_gdba_decide<T>), grid, block, 0, stream, g);
-            MXS_TRY(hipGetLastError());
-            rounds += 1;
-        }
-        MXS_TRY(hipStreamSynchronize(stream));
-        return MXS_OK;
-    }
-
-    int get_state(int32_t r, int32_t* idx, double* cst, uint8_t* has, double* imp, int32_t* nv) override {
-        if (r != 0) return fail(MXS_E_INVALID, "replica out of range");
-        MXS_TRY(hipSetDevice(device));
-        const int nV = g.n_vars;
-        if (!nV) return MXS_OK;
-        std::vector<T> hc(nV);
-        std::vector<int32_t> hi(nV);
-        std::vector<uint8_t> hh(nV);
-        std::vector<Rec<T>> hr(nV);
-        MXS_TRY(hipMemcpyAsync(hi.data(), cur.p, 4 * (size_t)nV, hipMemcpyDeviceToHost, stream));
-        MXS_TRY(hipMemcpyAsync(hh.data(), has_cost.p, nV, hipMemcpyDeviceToHost, stream));
-        MXS_TRY(hipMemcpyAsync(hc.data(), cost.p, sizeof(T) * nV, hipMemcpyDeviceToHost, stream));
-        MXS_TRY(hipMemcpyAsync(hr.data(), rec.p, sizeof(Rec<T>) * nV, hipMemcpyDeviceToHost, stream));
-        MXS_TRY(hipStreamSynchronize(stream));
-        for (int v = 0; v < nV; ++v) {
-            if (idx) idx[v] = hi[v];
-            if (has) has[v] = hh[v];
-            if (cst) cst[v] = (double)hc[v];
-            if (imp) imp[v] = (double)hr[v].improve;
-            if (nv) nv[v] = hr[v].newv;
-        }
-        return MXS_OK;
-    }
-
-    // slot -1: *n = the bytes of the whole pool.  Otherwise *n = the number of modifiers stored for the slot (0:
-    // none); with `out`, they are copied (base + counter) -- capacity must hold them
-    int get_modifiers(int32_t r, int32_t slot, int32_t* out, int64_t capacity, int64_t* n) override {
-        if (r != 0) return fail(MXS_E_INVALID, "replica out of range");
-        if (slot == -1) {
-            if (n) *n = plan.entries * (int64_t)sizeof(counter_t);
-            return MXS_OK;
-        }
-        if (slot < 0 || (size_t)slot >= plan.size.size()) return fail(MXS_E_INVALID, "gdba: slot out of range");
-        const int64_t cnt = plan.size[slot];
-        if (n) *n = cnt;
-        if (!out || cnt == 0) return MXS_OK;
-        if (capacity < cnt) return fail(MXS_E_INVALID, "gdba: buffer too small for the slot's modifiers");
-        MXS_TRY(hipSetDevice(device));
-        std::vector<counter_t> h((size_t)cnt);
-        MXS_TRY(hipMemcpyAsync(h.data(), pool.p + plan.mod_off[slot], sizeof(counter_t) * (size_t)cnt, hipMemcpyDeviceToHost, stream));
-        MXS_TRY(hipStreamSynchronize(stream));
-        for (int64_t i = 0; i < cnt; ++i) out[i] = g.modifier + (int32_t)h[(size_t)i];
-        return MXS_OK;
-    }
-
-    // DCOP.solution_cost of an assignment (constraints and the variables' own costs)
-    int eval_cost(const int32_t* idx, double infinity, double* cst, int64_t* viol_out) override {
-        std::vector<int32_t> c;
-        if (!idx) {
-            c.resize(g.n_vars);
-            int rc = get_state(0, c.data(), nullptr, nullptr, nullptr, nullptr);
-            if (rc) return rc;
-            idx = c.data();
-        }
-        return hg.eval_cost(idx, infinity, cst, viol_out);
-    }
-
-    // one run: its cost is eval_cost's
-    int replica_costs(double infinity, double* cst, int64_t* viol_out) override { return eval_cost(nullptr, infinity, cst, viol_out); }
-};
-
-// R seeded runs of the instance with the launches one run needs (mxs_gdba_create_replicas).  The slot view, the
+// The one host engine: R >= 1 seeded runs of the instance with the launches one run needs.  The slot view, the
 // tables, vref, mod_off, conc_first, dom, rank and the variable costs are stored once; cur, cost, has_cost, rec are
 // [R][n_vars], viol (and slot_vc where some variable cost is non-zero) [R][n_slots], the pool [R][plan.entries]; the
 // seeds are a device array.  The refusals, the allocations that grow with R, the start values of the variables
 // without neighbours and the cost launches are rephost::Host's (replica_host.h, shared with dsa.hip, mgm.hip and
 // mgm2.h); GDBA keeps its variables in graph order, so Host's q is the identity (graph_order).  A run's final state
 // is usually not its best: track_best keeps every replica's best state on the device, as DSA's does.
+// `single` (mxs_gdba_create): one replica under seeds = {seed} whose rounds are launched through the plain entry
+// points on the Dev base of g -- replica 0's slices are the buffers' bases.  It keeps the single run's API: its
+// replica cost is the host's eval_cost, it tracks no best state, and its budget refusal names no replicas.
 template <typename T>
-struct ReplicaEngine : Base {
+struct Engine : Base {
     rephost::Host<T> rh;
     DevR<T> g{};
+    bool single = false;
     Plan plan;
     mxs_host::DevSlots sl;
     size_t n_slots = 0;
@@ -710,8 +500,9 @@ struct ReplicaEngine : Base {
     Buf<int32_t> best_improved, best_idx;
 
     int init(const mxs_graph& G, const mxs_params& p, const int32_t* rk, const int32_t* vrk, int32_t modifier,
-             int32_t violation, int32_t increase_mode, const uint64_t* sds, int32_t n_replicas, int64_t budget,
-             int dev) override {
+             int32_t violation, int32_t increase_mode, const uint64_t* sds, int32_t n_replicas, bool one_run,
+             int64_t budget, int dev) override {
+        single = one_run;
         if (int rc = rh.open(sds, n_replicas, dev, true)) return rc;
         n_rep = rh.n_rep;
         if (int rc = check_params(modifier, violation, increase_mode, &budget)) return rc;
@@ -732,9 +523,11 @@ struct ReplicaEngine : Base {
         plan.build(increase_mode, hg.dom, hg.vrow, h_nb, hs);
         const int64_t one = plan.entries * (int64_t)sizeof(counter_t);
         if (plan.entries > budget / (int64_t)sizeof(counter_t) / n_rep)
-            return fail(MXS_E_INVALID, "gdba: the modifier tables of " + std::to_string(n_rep) + " replicas take " +
-                                           std::to_string(one * n_rep) + " bytes (" + std::to_string(one) +
-                                           " per replica), more than the budget of " + std::to_string(budget));
+            return fail(MXS_E_INVALID,
+                        (single ? "gdba: the modifier tables take " + std::to_string(one) + " bytes"
+                                : "gdba: the modifier tables of " + std::to_string(n_rep) + " replicas take " +
+                                      std::to_string(one * n_rep) + " bytes (" + std::to_string(one) + " per replica)") +
+                            ", more than the budget of " + std::to_string(budget));
         if (int rc = rh.graph_order(h_nb, rephost::blocks_of(nV, TPB))) return rc;
         n_slots = hs.base.size();
         if (int rc = sl.upload(hs, stream, nullptr, false)) return rc;  // no first-neighbour arrays, no rows
@@ -754,42 +547,26 @@ struct ReplicaEngine : Base {
         if (int rc = rephost::alloc_rep(rec, R * nV, "improvement records")) return rc;
         if (int rc = rephost::alloc_rep(viol, R * n_slots, "violation flags")) return rc;
         if (int rc = rephost::alloc_rep(slot_vc, any_vc ? R * n_slots : 0, "variable-cost sums")) return rc;
-        g.slots = sl.view();
-        g.n_vars = nV;
-        g.is_max = hg.is_max;
         g.modifier = modifier;
         g.violation = violation;
         g.increase_mode = increase_mode;
         g.has_var_cost = any_vc;
-        g.seed = 0;  // per block: seeds[r]
-        g.dom = rh.dom_size.p;
-        g.var_rowptr = rh.var_rowptr.p;
-        g.has_nb = rh.n_neigh.p;
-        g.rank = rank.p;
-        g.tables = rh.tables.p;
-        g.vref = vref.p;
-        g.mod_off = mod_off.p;
-        g.pool = pool.p;
-        g.conc_first = conc_first.p;
-        g.cost_off = rh.cost_off.p;
-        g.var_cost = var_cost.p;
-        g.cur = cur.p;
-        g.cost = cost.p;
-        g.has_cost = has_cost.p;
-        g.rec = rec.p;
-        g.viol = viol.p;
-        g.slot_vc = slot_vc.p;
-        g.bpr = 1;
-        g.n_rep = n_rep;
-        g.n_slots = (int64_t)n_slots;
-        g.n_pool = plan.entries;
-        g.seeds = rh.seeds.p;
-        g.dom_size = rh.dom_size.p;
-        g.factor_rowptr = rh.factor_rowptr.p;
-        g.edge_var = rh.edge_var.p;
-        g.q = rh.qmap.p;
-        g.table_off = rh.table_off.p;
+        bind();
         return reset();
+    }
+
+    // the kernels' argument: the Dev part, the per-replica arrays at their bases (replica 0's slices), then DevR's
+    void bind() {
+        g.slots = sl.view();
+        g.n_vars = rh.hg.nV, g.is_max = rh.hg.is_max;
+        g.seed = single ? rh.h_seeds[0] : 0;  // the replica kernels: seeds[r], per block
+        g.dom = rh.dom_size.p, g.var_rowptr = rh.var_rowptr.p, g.has_nb = rh.n_neigh.p, g.rank = rank.p;
+        g.tables = rh.tables.p, g.vref = vref.p, g.mod_off = mod_off.p, g.pool = pool.p;
+        g.conc_first = conc_first.p, g.cost_off = rh.cost_off.p, g.var_cost = var_cost.p;
+        g.cur = cur.p, g.cost = cost.p, g.has_cost = has_cost.p, g.rec = rec.p, g.viol = viol.p, g.slot_vc = slot_vc.p;
+        g.bpr = 1, g.n_rep = n_rep, g.n_slots = (int64_t)n_slots, g.n_pool = plan.entries, g.seeds = rh.seeds.p;
+        g.dom_size = rh.dom_size.p, g.factor_rowptr = rh.factor_rowptr.p, g.edge_var = rh.edge_var.p;
+        g.q = rh.qmap.p, g.table_off = rh.table_off.p;
     }
 
     // every replica back to its start state (k_gdbar_init), the pools and the violation flags cleared; the records
@@ -837,13 +614,21 @@ struct ReplicaEngine : Base {
         }
         const int vbpr = rephost::blocks_of(nV, TPB);
         const dim3 grid((unsigned)vbpr * (unsigned)n_rep), block(TPB);
+        const Dev<T>& one = g;  // what a single run's launches copy: the Dev part
         for (int32_t r = 0; r < n; ++r) {
             g.round = rounds + 1;
-            g.bpr = vbpr;  // (a kernel takes its DevR by value: the copy is made at the launch; record() sets its own)
-            hipLaunchKernelGGL((k_gdbar_eval<T>), grid, block, 0, stream, g);
-            MXS_TRY(hipGetLastError());
-            hipLaunchKernelGGL((k_gdbar_decide<T>), grid, block, 0, stream, g);
-            MXS_TRY(hipGetLastError());
+            g.bpr = vbpr;  // (a kernel takes its argument by value: the copy is made at the launch; record() sets its own)
+            if (single) {
+                hipLaunchKernelGGL((k_gdba_eval<T>), grid, block, 0, stream, one);
+                MXS_TRY(hipGetLastError());
+                hipLaunchKernelGGL((k_gdba_decide<T>), grid, block, 0, stream, one);
+                MXS_TRY(hipGetLastError());
+            } else {
+                hipLaunchKernelGGL((k_gdbar_eval<T>), grid, block, 0, stream, g);
+                MXS_TRY(hipGetLastError());
+                hipLaunchKernelGGL((k_gdbar_decide<T>), grid, block, 0, stream, g);
+                MXS_TRY(hipGetLastError());
+            }
             rounds += 1;
             if (every > 0 && rounds % every == 0)
                 if (int rc = record(1)) return rc;
@@ -874,7 +659,8 @@ struct ReplicaEngine : Base {
         return MXS_OK;
     }
 
-    // as Engine::get_modifiers, of replica r; slot -1: the bytes of the whole pool, all replicas
+    // slot -1: *n = the bytes of the whole pool, all replicas.  Otherwise *n = the number of modifiers stored for the
+    // slot (0: none); with `out`, those of replica r are copied (base + counter) -- capacity must hold them
     int get_modifiers(int32_t r, int32_t slot, int32_t* out, int64_t capacity, int64_t* n) override {
         if (r < 0 || r >= n_rep) return fail(MXS_E_INVALID, "replica out of range");
         if (slot == -1) {
@@ -900,7 +686,9 @@ struct ReplicaEngine : Base {
                             [&](int32_t* out) { return get_state(0, out, nullptr, nullptr, nullptr, nullptr); });
     }
 
+    // the device's reduction; a single run's cost is eval_cost's (the host's summation order)
     int replica_costs(double infinity, double* cst, int64_t* viol_out) override {
+        if (single) return eval_cost(nullptr, infinity, cst, viol_out);
         return rh.replica_costs(g, cur.p, infinity, cst, viol_out);
     }
 
@@ -909,7 +697,9 @@ struct ReplicaEngine : Base {
         every = 0;
     }
 
+    // (the best state is kept for mxs_gdba_create_replicas, one replica included)
     int track_best(int32_t ev, double infinity) override {
+        if (single) return fail(MXS_E_STATE, "gdba: the best state is tracked by the replica engine");
         if (ev < 0) return fail(MXS_E_INVALID, "every must be 0 (off) or positive");
         MXS_TRY(hipSetDevice(rh.device));
         drop_records();
@@ -937,7 +727,8 @@ struct ReplicaEngine : Base {
     }
 
     int get_best(int32_t r, int32_t* replica, int64_t* round, double* cst, int64_t* viol_out, int32_t* idx) override {
-        if (r < -1 || r >= n_rep) return fail(MXS_E_INVALID, "replica out of range");
+        // (a single run is never tracked -- track_best refuses it -- and answers so whatever r)
+        if (!single && (r < -1 || r >= n_rep)) return fail(MXS_E_INVALID, "replica out of range");
         if (!tracked) return fail(MXS_E_STATE, "mxs_gdba_get_best before mxs_gdba_track_best");
         MXS_TRY(hipSetDevice(rh.device));
         std::vector<double> hc;
@@ -978,14 +769,14 @@ extern "C" {
 int mxs_gdba_create(const mxs_graph* g, const mxs_params* p, const int32_t* name_rank, const int32_t* value_rank,
                     int32_t modifier, int32_t violation, int32_t increase_mode, uint64_t seed, int64_t pool_budget_bytes,
                     int32_t device, mxs_gdba** out) {
-    return mxs_host::create<mxs_gdba, gdba::Engine>(g, p, out, name_rank, value_rank, modifier, violation, increase_mode, seed,
-                                                    pool_budget_bytes, device);
+    return mxs_host::create<mxs_gdba, gdba::Engine>(g, p, out, name_rank, value_rank, modifier, violation, increase_mode,
+                                                    (const uint64_t*)&seed, 1, true, pool_budget_bytes, device);
 }
 int mxs_gdba_create_replicas(const mxs_graph* g, const mxs_params* p, const int32_t* name_rank, const int32_t* value_rank,
                              int32_t modifier, int32_t violation, int32_t increase_mode, const uint64_t* seeds,
                              int32_t n_replicas, int64_t pool_budget_bytes, int32_t device, mxs_gdba** out) {
-    return mxs_host::create<mxs_gdba, gdba::ReplicaEngine>(g, p, out, name_rank, value_rank, modifier, violation, increase_mode,
-                                                           seeds, n_replicas, pool_budget_bytes, device);
+    return mxs_host::create<mxs_gdba, gdba::Engine>(g, p, out, name_rank, value_rank, modifier, violation, increase_mode, seeds,
+                                                    n_replicas, false, pool_budget_bytes, device);
 }
 int mxs_gdba_replicas(const mxs_gdba* e, int32_t* n) {
     if (!e) return mxs_host::fail(MXS_E_INVALID, "null handle");

@@ -21,8 +21,9 @@
 // (assignment_cost, relations.py:1513-1531), through the slot view of local_search.h.
 //
 // REPLICAS (mxs_mgm2_create_replicas): R seeded runs advance with the same five launches, as in mgm.hip.  The five
-// phases are __device__ bodies (value_phase .. decide_phase) with two sets of __global__ entry points: k_mgm2_* on
-// the plain Dev -- what mxs_mgm2_create launches, argument layout and grid as before -- and k_mgm2r_* on DevR, where
+// phases are __device__ bodies (value_phase .. decide_phase) with two sets of __global__ entry points and ONE host
+// engine: k_mgm2_* on the plain Dev -- what an engine of mxs_mgm2_create launches for its one replica, argument layout
+// and grid as a single run has always had them -- and k_mgm2r_* on DevR, where
 // the replica is folded into blockIdx.x (block = r * bpr + b, replica_cost.h) and the block's copy of the argument
 // moves once to replica r's slice of the dynamic state and takes seeds[r] (enter_replica).  Everything static is
 // stored once; the state is [R][n_vars] / [R][n_entries] in GRAPH order (there is no packed order here).  The start
@@ -419,7 +420,7 @@ __global__ void __launch_bounds__(AUX_TPB) k_mgm2r_init(DevR<T> g, const int32_t
     g.has_cost[v] = g.has_nb[v] ? 0 : 1;
 }
 
-// ---- the host side the two engines share
+// ---- the host side
 inline int check_params(double threshold, int32_t favor) {
     if (!(threshold >= 0.0 && threshold <= 1.0)) return fail(MXS_E_INVALID, "threshold must be in [0, 1]");
     if (favor < 0 || favor > 2) return fail(MXS_E_INVALID, "favor must be 0 (unilateral), 1 (no) or 2 (coordinated)");
@@ -484,15 +485,11 @@ inline std::vector<int32_t> ranks_or_index(const int32_t* rk, int nV) {
     return h;
 }
 
+// Engine<T> behind struct mxs_mgm2, whatever its T
 struct Base {
     virtual ~Base() = default;
-    // mxs_mgm2_create (Engine) / mxs_mgm2_create_replicas (ReplicaEngine)
-    virtual int init(const mxs_graph&, const mxs_params&, const int32_t*, double, int32_t, uint64_t, int) {
-        return fail(MXS_E_STATE, "mgm2: not the single-run engine");
-    }
-    virtual int init(const mxs_graph&, const mxs_params&, const int32_t*, double, int32_t, const uint64_t*, int32_t, int) {
-        return fail(MXS_E_STATE, "mgm2: not the replica engine");
-    }
+    virtual int init(const mxs_graph& G, const mxs_params& p, const int32_t* name_rank, double threshold, int32_t favor,
+                     const uint64_t* seeds, int32_t n_replicas, bool single, int dev) = 0;
     virtual int reset() = 0;
     virtual int run(int32_t n) = 0;
     virtual int get_state(int32_t r, int32_t* idx, double* cost, uint8_t* has_cost) = 0;
@@ -503,191 +500,20 @@ struct Base {
     int32_t n_rep = 1;
 };
 
-template <typename T>
-struct Engine : Base {
-    int device = 0;
-    hipStream_t stream = nullptr;
-    Dev<T> g{};
-    mxs_host::HostGraph hg;
-    std::vector<int32_t> h_nb;
-    lsearch::HostSlots hs;
-    Buf<int32_t> dom, var_rowptr, has_nb, rank, off_w, ent_var, cur;
-    Buf<int64_t> off_off;
-    mxs_host::DevSlots sl;
-    Buf<T> tables, cost, offer;
-    Buf<uint8_t> has_cost, offer_ok;
-    Buf<Rec<T>> uni, recv;
-
-    ~Engine() override {
-        if (stream) (void)hipStreamDestroy(stream);
-    }
-
-    int init(const mxs_graph& G, const mxs_params& p, const int32_t* rk, double threshold, int32_t favor, uint64_t seed,
-             int dev) override {
-        device = dev;
-        if (int rc = mxs_host::open_device(dev, &stream)) return rc;
-        if (int rc = check_params(threshold, favor)) return rc;
-        if (int rc = hg.load(G, p)) return rc;
-        const int nV = hg.nV, nF = hg.nF;
-        if (int rc = check_tables(hg)) return rc;
-        if (int rc = hg.load_init(G)) return rc;
-        const std::string bad = hs.build(nV, nF, hg.dom, hg.frow, hg.evar, hg.toff, hg.vrow, hg.vedges);
-        if (!bad.empty()) return fail(MXS_E_INVALID, bad);
-        Layout lay;
-        if (int rc = lay.build(hg, hs)) return rc;
-        h_nb = lay.has_nb;
-        const std::vector<int32_t>&h_w = lay.width, &h_ent = lay.ent_var;
-        const std::vector<int64_t>& h_off = lay.off;
-        const std::vector<int32_t> h_rank = ranks_or_index(rk, nV);
-        if (int rc = sl.upload(hs, stream, nullptr, false)) return rc;  // no first-neighbour arrays, no rows
-        MXS_TRY(dom.upload(hg.dom, stream));
-        MXS_TRY(var_rowptr.upload(hg.vrow, stream));
-        MXS_TRY(has_nb.upload(h_nb, stream));
-        MXS_TRY(rank.upload(h_rank, stream));
-        MXS_TRY(off_w.upload(h_w, stream));
-        MXS_TRY(off_off.upload(h_off, stream));
-        MXS_TRY(ent_var.upload(h_ent, stream));
-        MXS_TRY(tables.upload(mxs_host::narrowed<T>(hg.tables), stream));
-        MXS_TRY(cur.alloc(nV));
-        MXS_TRY(cost.alloc(nV));
-        MXS_TRY(has_cost.alloc(nV));
-        MXS_TRY(uni.alloc(nV));
-        MXS_TRY(recv.alloc(nV));
-        MXS_TRY(offer.alloc((size_t)h_off[nV]));
-        MXS_TRY(offer_ok.alloc((size_t)h_off[nV]));
-        g.slots = sl.view();
-        g.n_vars = nV;
-        g.is_max = p.mode == MXS_MODE_MAX;
-        g.favor = favor;
-        g.threshold = threshold;
-        g.seed = seed;
-        g.dom = dom.p;
-        g.var_rowptr = var_rowptr.p;
-        g.has_nb = has_nb.p;
-        g.rank = rank.p;
-        g.off_off = off_off.p;
-        g.off_w = off_w.p;
-        g.ent_var = ent_var.p;
-        g.n_entries = h_off[nV];
-        g.tables = tables.p;
-        g.cur = cur.p;
-        g.cost = cost.p;
-        g.has_cost = has_cost.p;
-        g.uni = uni.p;
-        g.recv = recv.p;
-        g.offer = offer.p;
-        g.offer_ok = offer_ok.p;
-        return reset();
-    }
-
-    // on_start (:460-495): a variable with neighbours takes its initial value or a random one (held cost None);
-    // one without neighbours takes a random best value of its own constraints and is finished
-    int reset() override {
-        MXS_TRY(hipSetDevice(device));
-        const int nV = g.n_vars;
-        std::vector<int32_t> c0(nV);
-        std::vector<T> k0(nV, (T)0);
-        std::vector<uint8_t> h0(nV, 0);
-        std::vector<int32_t> vals;
-        for (int v = 0; v < nV; ++v) {
-            const double u = uniform(g.seed, v, 0, D_START);
-            if (h_nb[v]) {
-                c0[v] = hg.init[v] >= 0 ? hg.init[v] : (int)(u * hg.dom[v]);
-                continue;
-            }
-            k0[v] = best_own_values<T>(hg, hs, v, vals);
-            c0[v] = vals[(size_t)(int)(u * (int)vals.size())];
-            h0[v] = 1;
-        }
-        if (nV) {
-            MXS_TRY(hipMemcpyAsync(cur.p, c0.data(), 4 * (size_t)nV, hipMemcpyHostToDevice, stream));
-            MXS_TRY(hipMemcpyAsync(cost.p, k0.data(), sizeof(T) * nV, hipMemcpyHostToDevice, stream));
-            MXS_TRY(hipMemcpyAsync(has_cost.p, h0.data(), nV, hipMemcpyHostToDevice, stream));
-            MXS_TRY(hipStreamSynchronize(stream));
-        }
-        rounds = 0;
-        return MXS_OK;
-    }
-
-    int run(int32_t n) override {
-        MXS_TRY(hipSetDevice(device));
-        const int nV = g.n_vars;
-        if (nV == 0) {
-            rounds += n > 0 ? n : 0;
-            return MXS_OK;
-        }
-        const dim3 grid((unsigned)((nV + TPB - 1) / TPB)), block(TPB);
-        const dim3 ogrid((unsigned)((g.n_entries + OTPB - 1) / OTPB)), oblock(OTPB);
-        for (int32_t r = 0; r < n; ++r) {
-            g.round = rounds + 1;
-            hipLaunchKernelGGL((k_mgm2_value<T>), grid, block, 0, stream, g);
-            MXS_TRY(hipGetLastError());
-            if (g.n_entries > 0) {
-                hipLaunchKernelGGL((k_mgm2_offers<T>), ogrid, oblock, 0, stream, g);
-                MXS_TRY(hipGetLastError());
-            }
-            hipLaunchKernelGGL((k_mgm2_receive<T>), grid, block, 0, stream, g);
-            MXS_TRY(hipGetLastError());
-            hipLaunchKernelGGL((k_mgm2_resolve<T>), grid, block, 0, stream, g);
-            MXS_TRY(hipGetLastError());
-            hipLaunchKernelGGL((k_mgm2_decide<T>), grid, block, 0, stream, g);
-            MXS_TRY(hipGetLastError());
-            rounds += 1;
-        }
-        MXS_TRY(hipStreamSynchronize(stream));
-        return MXS_OK;
-    }
-
-    int get_state(int32_t r, int32_t* idx, double* cst, uint8_t* has) override {
-        if (r != 0) return fail(MXS_E_INVALID, "replica out of range");
-        MXS_TRY(hipSetDevice(device));
-        const int nV = g.n_vars;
-        if (!nV) return MXS_OK;
-        std::vector<T> hc(nV);
-        std::vector<int32_t> hi(nV);
-        std::vector<uint8_t> hh(nV);
-        MXS_TRY(hipMemcpyAsync(hi.data(), cur.p, 4 * (size_t)nV, hipMemcpyDeviceToHost, stream));
-        MXS_TRY(hipMemcpyAsync(hh.data(), has_cost.p, nV, hipMemcpyDeviceToHost, stream));
-        MXS_TRY(hipMemcpyAsync(hc.data(), cost.p, sizeof(T) * nV, hipMemcpyDeviceToHost, stream));
-        MXS_TRY(hipStreamSynchronize(stream));
-        for (int v = 0; v < nV; ++v) {
-            if (idx) idx[v] = hi[v];
-            if (has) has[v] = hh[v];
-            if (cst) cst[v] = (double)hc[v];
-        }
-        return MXS_OK;
-    }
-
-    // DCOP.solution_cost of an assignment (the variables' own costs included, unlike the search itself)
-    int eval_cost(const int32_t* idx, double infinity, double* cst, int64_t* viol) override {
-        std::vector<int32_t> c;
-        if (!idx) {
-            c.resize(g.n_vars);
-            int rc = get_state(0, c.data(), nullptr, nullptr);
-            if (rc) return rc;
-            idx = c.data();
-        }
-        return hg.eval_cost(idx, infinity, cst, viol);
-    }
-
-    // one run: its cost is eval_cost's, and it is the best replica
-    int replica_costs(double infinity, double* cst, int64_t* viol) override { return eval_cost(nullptr, infinity, cst, viol); }
-    int best_replica(double infinity, int32_t* replica, double* cst, int64_t* viol) override {
-        if (replica) *replica = 0;
-        return eval_cost(nullptr, infinity, cst, viol);
-    }
-};
-
-// R seeded runs of the instance with the launches one run needs (mxs_mgm2_create_replicas).  The slot view, the
+// The one host engine: R >= 1 seeded runs of the instance with the launches one run needs.  The slot view, the
 // tables, dom, rank and the offer tables' layout are stored once; cur, cost, has_cost, uni, recv are [R][n_vars],
 // offer and offer_ok [R][n_entries]; the seeds are a device array.  The refusals, the allocations that grow with R
 // and the cost launches are rephost::Host's (replica_host.h, shared with dsa.hip and mgm.hip); MGM-2 keeps its
 // variables in graph order, so Host's q is the identity (graph_order).  MGM-2's sum stops improving at a local
 // optimum and is not tracked: the CURRENT states are ranked (repcost::best_replica).
+// `single` (mxs_mgm2_create): one replica under seeds = {seed} whose rounds are launched through the plain entry
+// points on the Dev base of g -- replica 0's slices are the buffers' bases.  It keeps the single run's API: its
+// replica cost, and the best replica's, is the host's eval_cost.
 template <typename T>
-struct ReplicaEngine : Base {
+struct Engine : Base {
     rephost::Host<T> rh;
     DevR<T> g{};
+    bool single = false;
     mxs_host::DevSlots sl;
     Buf<int32_t> rank, off_w, ent_var, init_idx, best_val;
     Buf<int64_t> off_off, best_off;
@@ -698,7 +524,8 @@ struct ReplicaEngine : Base {
     Buf<Rec<T>> uni, recv;
 
     int init(const mxs_graph& G, const mxs_params& p, const int32_t* rk, double threshold, int32_t favor,
-             const uint64_t* sds, int32_t n_replicas, int dev) override {
+             const uint64_t* sds, int32_t n_replicas, bool one_run, int dev) override {
+        single = one_run;
         if (int rc = rh.open(sds, n_replicas, dev, true)) return rc;
         n_rep = rh.n_rep;
         if (int rc = check_params(threshold, favor)) return rc;
@@ -746,37 +573,25 @@ struct ReplicaEngine : Base {
         if (int rc = rephost::alloc_rep(recv, R * nV, "receiver records")) return rc;
         if (int rc = rephost::alloc_rep(offer, R * (size_t)nE, "offer tables")) return rc;
         if (int rc = rephost::alloc_rep(offer_ok, R * (size_t)nE, "offer tables")) return rc;
-        g.slots = sl.view();
-        g.n_vars = nV;
-        g.is_max = hg.is_max;
         g.favor = favor;
         g.threshold = threshold;
-        g.seed = 0;  // per block: seeds[r]
-        g.dom = rh.dom_size.p;
-        g.var_rowptr = rh.var_rowptr.p;
-        g.has_nb = rh.n_neigh.p;
-        g.rank = rank.p;
-        g.off_off = off_off.p;
-        g.off_w = off_w.p;
-        g.ent_var = ent_var.p;
         g.n_entries = nE;
-        g.tables = rh.tables.p;
-        g.cur = cur.p;
-        g.cost = cost.p;
-        g.has_cost = has_cost.p;
-        g.uni = uni.p;
-        g.recv = recv.p;
-        g.offer = offer.p;
-        g.offer_ok = offer_ok.p;
-        g.bpr = 1;
-        g.n_rep = n_rep;
-        g.seeds = rh.seeds.p;
-        g.dom_size = rh.dom_size.p;
-        g.factor_rowptr = rh.factor_rowptr.p;
-        g.edge_var = rh.edge_var.p;
-        g.q = rh.qmap.p;
-        g.table_off = rh.table_off.p;
+        bind();
         return reset();
+    }
+
+    // the kernels' argument: the Dev part, the per-replica arrays at their bases (replica 0's slices), then DevR's
+    void bind() {
+        g.slots = sl.view();
+        g.n_vars = rh.hg.nV, g.is_max = rh.hg.is_max;
+        g.seed = single ? rh.h_seeds[0] : 0;  // the replica kernels: seeds[r], per block
+        g.dom = rh.dom_size.p, g.var_rowptr = rh.var_rowptr.p, g.has_nb = rh.n_neigh.p, g.rank = rank.p;
+        g.off_off = off_off.p, g.off_w = off_w.p, g.ent_var = ent_var.p, g.tables = rh.tables.p;
+        g.cur = cur.p, g.cost = cost.p, g.has_cost = has_cost.p, g.uni = uni.p, g.recv = recv.p;
+        g.offer = offer.p, g.offer_ok = offer_ok.p;
+        g.bpr = 1, g.n_rep = n_rep, g.seeds = rh.seeds.p;
+        g.dom_size = rh.dom_size.p, g.factor_rowptr = rh.factor_rowptr.p, g.edge_var = rh.edge_var.p;
+        g.q = rh.qmap.p, g.table_off = rh.table_off.p;
     }
 
     // every replica back to its start state (k_mgm2r_init): nothing is uploaded
@@ -805,23 +620,39 @@ struct ReplicaEngine : Base {
         const int vbpr = rephost::blocks_of(nV, TPB), obpr = rephost::blocks_of(g.n_entries, OTPB);
         const dim3 grid((unsigned)vbpr * (unsigned)n_rep), block(TPB);
         const dim3 ogrid((unsigned)obpr * (unsigned)n_rep), oblock(OTPB);
+        const Dev<T>& one = g;  // what a single run's launches copy: the Dev part
         for (int32_t r = 0; r < n; ++r) {
             g.round = rounds + 1;
-            g.bpr = vbpr;  // (a kernel takes its DevR by value: the copy is made at the launch)
-            hipLaunchKernelGGL((k_mgm2r_value<T>), grid, block, 0, stream, g);
-            MXS_TRY(hipGetLastError());
-            if (g.n_entries > 0) {
-                g.bpr = obpr;
-                hipLaunchKernelGGL((k_mgm2r_offers<T>), ogrid, oblock, 0, stream, g);
+            if (single) {
+                hipLaunchKernelGGL((k_mgm2_value<T>), grid, block, 0, stream, one);
                 MXS_TRY(hipGetLastError());
-                g.bpr = vbpr;
+                if (g.n_entries > 0) {
+                    hipLaunchKernelGGL((k_mgm2_offers<T>), ogrid, oblock, 0, stream, one);
+                    MXS_TRY(hipGetLastError());
+                }
+                hipLaunchKernelGGL((k_mgm2_receive<T>), grid, block, 0, stream, one);
+                MXS_TRY(hipGetLastError());
+                hipLaunchKernelGGL((k_mgm2_resolve<T>), grid, block, 0, stream, one);
+                MXS_TRY(hipGetLastError());
+                hipLaunchKernelGGL((k_mgm2_decide<T>), grid, block, 0, stream, one);
+                MXS_TRY(hipGetLastError());
+            } else {
+                g.bpr = vbpr;  // (a kernel takes its DevR by value: the copy is made at the launch)
+                hipLaunchKernelGGL((k_mgm2r_value<T>), grid, block, 0, stream, g);
+                MXS_TRY(hipGetLastError());
+                if (g.n_entries > 0) {
+                    g.bpr = obpr;
+                    hipLaunchKernelGGL((k_mgm2r_offers<T>), ogrid, oblock, 0, stream, g);
+                    MXS_TRY(hipGetLastError());
+                    g.bpr = vbpr;
+                }
+                hipLaunchKernelGGL((k_mgm2r_receive<T>), grid, block, 0, stream, g);
+                MXS_TRY(hipGetLastError());
+                hipLaunchKernelGGL((k_mgm2r_resolve<T>), grid, block, 0, stream, g);
+                MXS_TRY(hipGetLastError());
+                hipLaunchKernelGGL((k_mgm2r_decide<T>), grid, block, 0, stream, g);
+                MXS_TRY(hipGetLastError());
             }
-            hipLaunchKernelGGL((k_mgm2r_receive<T>), grid, block, 0, stream, g);
-            MXS_TRY(hipGetLastError());
-            hipLaunchKernelGGL((k_mgm2r_resolve<T>), grid, block, 0, stream, g);
-            MXS_TRY(hipGetLastError());
-            hipLaunchKernelGGL((k_mgm2r_decide<T>), grid, block, 0, stream, g);
-            MXS_TRY(hipGetLastError());
             rounds += 1;
         }
         MXS_TRY(hipStreamSynchronize(stream));
@@ -849,11 +680,17 @@ struct ReplicaEngine : Base {
         return rh.eval_cost(idx, infinity, cst, viol, [&](int32_t* out) { return get_state(0, out, nullptr, nullptr); });
     }
 
+    // the device's reduction; a single run's cost is eval_cost's (the host's summation order), and it is the best replica
     int replica_costs(double infinity, double* cst, int64_t* viol) override {
+        if (single) return eval_cost(nullptr, infinity, cst, viol);
         return rh.replica_costs(g, cur.p, infinity, cst, viol);
     }
 
     int best_replica(double infinity, int32_t* replica, double* cst, int64_t* viol) override {
+        if (single) {
+            if (replica) *replica = 0;
+            return eval_cost(nullptr, infinity, cst, viol);
+        }
         std::vector<double> hc;
         std::vector<long long> hv;
         if (int rc = rh.current_costs(g, cur.p, infinity, hc, hv)) return rc;
@@ -875,11 +712,12 @@ extern "C" {
 
 int mxs_mgm2_create(const mxs_graph* g, const mxs_params* p, const int32_t* name_rank, double threshold, int32_t favor,
                     uint64_t seed, int32_t device, mxs_mgm2** out) {
-    return mxs_host::create<mxs_mgm2, mgm2::Engine>(g, p, out, name_rank, threshold, favor, seed, device);
+    return mxs_host::create<mxs_mgm2, mgm2::Engine>(g, p, out, name_rank, threshold, favor, (const uint64_t*)&seed, 1, true,
+                                                    device);
 }
 int mxs_mgm2_create_replicas(const mxs_graph* g, const mxs_params* p, const int32_t* name_rank, double threshold,
                              int32_t favor, const uint64_t* seeds, int32_t n_replicas, int32_t device, mxs_mgm2** out) {
-    return mxs_host::create<mxs_mgm2, mgm2::ReplicaEngine>(g, p, out, name_rank, threshold, favor, seeds, n_replicas, device);
+    return mxs_host::create<mxs_mgm2, mgm2::Engine>(g, p, out, name_rank, threshold, favor, seeds, n_replicas, false, device);
 }
 int mxs_mgm2_replicas(const mxs_mgm2* e, int32_t* n) {
     if (!e) return mxs_host::fail(MXS_E_INVALID, "null handle");

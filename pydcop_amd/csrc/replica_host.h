@@ -1,10 +1,12 @@
 // replica_host.h -- the host side of an engine that advances R seeded runs of one instance with the same launches
-// (dsa.hip, mgm.hip, mgm2.h; the device side is replica_cost.h): what such an engine owns whatever its algorithm, and
-// the steps of its life that do not depend on the algorithm.  Host code only: no kernel, no kernel-argument layout.  An
-// engine HOLDS a Host<T> and supplies its Dev (the kernels' argument), its per-lane extras (built from the host views
-// between build_views and upload_views), its init kernel (after start_values) and the launches of a cycle.  MGM-2
-// brings its own view and keeps its state in graph order: it takes open, graph_order / upload_order in place of
-// build_views / upload_views, upload_graph, alloc_rep and the cost launches, and binds its DevR itself.
+// (dsa.hip, mgm.hip, mgm2.h, gdba.h; the device side is replica_cost.h): what such an engine owns whatever its
+// algorithm, and the steps of its life that do not depend on the algorithm.  Host code only: no kernel, no
+// kernel-argument layout.  Every one of the four algorithms has ONE host engine on it, a single run being the case
+// R = 1.  An engine HOLDS a Host<T> and supplies its Dev (the kernels' argument), its per-lane extras (built from the
+// host views between build_views and upload_views), its init kernel (after start_values) and the launches of a cycle.
+// MGM-2 and GDBA bring their own view and keep their state in graph order: they take open, graph_order /
+// upload_order in place of build_views / upload_views, upload_graph, alloc_rep and the cost launches, and bind their
+// DevR themselves; their mxs_*_create engine launches its one replica through the plain-Dev entry points.
 #pragma once
 
 #include <hip/hip_runtime.h>

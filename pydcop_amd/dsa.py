@@ -29,6 +29,7 @@ class DsaEngine(ReplicaBinding):
     """
     PREFIX = "mxs_dsa"
     COUNTER = "cycles"
+    STATE_FIELDS = (("idx", np.int32), ("cost", np.float64))
 
     def __init__(self, graph: FlatGraph, params: Optional[Params] = None, variant: str = "B",
                  probability: float = 0.7, p_mode: str = "fixed", seed: int = 0, device: int = 0,
@@ -54,12 +55,6 @@ class DsaEngine(ReplicaBinding):
 
     def run(self, n_cycles: int):
         self._call("run", int(n_cycles))
-
-    def assignment(self, replica: int = 0) -> Tuple[np.ndarray, np.ndarray]:
-        idx = np.empty(self.graph.n_vars, dtype=np.int32)
-        cost = np.empty(self.graph.n_vars)
-        self._call("get_state_replica", int(replica), idx.ctypes.data, cost.ctypes.data)
-        return idx, cost
 
     def track_best(self, every: int = 1, infinity: float = float("inf")):
         """Keep, per replica, the best state seen at cycle 0 and after every `every`-th cycle (0: off; the

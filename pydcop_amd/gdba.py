@@ -7,7 +7,7 @@ from typing import Dict, Optional, Sequence, Tuple
 import numpy as np
 
 from ._binding import ReplicaBinding
-from .engine import GDBA_REPLICA_SYMBOLS as REPLICA_SYMBOLS, MaxSumGpuError, load_library
+from .engine import GDBA_REPLICA_SYMBOLS as REPLICA_SYMBOLS, load_library
 from .graph import FlatGraph, Params
 from .mgm import name_ranks
 
@@ -42,9 +42,14 @@ class GdbaEngine(ReplicaBinding):
     >>> eng.track_best(every=1, infinity=10000)
     >>> eng.run(30)
     >>> eng.best()                                     # the best replica's record
-    `replicas=1` without `seeds` is the single-run engine (`mxs_gdba_create`); it tracks no best state."""
+    `replicas=1` without `seeds` is the single run (`mxs_gdba_create`: the same engine with one replica, launched
+    through the single-run kernels); it tracks no best state."""
     PREFIX = "mxs_gdba"
     COUNTER = "rounds"
+    STATE_FIELDS = (("idx", np.int32), ("cost", np.float64), ("has_cost", np.uint8), ("improve", np.float64),
+                    ("new", np.int32))
+    REPLICA_SYMBOLS = REPLICA_SYMBOLS
+    REPLICA_FEATURE = "GDBA's replicas"
 
     def __init__(self, graph: FlatGraph, params: Optional[Params] = None, modifier: str = "A", violation: str = "NZ",
                  increase_mode: str = "E", seed: int = 0, pool_budget: int = 0, device: int = 0,
@@ -73,34 +78,11 @@ class GdbaEngine(ReplicaBinding):
                                                            int(device), C.byref(h)))
         self._h = h
 
-    def _need_replica_symbols(self, why):
-        missing = [n for n in REPLICA_SYMBOLS if not hasattr(self._lib, n)]
-        if missing:
-            raise MaxSumGpuError(
-                f"{self._lib._name} was built from sources without GDBA's replicas (no {', '.join(missing)}): "
-                f"rebuild the library, {why}")
-
     def reset(self):
         self._call("reset")
 
     def run(self, n_rounds: int):
         self._call("run", int(n_rounds))
-
-    def state(self, replica: int = 0) -> dict:
-        n = self.graph.n_vars
-        out = {"idx": np.empty(n, dtype=np.int32), "cost": np.empty(n), "has_cost": np.empty(n, dtype=np.uint8),
-               "improve": np.empty(n), "new": np.empty(n, dtype=np.int32)}
-        ptrs = [out[k].ctypes.data for k in ("idx", "cost", "has_cost", "improve", "new")]
-        if int(replica) == 0:       # (the call every version of the library has)
-            self._call("get_state", *ptrs)
-        else:
-            self._need_replica_symbols("state(replica) needs them")
-            self._call("get_state_replica", int(replica), *ptrs)
-        return out
-
-    def assignment(self, replica: int = 0) -> Tuple[np.ndarray, np.ndarray]:
-        s = self.state(replica)
-        return s["idx"], s["cost"]
 
     def modifiers(self, slot: int, replica: int = 0) -> np.ndarray:
         """The modifier table of slot = var_rowptr[v] + k (variable v, its k-th constraint) of `replica`, in the layout

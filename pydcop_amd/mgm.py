@@ -7,7 +7,7 @@ from typing import Dict, Optional, Sequence, Tuple
 import numpy as np
 
 from ._binding import ReplicaBinding
-from .engine import MaxSumGpuError, load_library
+from .engine import load_library
 from .graph import FlatGraph, Params
 
 DRAWS = ("fixed", "keyed")
@@ -41,6 +41,10 @@ class MgmEngine(ReplicaBinding):
     """
     PREFIX = "mxs_mgm"
     COUNTER = "rounds"
+    STATE_FIELDS = (("idx", np.int32), ("cost", np.float64), ("has_cost", np.uint8), ("gain", np.float64),
+                    ("new", np.int32))
+    REPLICA_SYMBOLS = KEYED_SYMBOLS
+    REPLICA_FEATURE = "MGM's keyed draws"
 
     def __init__(self, graph: FlatGraph, params: Optional[Params] = None, device: int = 0,
                  lib_path: Optional[str] = None, draws: str = "fixed", seed: int = 0,
@@ -61,11 +65,7 @@ class MgmEngine(ReplicaBinding):
         if draws == "fixed":
             self._check(self._lib.mxs_mgm_create(C.byref(cg), C.byref(cp), rank, int(device), C.byref(h)))
         else:
-            missing = [n for n in KEYED_SYMBOLS if not hasattr(self._lib, n)]
-            if missing:
-                raise MaxSumGpuError(
-                    f"{self._lib._name} was built from sources without MGM's keyed draws (no {', '.join(missing)}): "
-                    "rebuild the library, draws=\"keyed\" needs them")
+            self._need_replica_symbols("draws=\"keyed\" needs them")
             self._check(self._lib.mxs_mgm_create_keyed(C.byref(cg), C.byref(cp), rank, sd.ctypes.data, self.replicas,
                                                        int(device), C.byref(h)))
         self._h = h
@@ -76,21 +76,6 @@ class MgmEngine(ReplicaBinding):
 
     def run(self, n_rounds: int):
         self._call("run", int(n_rounds))
-
-    def state(self, replica: int = 0) -> dict:
-        n = self.graph.n_vars
-        out = {"idx": np.empty(n, dtype=np.int32), "cost": np.empty(n), "has_cost": np.empty(n, dtype=np.uint8),
-               "gain": np.empty(n), "new": np.empty(n, dtype=np.int32)}
-        ptrs = [out[k].ctypes.data for k in ("idx", "cost", "has_cost", "gain", "new")]
-        if int(replica) == 0:       # (the call every version of the library has)
-            self._call("get_state", *ptrs)
-        else:
-            self._call("get_state_replica", int(replica), *ptrs)
-        return out
-
-    def assignment(self, replica: int = 0) -> Tuple[np.ndarray, np.ndarray]:
-        s = self.state(replica)
-        return s["idx"], s["cost"]
 
     def _keyed_only(self, what):
         if self.draws != "keyed":

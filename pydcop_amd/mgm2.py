@@ -7,7 +7,7 @@ from typing import Dict, Optional, Sequence, Tuple
 import numpy as np
 
 from ._binding import ReplicaBinding
-from .engine import MaxSumGpuError, load_library
+from .engine import load_library
 from .graph import FlatGraph, Params
 from .mgm import name_ranks
 
@@ -41,9 +41,13 @@ class Mgm2Engine(ReplicaBinding):
     >>> eng = Mgm2Engine(graph, favor="coordinated", replicas=8, seed=5)
     >>> eng.run(30)
     >>> eng.best(infinity=10000)                       # the best replica's current state
-    `replicas=1` without `seeds` is the single-run engine (`mxs_mgm2_create`)."""
+    `replicas=1` without `seeds` is the single run (`mxs_mgm2_create`: the same engine with one replica, launched
+    through the single-run kernels)."""
     PREFIX = "mxs_mgm2"
     COUNTER = "rounds"
+    STATE_FIELDS = (("idx", np.int32), ("cost", np.float64), ("has_cost", np.uint8))
+    REPLICA_SYMBOLS = REPLICA_SYMBOLS
+    REPLICA_FEATURE = "MGM-2's replicas"
 
     def __init__(self, graph: FlatGraph, params: Optional[Params] = None, threshold: float = 0.5,
                  favor: str = "unilateral", seed: int = 0, device: int = 0, lib_path: Optional[str] = None,
@@ -68,33 +72,11 @@ class Mgm2Engine(ReplicaBinding):
                                                            sd.ctypes.data, self.replicas, int(device), C.byref(h)))
         self._h = h
 
-    def _need_replica_symbols(self, why):
-        missing = [n for n in REPLICA_SYMBOLS if not hasattr(self._lib, n)]
-        if missing:
-            raise MaxSumGpuError(
-                f"{self._lib._name} was built from sources without MGM-2's replicas (no {', '.join(missing)}): "
-                f"rebuild the library, {why}")
-
     def reset(self):
         self._call("reset")
 
     def run(self, n_rounds: int):
         self._call("run", int(n_rounds))
-
-    def state(self, replica: int = 0) -> dict:
-        n = self.graph.n_vars
-        out = {"idx": np.empty(n, dtype=np.int32), "cost": np.empty(n), "has_cost": np.empty(n, dtype=np.uint8)}
-        ptrs = [out[k].ctypes.data for k in ("idx", "cost", "has_cost")]
-        if int(replica) == 0:       # (the call every version of the library has)
-            self._call("get_state", *ptrs)
-        else:
-            self._need_replica_symbols("state(replica) needs them")
-            self._call("get_state_replica", int(replica), *ptrs)
-        return out
-
-    def assignment(self, replica: int = 0) -> Tuple[np.ndarray, np.ndarray]:
-        s = self.state(replica)
-        return s["idx"], s["cost"]
 
     def replica_costs(self, infinity: float = float("inf")) -> Tuple[np.ndarray, np.ndarray]:
         self._need_replica_symbols("replica_costs needs them")
