@@ -1,7 +1,7 @@
 """What the ctypes bindings of the `mxs_dsa_*`, `mxs_mgm_*`, `mxs_mgm2_*`, `mxs_gdba_*`, `mxs_dba_*` and `mxs_dpop_*` entry points
 (include/maxsum_gpu.h) share: the handle, the error check, `eval_cost`, the cycle counter and the life cycle."""
 import ctypes as C
-from typing import Optional, Sequence, Tuple
+from typing import Dict, Optional, Sequence, Tuple
 
 import numpy as np
 
@@ -111,3 +111,23 @@ class ReplicaBinding(EngineBinding):
         viol = np.empty(self.replicas, dtype=np.int64)
         self._call("replica_costs", float(infinity), cost.ctypes.data, viol.ctypes.data)
         return cost, viol
+
+    # what the public `track_best` / `best` of the engines call after their own guard (the docstrings are theirs)
+
+    def _track_best(self, every: int, infinity: float):
+        self._call("track_best", int(every), float(infinity))
+
+    def _best_record(self, replica: int) -> Dict:
+        """`<PREFIX>_get_best`: the record of an engine that tracks the best state"""
+        r, cyc, cost, viol = C.c_int32(0), C.c_int64(0), C.c_double(0), C.c_int64(0)
+        idx = np.empty(self.graph.n_vars, dtype=np.int32)
+        self._call("get_best", int(replica), C.byref(r), C.byref(cyc), C.byref(cost), C.byref(viol), idx.ctypes.data)
+        return {"replica": int(r.value), "cycle": int(cyc.value), "cost": float(cost.value),
+                "violations": int(viol.value), "idx": idx}
+
+    def _best_ranked(self, infinity: float) -> Dict:
+        """`<PREFIX>_best_replica`: the best current state of an engine that keeps no records"""
+        r, cost, viol = C.c_int32(0), C.c_double(0), C.c_int64(0)
+        self._call("best_replica", float(infinity), C.byref(r), C.byref(cost), C.byref(viol))
+        return {"replica": int(r.value), "cost": float(cost.value), "violations": int(viol.value),
+                "idx": self.state(int(r.value))["idx"]}

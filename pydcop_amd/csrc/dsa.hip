@@ -16,10 +16,10 @@
 // replica, everything a kernel derives from the replica is block-uniform (R = 1 runs instantiations without it).  Replica r is bit for bit the
 // single-seed run with seed seeds[r]; mxs_dsa_create is R = 1 of the same path.  Per replica, the solution
 // cost of the current assignment is reduced on the device (replica_cost.h, shared with mgm.hip: fixed
-// shape, no atomics) and the best state seen can be kept on the device (k_dsa_best_copy).  The host side that does
-// not depend on the algorithm -- set-up, views, uploads, start values, the cost launches -- is rephost::Host
-// (replica_host.h, shared with mgm.hip); this file keeps the kernels, Dev, the per-lane extras, the cycle's
-// launches and the best-state tracking.
+// shape, no atomics) and the best state seen can be kept on the device (rephost::BestTracker, repcost::k_best_copy).
+// The host side that does not depend on the algorithm -- set-up, views, uploads, start values, the cost launches,
+// the best-state records -- is rephost::Host and rephost::BestTracker (replica_host.h, shared with mgm.hip); this
+// file keeps the kernels, Dev, the per-lane extras and the cycle's launches.
 //
 // The reference draws from Python's unseeded `random` module (initial value, move test, choice
 // among the best values).  Here every draw comes from a counter-based generator keyed on (seed,
@@ -355,25 +355,8 @@ __global__ void __launch_bounds__(AUX_TPB) k_dsa_init(Dev<T> g, const int32_t* i
 }
 
 // ---- the solution cost of every replica's current assignment: k_cost_partial / k_cost_final of replica_cost.h,
-// launched by replica_host.h (one implementation, shared with mgm.hip); BestRec: the best state a replica has
-// shown (mxs_dsa_track_best)
-using repcost::BestRec;
-
-// a launch of its own, after k_cost_final in stream order: the replicas that improved copy their state
-// and take the new record (nothing in this launch reads a record)
-__global__ void __launch_bounds__(AUX_TPB) k_dsa_best_copy(int n_vars, int bpr, const int32_t* cur, const double* cost,
-                                                           const long long* viol, long long cycle, BestRec best) {
-    const int r = (int)(blockIdx.x / (unsigned)bpr);
-    const int b = (int)blockIdx.x - r * bpr;
-    if (!best.improved[r]) return;
-    const int i = b * (int)blockDim.x + (int)threadIdx.x;
-    if (i < n_vars) best.idx[(int64_t)r * n_vars + i] = cur[(int64_t)r * n_vars + i];
-    if (i == 0) {
-        best.cost[r] = cost[r];
-        best.viol[r] = viol[r];
-        best.cycle[r] = cycle;
-    }
-}
+// launched by replica_host.h (one implementation, shared with mgm.hip), as is the snapshot of the best state a
+// replica has shown (mxs_dsa_track_best)
 
 struct Base {
     virtual ~Base() {}
@@ -408,13 +391,7 @@ struct Engine : Base {
     Buf<uint64_t> pk_key;   // what only DSA keeps per packed variable / lane (Dev::pack_key, pack_prob, pack_fopt)
     Buf<double> pk_prob;
     Buf<T> pk_fopt;
-    // the best state (track_best): `tracked`: track_best was called, `every` > 0: records are kept
-    bool tracked = false;
-    int32_t every = 0;
-    double best_infinity = INFINITY;
-    Buf<double> best_cost;
-    Buf<long long> best_viol, best_cycle;
-    Buf<int32_t> best_improved, best_idx;
+    rephost::BestTracker<T> bt;  // the best state every replica has shown (track_best, get_best)
 
     int init(const mxs_graph& G, const mxs_params& p, int variant, double probability, int arity_mode,
              const uint64_t* sds, int n_replicas, int dev) override {
@@ -495,22 +472,9 @@ struct Engine : Base {
             hipLaunchKernelGGL((k_dsa_init<T>), grid, block, 0, rh.stream, g, rh.iso_val.p, rh.iso_cost.p, cur[0].p, cur[1].p);
             MXS_TRY(hipGetLastError());
         }
-        const int rc = every > 0 ? record(2) : MXS_OK;
-        MXS_TRY(hipStreamSynchronize(rh.stream));  // (also when record() failed)
+        const int rc = bt.on_reset(rh, g, cur[which].p);
+        MXS_TRY(hipStreamSynchronize(rh.stream));  // (also when the record failed)
         return rc;
-    }
-
-    BestRec best_rec() const { return BestRec{best_cost.p, best_viol.p, best_cycle.p, best_improved.p, best_idx.p}; }
-
-    // the current states against the records (mode 1; 2: the first record), three launches in stream order
-    int record(int mode) {
-        if (int rc = rh.launch_costs(g, cur[which].p, best_infinity, mode, best_rec())) return rc;
-        const int bpr = std::max(1, blocks_of(g.n_vars, AUX_TPB));
-        hipLaunchKernelGGL(k_dsa_best_copy, dim3((unsigned)(bpr * n_rep)), dim3(AUX_TPB), 0, rh.stream, (int)g.n_vars, bpr,
-                           (const int32_t*)cur[which].p, (const double*)rh.rep_cost.p, (const long long*)rh.rep_viol.p,
-                           (long long)cycles, best_rec());
-        MXS_TRY(hipGetLastError());
-        return MXS_OK;
     }
 
     // the launches of one cycle of all replicas: packed plus rest, or thread per variable alone
@@ -552,8 +516,7 @@ struct Engine : Base {
             if (int rc = n_rep == 1 ? launch_cycle<false>(k.packed, k.generic) : launch_cycle<true>(k.packed, k.generic)) return rc;
             which ^= 1;
             cycles += 1;
-            if (every > 0 && cycles % every == 0)
-                if (int rc = record(1)) return rc;
+            if (int rc = bt.after_step(rh, g, cur[which].p, cycles)) return rc;
         }
         MXS_TRY(hipStreamSynchronize(rh.stream));
         return MXS_OK;
@@ -584,68 +547,13 @@ struct Engine : Base {
         return rh.replica_costs(g, cur[which].p, infinity, cst, viol);
     }
 
-    void drop_records() {
-        best_cost.release(), best_viol.release(), best_cycle.release(), best_improved.release(), best_idx.release();
-        every = 0;
-    }
-
     int track_best(int32_t ev, double infinity) override {
-        if (ev < 0) return fail(MXS_E_INVALID, "every must be 0 (off) or positive");
-        MXS_TRY(hipSetDevice(rh.device));
-        drop_records();
-        if (ev == 0) {
-            tracked = true;
-            best_infinity = infinity;
-            return MXS_OK;
-        }
-        const size_t R = (size_t)n_rep;
-        int rc = alloc_rep(best_cost, R, "records");
-        if (!rc) rc = alloc_rep(best_viol, R, "records");
-        if (!rc) rc = alloc_rep(best_cycle, R, "records");
-        if (!rc) rc = alloc_rep(best_improved, R, "records");
-        if (!rc) rc = alloc_rep(best_idx, R * g.n_vars, "best states");
-        if (rc) {  // no records, and get_best keeps what the last successful call set (tracked, best_infinity)
-            drop_records();
-            return rc;
-        }
-        tracked = true;
-        best_infinity = infinity;
-        every = ev;
-        if (int rc2 = record(2)) return rc2;  // the state as it is now: cycle 0 of a fresh engine
-        MXS_TRY(hipStreamSynchronize(rh.stream));
-        return MXS_OK;
+        return bt.track(rh, g, cur[which].p, cycles, ev, infinity);
     }
 
     int get_best(int32_t r, int32_t* replica, int64_t* cycle, double* cst, int64_t* viol, int32_t* idx) override {
-        if (r < -1 || r >= n_rep) return fail(MXS_E_INVALID, "replica out of range");
-        if (!tracked) return fail(MXS_E_STATE, "mxs_dsa_get_best before mxs_dsa_track_best");
-        MXS_TRY(hipSetDevice(rh.device));
-        std::vector<double> hc;
-        std::vector<long long> hv, hy(n_rep, (long long)cycles);
-        if (every > 0) {  // the records
-            if (int rc = rh.fetch_costs(hc, hv, best_cost.p, best_viol.p)) return rc;
-            MXS_TRY(hipMemcpyAsync(hy.data(), best_cycle.p, 8 * (size_t)n_rep, hipMemcpyDeviceToHost, rh.stream));
-            MXS_TRY(hipStreamSynchronize(rh.stream));
-        } else {          // the current states
-            if (int rc = rh.current_costs(g, cur[which].p, best_infinity, hc, hv)) return rc;
-        }
-        if (r < 0) r = repcost::best_replica(n_rep, g.is_max, hc.data(), hv.data());
-        if (replica) *replica = r;
-        if (cycle) *cycle = (int64_t)hy[r];
-        if (cst) *cst = hc[r];
-        if (viol) *viol = (int64_t)hv[r];
-        if (idx && g.n_vars) {
-            if (every > 0) {
-                std::vector<int32_t> hi(g.n_vars);
-                MXS_TRY(hipMemcpyAsync(hi.data(), best_idx.p + (size_t)r * g.n_vars, 4 * (size_t)g.n_vars,
-                                       hipMemcpyDeviceToHost, rh.stream));
-                MXS_TRY(hipStreamSynchronize(rh.stream));
-                rh.unpack(hi, idx);
-            } else if (int rc = get_state(r, idx, nullptr)) {
-                return rc;
-            }
-        }
-        return MXS_OK;
+        return bt.get(rh, g, cur[which].p, cycles, r, replica, cycle, cst, viol, idx,
+                      [&](int32_t rep, int32_t* out) { return get_state(rep, out, nullptr); }, "mxs_dsa");
     }
 };
 

@@ -29,8 +29,8 @@
 // the state is [R][n_vars] in GRAPH order, viol / slot_vc [R][n_slots], the modifier pool [R][plan.entries] (mod_off
 // stays per slot).  The start state is drawn on the device (k_gdbar_init).  A GDBA run is not monotone -- the breakout
 // makes the assignment wander -- so the best state every replica has shown is kept on the device: the solution costs
-// are reduced by replica_cost.h's kernels, k_gdbar_best_copy takes the snapshot; the refusals, the allocations that
-// grow with R and the cost launches are replica_host.h's.
+// are reduced by replica_cost.h's kernels and its k_best_copy takes the snapshot; the refusals, the allocations that
+// grow with R, the cost launches and the records of the best state (rephost::BestTracker) are replica_host.h's.
 #pragma once
 
 namespace gdba {
@@ -323,24 +323,6 @@ __global__ void __launch_bounds__(AUX_TPB) k_gdbar_init(DevR<T> g, const int32_t
     g.rec[v] = r;
 }
 
-// the best state a replica has shown (mxs_gdba_track_best): a launch of its own, after k_cost_final in stream order.
-// The replicas that improved copy their state (graph order, as stored) and take the new record; nothing in this
-// launch reads a record.
-using repcost::BestRec;
-__global__ void __launch_bounds__(AUX_TPB) k_gdbar_best_copy(int n_vars, int bpr, const int32_t* cur, const double* cost,
-                                                             const long long* viol, long long round, BestRec best) {
-    const int r = (int)(blockIdx.x / (unsigned)bpr);
-    const int b = (int)blockIdx.x - r * bpr;
-    if (!best.improved[r]) return;
-    const int i = b * (int)blockDim.x + (int)threadIdx.x;
-    if (i < n_vars) best.idx[(int64_t)r * n_vars + i] = cur[(int64_t)r * n_vars + i];
-    if (i == 0) {
-        best.cost[r] = cost[r];
-        best.viol[r] = viol[r];
-        best.cycle[r] = round;
-    }
-}
-
 // The host plan of the modifier pool: which slots are live, where their counters start, how many there are
 struct Plan {
     std::vector<int64_t> mod_off, size;  // per slot: offset (-1: none) and number of counters
@@ -491,13 +473,7 @@ struct Engine : Base {
     Buf<counter_t> pool;
     Buf<uint8_t> has_cost, viol;
     Buf<Rec<T>> rec;
-    // the best state (track_best): `tracked`: track_best was called, `every` > 0: records are kept
-    bool tracked = false;
-    int32_t every = 0;
-    double best_infinity = INFINITY;
-    Buf<double> best_cost;
-    Buf<long long> best_viol, best_round;
-    Buf<int32_t> best_improved, best_idx;
+    rephost::BestTracker<T> bt;       // the best state every replica has shown (track_best, get_best)
 
     int init(const mxs_graph& G, const mxs_params& p, const int32_t* rk, const int32_t* vrk, int32_t modifier,
              int32_t violation, int32_t increase_mode, const uint64_t* sds, int32_t n_replicas, bool one_run,
@@ -584,22 +560,9 @@ struct Engine : Base {
         }
         if (plan.entries) MXS_TRY(hipMemsetAsync(pool.p, 0, sizeof(counter_t) * R * (size_t)plan.entries, stream));
         if (n_slots) MXS_TRY(hipMemsetAsync(viol.p, 0, R * n_slots, stream));
-        const int rc = every > 0 ? record(2) : MXS_OK;
-        MXS_TRY(hipStreamSynchronize(stream));  // (also when record() failed)
+        const int rc = bt.on_reset(rh, g, cur.p);
+        MXS_TRY(hipStreamSynchronize(stream));  // (also when the record failed)
         return rc;
-    }
-
-    BestRec best_rec() const { return BestRec{best_cost.p, best_viol.p, best_round.p, best_improved.p, best_idx.p}; }
-
-    // the current states against the records (mode 1; 2: the first record), three launches in stream order
-    int record(int mode) {
-        if (int rc = rh.launch_costs(g, cur.p, best_infinity, mode, best_rec())) return rc;
-        const int bpr = std::max(1, rephost::blocks_of(g.n_vars, AUX_TPB));
-        hipLaunchKernelGGL(k_gdbar_best_copy, dim3((unsigned)(bpr * n_rep)), dim3(AUX_TPB), 0, rh.stream, (int)g.n_vars, bpr,
-                           (const int32_t*)cur.p, (const double*)rh.rep_cost.p, (const long long*)rh.rep_viol.p,
-                           (long long)rounds, best_rec());
-        MXS_TRY(hipGetLastError());
-        return MXS_OK;
     }
 
     int run(int32_t n) override {
@@ -617,7 +580,7 @@ struct Engine : Base {
         const Dev<T>& one = g;  // what a single run's launches copy: the Dev part
         for (int32_t r = 0; r < n; ++r) {
             g.round = rounds + 1;
-            g.bpr = vbpr;  // (a kernel takes its argument by value: the copy is made at the launch; record() sets its own)
+            g.bpr = vbpr;  // (a kernel takes its argument by value: the copy is made at the launch; the record sets its own)
             if (single) {
                 hipLaunchKernelGGL((k_gdba_eval<T>), grid, block, 0, stream, one);
                 MXS_TRY(hipGetLastError());
@@ -630,8 +593,7 @@ struct Engine : Base {
                 MXS_TRY(hipGetLastError());
             }
             rounds += 1;
-            if (every > 0 && rounds % every == 0)
-                if (int rc = record(1)) return rc;
+            if (int rc = bt.after_step(rh, g, cur.p, rounds)) return rc;
         }
         MXS_TRY(hipStreamSynchronize(stream));
         return MXS_OK;
@@ -692,69 +654,17 @@ struct Engine : Base {
         return rh.replica_costs(g, cur.p, infinity, cst, viol_out);
     }
 
-    void drop_records() {
-        best_cost.release(), best_viol.release(), best_round.release(), best_improved.release(), best_idx.release();
-        every = 0;
-    }
-
     // (the best state is kept for mxs_gdba_create_replicas, one replica included)
     int track_best(int32_t ev, double infinity) override {
         if (single) return fail(MXS_E_STATE, "gdba: the best state is tracked by the replica engine");
-        if (ev < 0) return fail(MXS_E_INVALID, "every must be 0 (off) or positive");
-        MXS_TRY(hipSetDevice(rh.device));
-        drop_records();
-        if (ev == 0) {
-            tracked = true;
-            best_infinity = infinity;
-            return MXS_OK;
-        }
-        const size_t R = (size_t)n_rep;
-        int rc = rephost::alloc_rep(best_cost, R, "records");
-        if (!rc) rc = rephost::alloc_rep(best_viol, R, "records");
-        if (!rc) rc = rephost::alloc_rep(best_round, R, "records");
-        if (!rc) rc = rephost::alloc_rep(best_improved, R, "records");
-        if (!rc) rc = rephost::alloc_rep(best_idx, R * g.n_vars, "best states");
-        if (rc) {  // no records, and get_best keeps what the last successful call set (tracked, best_infinity)
-            drop_records();
-            return rc;
-        }
-        tracked = true;
-        best_infinity = infinity;
-        every = ev;
-        if (int rc2 = record(2)) return rc2;  // the state as it is now: round 0 of a fresh engine
-        MXS_TRY(hipStreamSynchronize(rh.stream));
-        return MXS_OK;
+        return bt.track(rh, g, cur.p, rounds, ev, infinity);
     }
 
     int get_best(int32_t r, int32_t* replica, int64_t* round, double* cst, int64_t* viol_out, int32_t* idx) override {
-        // (a single run is never tracked -- track_best refuses it -- and answers so whatever r)
-        if (!single && (r < -1 || r >= n_rep)) return fail(MXS_E_INVALID, "replica out of range");
-        if (!tracked) return fail(MXS_E_STATE, "mxs_gdba_get_best before mxs_gdba_track_best");
-        MXS_TRY(hipSetDevice(rh.device));
-        std::vector<double> hc;
-        std::vector<long long> hv, hy(n_rep, (long long)rounds);
-        if (every > 0) {  // the records
-            if (int rc = rh.fetch_costs(hc, hv, best_cost.p, best_viol.p)) return rc;
-            MXS_TRY(hipMemcpyAsync(hy.data(), best_round.p, 8 * (size_t)n_rep, hipMemcpyDeviceToHost, rh.stream));
-            MXS_TRY(hipStreamSynchronize(rh.stream));
-        } else {          // the current states
-            if (int rc = rh.current_costs(g, cur.p, best_infinity, hc, hv)) return rc;
-        }
-        if (r < 0) r = repcost::best_replica(n_rep, g.is_max, hc.data(), hv.data());
-        if (replica) *replica = r;
-        if (round) *round = (int64_t)hy[r];
-        if (cst) *cst = hc[r];
-        if (viol_out) *viol_out = (int64_t)hv[r];
-        if (idx && g.n_vars) {
-            if (every > 0) {  // (graph order, as stored)
-                MXS_TRY(hipMemcpyAsync(idx, best_idx.p + (size_t)r * g.n_vars, 4 * (size_t)g.n_vars, hipMemcpyDeviceToHost,
-                                       rh.stream));
-                MXS_TRY(hipStreamSynchronize(rh.stream));
-            } else if (int rc = get_state(r, idx, nullptr, nullptr, nullptr, nullptr)) {
-                return rc;
-            }
-        }
-        return MXS_OK;
+        if (single) r = -1;  // (a single run is never tracked -- track_best refuses it -- and answers so whatever r)
+        return bt.get(rh, g, cur.p, rounds, r, replica, round, cst, viol_out, idx,
+                      [&](int32_t rep, int32_t* out) { return get_state(rep, out, nullptr, nullptr, nullptr, nullptr); },
+                      "mxs_gdba");
     }
 };
 

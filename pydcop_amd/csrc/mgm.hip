@@ -809,14 +809,7 @@ struct Engine : Base {
 
     // MGM's own sum never rises: a run's final state is its best, the final states are ranked
     int best_replica(double infinity, int32_t* replica, double* cst, int64_t* viol) override {
-        std::vector<double> hc;
-        std::vector<long long> hv;
-        if (int rc = rh.current_costs(g, cur[which].p, infinity, hc, hv)) return rc;
-        const int r = repcost::best_replica(n_rep, g.is_max, hc.data(), hv.data());
-        if (replica) *replica = r;
-        if (cst) *cst = hc[r];
-        if (viol) *viol = (int64_t)hv[r];
-        return MXS_OK;
+        return rh.best_current(g, cur[which].p, infinity, replica, cst, viol);
     }
 };
 

@@ -505,7 +505,7 @@ struct Base {
 // offer and offer_ok [R][n_entries]; the seeds are a device array.  The refusals, the allocations that grow with R
 // and the cost launches are rephost::Host's (replica_host.h, shared with dsa.hip and mgm.hip); MGM-2 keeps its
 // variables in graph order, so Host's q is the identity (graph_order).  MGM-2's sum stops improving at a local
-// optimum and is not tracked: the CURRENT states are ranked (repcost::best_replica).
+// optimum and is not tracked: the CURRENT states are ranked (Host::best_current).
 // `single` (mxs_mgm2_create): one replica under seeds = {seed} whose rounds are launched through the plain entry
 // points on the Dev base of g -- replica 0's slices are the buffers' bases.  It keeps the single run's API: its
 // replica cost, and the best replica's, is the host's eval_cost.
@@ -691,14 +691,7 @@ struct Engine : Base {
             if (replica) *replica = 0;
             return eval_cost(nullptr, infinity, cst, viol);
         }
-        std::vector<double> hc;
-        std::vector<long long> hv;
-        if (int rc = rh.current_costs(g, cur.p, infinity, hc, hv)) return rc;
-        const int r = repcost::best_replica(n_rep, g.is_max, hc.data(), hv.data());
-        if (replica) *replica = r;
-        if (cst) *cst = hc[r];
-        if (viol) *viol = (int64_t)hv[r];
-        return MXS_OK;
+        return rh.best_current(g, cur.p, infinity, replica, cst, viol);
     }
 };
 

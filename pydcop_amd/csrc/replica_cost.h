@@ -1,8 +1,10 @@
 // replica_cost.h -- the DEVICE side of what the engines that advance R seeded runs of one instance in one engine share
-// (dsa.hip, mgm.hip, mgm2.h; the host side, which launches these kernels, is replica_host.h): the fold of the replica into
-// blockIdx.x, and the solution cost of every replica's current assignment reduced on the device.  G is the engine's Dev: it carries n_vars, bpr (blocks per replica of the launch being made), the CSR arrays
+// (dsa.hip, mgm.hip, mgm2.h, gdba.h; the host side, which launches these kernels, is replica_host.h): the fold of the
+// replica into blockIdx.x, the solution cost of every replica's current assignment reduced on the device, and the
+// best state a replica has shown (BestRec, k_best_copy: the engines that track it, DSA and GDBA).  G is the engine's
+// Dev: it carries n_vars, bpr (blocks per replica of the launch being made), the CSR arrays
 // of the constraints (factor_rowptr, edge_var, dom_size, table_off, tables) and q (graph index -> position in the
-// dynamic state); the values are passed beside it, [replicas][n_vars] in packed order.
+// dynamic state); the values are passed beside it, [replicas][n_vars] in the engine's order (q).
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -90,11 +92,11 @@ __global__ void __launch_bounds__(COST_TPB) k_cost_partial(G g, CostArgs a) {
     }
 }
 
-// the best state a replica has shown (DSA's mxs_dsa_track_best): the record and the snapshot, in packed order
+// the best state a replica has shown (rephost::BestTracker): the record and the snapshot, in the order of the state
 struct BestRec {
     double* cost;          // [n_rep]
     long long* viol;
-    long long* cycle;
+    long long* cycle;      // the engine's cycle or round of the record
     int32_t* improved;     // [n_rep] written by k_cost_final, read by the copy kernel (the next launch)
     int32_t* idx;          // [n_rep][n_vars]
 };
@@ -122,6 +124,25 @@ __global__ void __launch_bounds__(64) k_cost_final(int n_rep, int n_blocks, int 
         const long long bv = best.viol[r];
         const double bc = best.cost[r];
         best.improved[r] = (hard < bv || (hard == bv && (is_max ? soft > bc : soft < bc))) ? 1 : 0;
+    }
+}
+
+// a launch of its own, after k_cost_final in stream order: the replicas that improved copy their state (as stored)
+// and take the new record; nothing in this launch reads a record.  Blocks of BEST_TPB threads, bpr per replica.
+// (A template for the same reason.)
+constexpr int BEST_TPB = 256;
+template <typename Rec>
+__global__ void __launch_bounds__(BEST_TPB) k_best_copy(int n_vars, int bpr, const int32_t* cur, const double* cost,
+                                                        const long long* viol, long long cycle, Rec best) {
+    const int r = (int)(blockIdx.x / (unsigned)bpr);
+    const int b = (int)blockIdx.x - r * bpr;
+    if (!best.improved[r]) return;
+    const int i = b * (int)blockDim.x + (int)threadIdx.x;
+    if (i < n_vars) best.idx[(int64_t)r * n_vars + i] = cur[(int64_t)r * n_vars + i];
+    if (i == 0) {
+        best.cost[r] = cost[r];
+        best.viol[r] = viol[r];
+        best.cycle[r] = cycle;
     }
 }
 

@@ -4,6 +4,11 @@
 // kernel-argument layout.  Every one of the four algorithms has ONE host engine on it, a single run being the case
 // R = 1.  An engine HOLDS a Host<T> and supplies its Dev (the kernels' argument), its per-lane extras (built from the
 // host views between build_views and upload_views), its init kernel (after start_values) and the launches of a cycle.
+// It takes from Host the device costs of the current states and their ranking (replica_costs, best_current: what
+// MGM's and MGM-2's best_replica is).  An engine whose runs are not monotone (DSA, GDBA) also HOLDS a BestTracker<T>:
+// the records of the best state every replica has shown, their allocation, the launches that compare and copy, and
+// get_best -- the engine calls it after reset, after every step and from track_best / get_best, passing its live
+// values and its step count, and keeps only the refusals that are its own.
 // MGM-2 and GDBA bring their own view and keep their state in graph order: they take open, graph_order /
 // upload_order in place of build_views / upload_views, upload_graph, alloc_rep and the cost launches, and bind their
 // DevR themselves; their mxs_*_create engine launches its one replica through the plain-Dev entry points.
@@ -12,6 +17,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <cmath>
 #include <cstdint>
 #include <cstdlib>
 #include <string>
@@ -28,6 +34,7 @@ using mxs_host::fail;
 // the block sizes of the launches that fold the replica into blockIdx.x (the engines assert theirs against these):
 // thread per variable, lane per (variable, constraint), init and copy kernels
 constexpr int VAR_TPB = 64, PACK_TPB = 256, AUX_TPB = 256;
+static_assert(AUX_TPB == repcost::BEST_TPB, "k_best_copy is launched with blocks of AUX_TPB threads");
 
 inline int blocks_of(int64_t n, int per_block) { return (int)((n + per_block - 1) / per_block); }
 
@@ -267,6 +274,127 @@ struct Host {
         for (int r = 0; r < n_rep; ++r) {
             if (cst) cst[r] = hc[r];
             if (viol) viol[r] = (int64_t)hv[r];
+        }
+        return MXS_OK;
+    }
+
+    // the CURRENT states ranked (repcost::best_replica): the best replica, its cost and its violations
+    template <typename G>
+    int best_current(G& g, const int32_t* cur, double infinity, int32_t* replica, double* cst, int64_t* viol) {
+        std::vector<double> hc;
+        std::vector<long long> hv;
+        if (int rc = current_costs(g, cur, infinity, hc, hv)) return rc;
+        const int r = repcost::best_replica(n_rep, g.is_max, hc.data(), hv.data());
+        if (replica) *replica = r;
+        if (cst) *cst = hc[r];
+        if (viol) *viol = (int64_t)hv[r];
+        return MXS_OK;
+    }
+};
+
+// The best state every replica has shown, kept on the device (mxs_dsa_track_best, mxs_gdba_track_best): what an engine
+// whose runs are not monotone holds beside its Host.  The engine passes what is its own with every call: rh, its Dev
+// g, the live values `cur` ([R][n_vars], in the order of rh.h_q) and `step`, its count of cycles or rounds.
+template <typename T>
+struct BestTracker {
+    bool tracked = false;  // track() was called
+    int32_t every = 0;     // > 0: records are kept
+    double best_infinity = INFINITY;
+    Buf<double> best_cost;
+    Buf<long long> best_viol, best_step;
+    Buf<int32_t> best_improved, best_idx;
+
+    repcost::BestRec rec() const {
+        return repcost::BestRec{best_cost.p, best_viol.p, best_step.p, best_improved.p, best_idx.p};
+    }
+
+    void drop() {
+        best_cost.release(), best_viol.release(), best_step.release(), best_improved.release(), best_idx.release();
+        every = 0;
+    }
+
+    // the current states against the records (mode 1; 2: the first record), three launches in stream order
+    template <typename G>
+    int record(Host<T>& rh, G& g, const int32_t* cur, int64_t step, int mode) {
+        if (int rc = rh.launch_costs(g, cur, best_infinity, mode, rec())) return rc;
+        const int bpr = std::max(1, blocks_of(g.n_vars, AUX_TPB));
+        hipLaunchKernelGGL((repcost::k_best_copy<repcost::BestRec>), dim3((unsigned)(bpr * rh.n_rep)), dim3(AUX_TPB), 0,
+                           rh.stream, (int)g.n_vars, bpr, cur, (const double*)rh.rep_cost.p,
+                           (const long long*)rh.rep_viol.p, (long long)step, rec());
+        MXS_TRY(hipGetLastError());
+        return MXS_OK;
+    }
+
+    // after the launches of step `step` (counted from 1)
+    template <typename G>
+    int after_step(Host<T>& rh, G& g, const int32_t* cur, int64_t step) {
+        return every > 0 && step % every == 0 ? record(rh, g, cur, step, 1) : MXS_OK;
+    }
+
+    // after the engine's init kernel: the records start again (the engine synchronises, also when this failed)
+    template <typename G>
+    int on_reset(Host<T>& rh, G& g, const int32_t* cur) {
+        return every > 0 ? record(rh, g, cur, 0, 2) : MXS_OK;
+    }
+
+    // ev > 0: a record per replica, compared after every ev-th step, the first one the state as it is now (step 0 of
+    // a fresh engine); ev == 0: none, get() ranks the current states under `infinity`.  Clears the records.
+    template <typename G>
+    int track(Host<T>& rh, G& g, const int32_t* cur, int64_t step, int32_t ev, double infinity) {
+        if (ev < 0) return fail(MXS_E_INVALID, "every must be 0 (off) or positive");
+        MXS_TRY(hipSetDevice(rh.device));
+        drop();
+        if (ev > 0) {
+            const size_t R = (size_t)rh.n_rep;
+            int rc = alloc_rep(best_cost, R, "records");
+            if (!rc) rc = alloc_rep(best_viol, R, "records");
+            if (!rc) rc = alloc_rep(best_step, R, "records");
+            if (!rc) rc = alloc_rep(best_improved, R, "records");
+            if (!rc) rc = alloc_rep(best_idx, R * g.n_vars, "best states");
+            if (rc) {  // no records, and get keeps what the last successful call set (tracked, best_infinity)
+                drop();
+                return rc;
+            }
+        }
+        tracked = true;
+        best_infinity = infinity;
+        every = ev;
+        if (ev == 0) return MXS_OK;
+        if (int rc = record(rh, g, cur, step, 2)) return rc;
+        MXS_TRY(hipStreamSynchronize(rh.stream));
+        return MXS_OK;
+    }
+
+    // the record of replica r (-1: of the best one) where records are kept, else its current state at `step`;
+    // current_idx_of(r, idx): the engine's get_state; prefix: the engine's, for the refusal ("mxs_dsa")
+    template <typename G, typename F>
+    int get(Host<T>& rh, G& g, const int32_t* cur, int64_t step, int32_t r, int32_t* replica, int64_t* step_out, double* cst,
+            int64_t* viol, int32_t* idx, F current_idx_of, const char* prefix) {
+        const int32_t n_rep = rh.n_rep;
+        if (r < -1 || r >= n_rep) return fail(MXS_E_INVALID, "replica out of range");
+        if (!tracked) return fail(MXS_E_STATE, std::string(prefix) + "_get_best before " + prefix + "_track_best");
+        MXS_TRY(hipSetDevice(rh.device));
+        std::vector<double> hc;
+        std::vector<long long> hv, hy(n_rep, (long long)step);
+        if (every > 0) {  // the records
+            if (int rc = rh.fetch_costs(hc, hv, best_cost.p, best_viol.p)) return rc;
+            MXS_TRY(hipMemcpyAsync(hy.data(), best_step.p, 8 * (size_t)n_rep, hipMemcpyDeviceToHost, rh.stream));
+            MXS_TRY(hipStreamSynchronize(rh.stream));
+        } else {          // the current states
+            if (int rc = rh.current_costs(g, cur, best_infinity, hc, hv)) return rc;
+        }
+        if (r < 0) r = repcost::best_replica(n_rep, g.is_max, hc.data(), hv.data());
+        if (replica) *replica = r;
+        if (step_out) *step_out = (int64_t)hy[r];
+        if (cst) *cst = hc[r];
+        if (viol) *viol = (int64_t)hv[r];
+        if (idx && g.n_vars) {
+            if (every == 0) return current_idx_of(r, idx);
+            std::vector<int32_t> hi(g.n_vars);
+            MXS_TRY(hipMemcpyAsync(hi.data(), best_idx.p + (size_t)r * g.n_vars, 4 * (size_t)g.n_vars, hipMemcpyDeviceToHost,
+                                   rh.stream));
+            MXS_TRY(hipStreamSynchronize(rh.stream));
+            rh.unpack(hi, idx);
         }
         return MXS_OK;
     }

@@ -59,13 +59,9 @@ class DsaEngine(ReplicaBinding):
     def track_best(self, every: int = 1, infinity: float = float("inf")):
         """Keep, per replica, the best state seen at cycle 0 and after every `every`-th cycle (0: off; the
         `infinity` then only serves `best()`).  Clears the records."""
-        self._call("track_best", int(every), float(infinity))
+        self._track_best(every, infinity)
 
     def best(self, replica: int = -1) -> Dict:
         """The record of `replica` (-1: of the best replica: fewest violations, then best cost, then lowest
         index) when tracking is on, else its current state: {"replica", "cycle", "cost", "violations", "idx"}."""
-        r, cyc, cost, viol = C.c_int32(0), C.c_int64(0), C.c_double(0), C.c_int64(0)
-        idx = np.empty(self.graph.n_vars, dtype=np.int32)
-        self._call("get_best", int(replica), C.byref(r), C.byref(cyc), C.byref(cost), C.byref(viol), idx.ctypes.data)
-        return {"replica": int(r.value), "cycle": int(cyc.value), "cost": float(cost.value),
-                "violations": int(viol.value), "idx": idx}
+        return self._best_record(replica)

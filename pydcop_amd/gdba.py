@@ -114,15 +114,11 @@ class GdbaEngine(ReplicaBinding):
         """Keep, per replica, the best state seen now and after every `every`-th round (0: off; the `infinity` then
         only serves `best()`).  Clears the records.  The replica engine's (`replicas` > 1, or `seeds`)."""
         self._need_replica_symbols("track_best needs them")
-        self._call("track_best", int(every), float(infinity))
+        self._track_best(every, infinity)
 
     def best(self, replica: int = -1) -> Dict:
         """The record of `replica` (-1: of the best replica: fewest violations, then best cost, then lowest
         index) when tracking is on, else its current state: {"replica", "cycle", "cost", "violations", "idx"},
         "cycle" the round of the record."""
         self._need_replica_symbols("best needs them")
-        r, cyc, cost, viol = C.c_int32(0), C.c_int64(0), C.c_double(0), C.c_int64(0)
-        idx = np.empty(self.graph.n_vars, dtype=np.int32)
-        self._call("get_best", int(replica), C.byref(r), C.byref(cyc), C.byref(cost), C.byref(viol), idx.ctypes.data)
-        return {"replica": int(r.value), "cycle": int(cyc.value), "cost": float(cost.value),
-                "violations": int(viol.value), "idx": idx}
+        return self._best_record(replica)

@@ -89,7 +89,4 @@ class MgmEngine(ReplicaBinding):
         """The best replica's current state -- fewest violations, then best cost, then lowest index, ranked on the
         device: {"replica", "cost", "violations", "idx"}."""
         self._keyed_only("best")
-        r, cost, viol = C.c_int32(0), C.c_double(0), C.c_int64(0)
-        self._call("best_replica", float(infinity), C.byref(r), C.byref(cost), C.byref(viol))
-        return {"replica": int(r.value), "cost": float(cost.value), "violations": int(viol.value),
-                "idx": self.state(int(r.value))["idx"]}
+        return self._best_ranked(infinity)

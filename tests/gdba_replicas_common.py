@@ -290,6 +290,38 @@ def test_best_state_records_equal_the_oracle_derived_ones(every, lib_path):
         np.testing.assert_array_equal(b["idx"], finals[b["replica"]][2])
 
 
+SPAN_SEEDS = [5, 6, 7, 8]
+SPAN_ROUNDS = 40
+SPAN_BLOCK = 256                            # the copy kernel's block: index >= 256 is its second block
+
+
+@pytest.mark.parametrize("every", [1, 4])
+def test_gdba_best_state_snapshots_span_blocks(every, lib_path):
+    """300 variables: two blocks of repcost::k_best_copy per replica, the smallest size with a second block.  M / NM /
+    T on the hard colouring (integer tables, no variable costs: every cost is exact), seeds 5..8, 40 rounds, infinity
+    1000.  Measured on the oracle: the records are of rounds 21 / 32 / 33 / 40 (every = 1) and 20 / 32 / 32 / 40
+    (every = 4); those of seeds 5 and 6 differ from the run's final state at 7 and 3 indices >= 256."""
+    g, params, inf = G.random_coloring(300, seed=32, variant="hard", unary_noise=0), Params(), 1000.0
+    records, finals = oracle_records(OracleGdba, g, params, BEST_KW, SPAN_SEEDS, SPAN_ROUNDS, every, inf)
+    # the oracle side: a snapshot that missed its second block (the final state left there) would be seen
+    beyond = [int((rec[3][SPAN_BLOCK:] != fin[2][SPAN_BLOCK:]).sum()) for rec, fin in zip(records, finals)]
+    assert sum(n > 0 for n in beyond) >= 2, f"every={every}: records differ from the final states past index 256 in {beyond}"
+    assert [rec[2] for rec in records] == {1: [21, 32, 33, 40], 4: [20, 32, 32, 40]}[every]
+    w = winner(records, False)
+    with GdbaEngine(g, params, seeds=SPAN_SEEDS, replicas=len(SPAN_SEEDS), lib_path=lib_path, **BEST_KW) as eng:
+        eng.track_best(every, inf)
+        for _ in range(2):
+            eng.run(SPAN_ROUNDS)
+            for r, (viol, cost, rnd, idx) in enumerate(records):
+                b = eng.best(r)
+                assert (b["replica"], b["violations"], b["cost"], b["cycle"]) == (r, viol, cost, rnd), (r, b, records[r][:3])
+                np.testing.assert_array_equal(b["idx"], idx, err_msg=f"snapshot of replica {r}")
+            b = eng.best()
+            assert (b["replica"], b["violations"], b["cost"], b["cycle"]) == (w,) + records[w][:3]
+            np.testing.assert_array_equal(b["idx"], records[w][3])
+            eng.reset()                     # the records start again: the same run gives the same records
+
+
 def test_device_costs_in_max_mode_with_float_tables(lib_path):
     """float tables and variable costs: the cost to rounding (check_costs), the ranking on the negated cost"""
     g = G.random_coloring(40, seed=33)

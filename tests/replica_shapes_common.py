@@ -165,7 +165,7 @@ def compare_shape(name, engine, lib_path):
         ora.close()
 
 
-# ---- the best state across blocks (DSA): 300 variables, two blocks of k_dsa_best_copy
+# ---- the best state across blocks (DSA): 300 variables, two blocks of repcost::k_best_copy
 
 def best_cases():
     soft = lambda: G.random_coloring(300, seed=31, unary_noise=0)                      # noqa: E731

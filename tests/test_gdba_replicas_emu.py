@@ -10,6 +10,7 @@ from gdba_replicas_common import (  # noqa: F401  (collected here)
     test_reference_fixtures,
     test_fixture_set_is_complete,
     test_best_state_records_equal_the_oracle_derived_ones,
+    test_gdba_best_state_snapshots_span_blocks,
     test_device_costs_in_max_mode_with_float_tables,
     test_refusals)
 

@@ -1,12 +1,13 @@
 """The replica kernels of GDBA (pydcop_amd/csrc/gdba.h: k_gdbar_*) use no scratch memory and come in exactly the
-expected instantiations -- f32 and f64 of the init, eval and decide kernels, one copy kernel: hipcc's
-kernel-resource-usage remarks for gfx950 (`make -C pydcop_amd/csrc resource-usage-mgm`), read here.  Compile only: no GPU."""
+expected instantiations -- f32 and f64 of the init, eval and decide kernels; the best-state copy kernel is the one
+repcost::k_best_copy of the unit: hipcc's kernel-resource-usage remarks for gfx950
+(`make -C pydcop_amd/csrc resource-usage-mgm`), read here.  Compile only: no GPU."""
 import os
 import re
 import subprocess
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-KERNELS = {"k_gdbar_init": 2, "k_gdbar_eval": 2, "k_gdbar_decide": 2, "k_gdbar_best_copy": 1}
+KERNELS = {"k_gdbar_init": 2, "k_gdbar_eval": 2, "k_gdbar_decide": 2}
 
 
 def test_gdba_replica_kernels_use_no_scratch():
@@ -26,6 +27,9 @@ def test_gdba_replica_kernels_use_no_scratch():
         assert sum(k in n for n in mine) == count, (k, sorted(mine))
     assert len(mine) == sum(KERNELS.values()), sorted(mine)
     assert all(s == 0 for s in mine.values()), mine
+    # the snapshot of the best state is replica_cost.h's copy kernel: one in the unit, none of GDBA's own
+    copy = [n for n in usage if "best_copy" in n]
+    assert len(copy) == 1 and "k_best_copy" in copy[0] and usage[copy[0]] == 0, copy
     # the single-run kernels are still there, on the plain argument
     assert sum("k_gdba_eval" in n or "k_gdba_decide" in n for n in usage) == 4
     # the cost reduction is replica_cost.h's, instantiated for GDBA's argument: no copy of it here
