@@ -721,13 +721,19 @@ int mxs_dba_get_weights(mxs_dba *e, int32_t *out /* [n_slots] */);
 int mxs_dba_mask_bytes(const mxs_dba *e, int64_t *bytes);
 int mxs_dba_eval_cost(mxs_dba *e, const int32_t *idx, double infinity, double *cost, int64_t *violations);
 int mxs_dba_destroy(mxs_dba *e);
+/* REPLICAS: n seeded runs of the instance in one engine under a stop policy (create_replicas, replicas,
+ * get_state_replica, get_weights_replica, stop_rounds), their violated constraints counted on the device and the
+ * ranking by them (replica_violations, best_replica) are declared and documented in maxsum_gpu_dba_replicas.h, in the
+ * style of the GDBA block above. */
+#include "maxsum_gpu_dba_replicas.h"
 
 /* Library/ABI version (major*100+minor).  270 also covers the MGM additions made after it was set -- mxs_mgm_create_keyed,
  * mxs_mgm_replicas, mxs_mgm_get_state_replica, mxs_mgm_replica_costs, mxs_mgm_best_replica -- and the MGM-2 additions
  * after those -- mxs_mgm2_create_replicas, mxs_mgm2_replicas, mxs_mgm2_get_state_replica, mxs_mgm2_replica_costs,
- * mxs_mgm2_best_replica -- and the GDBA additions of maxsum_gpu_gdba_replicas.h: a binding that needs them looks the
- * symbols up instead of comparing versions (pydcop_amd/mgm.py, pydcop_amd/mgm2.py and pydcop_amd/gdba.py do, and say so
- * when they are missing). */
+ * mxs_mgm2_best_replica -- and the GDBA additions of maxsum_gpu_gdba_replicas.h and the DBA additions of
+ * maxsum_gpu_dba_replicas.h: a binding that needs them looks the symbols up instead of comparing versions
+ * (pydcop_amd/mgm.py, pydcop_amd/mgm2.py, pydcop_amd/gdba.py and pydcop_amd/dba.py do, and say so when they are
+ * missing). */
 int32_t mxs_version(void);
 
 /* What this binary is: 1 = the product, compiled by hipcc for gfx950; 0 = the host

@@ -59,9 +59,12 @@ def _engine_for(graph: FlatGraph, params: Params, device: int, devices: int, lib
 
 
 def _algo_kw(algo, variant, probability, p_mode, seed, threshold, favor, modifier="A", violation="NZ",
-             increase_mode="E", dba_infinity=10000, max_distance=50, restarts=1, draws="fixed", best_every=0):
+             increase_mode="E", dba_infinity=10000, max_distance=50, restarts=1, draws="fixed", best_every=0,
+             dba_stop="first"):
     if algo == "dba":
-        return dict(infinity=dba_infinity, max_distance=max_distance, seed=seed)
+        kw = dict(infinity=dba_infinity, max_distance=max_distance, seed=seed)
+        # (one run: mxs_dba_create, as ever -- the two stop policies are the same thing there)
+        return dict(kw, replicas=int(restarts), stop=dba_stop) if int(restarts) != 1 else kw
     if algo == "gdba":
         kw = dict(modifier=modifier, violation=violation, increase_mode=increase_mode, seed=seed)
         if int(restarts) != 1 or int(best_every) != 0:      # (else one run: mxs_gdba_create, as ever)
@@ -92,7 +95,7 @@ def _run_and_trace(eng, algo: str, cycles: int, cost_every: int, infinity: float
     return curve
 
 
-def _check_restarts(algo, restarts, best_every, draws="fixed"):
+def _check_restarts(algo, restarts, best_every, draws="fixed", dba_stop="first"):
     if int(restarts) < 1 or int(best_every) < 0:
         raise ValueError("restarts must be at least 1 and best_every at least 0")
     if draws not in ("fixed", "keyed"):
@@ -100,10 +103,12 @@ def _check_restarts(algo, restarts, best_every, draws="fixed"):
     if draws != "fixed" and algo != "mgm":
         raise ValueError("draws: algo=\"mgm\" only (the other local searches always key their draws on `seed`)")
     # (a GDBA run's final state is usually not its best: restarts without records would rank wandering states)
-    if int(restarts) != 1 and not (algo in ("dsa", "mgm2") or (algo == "mgm" and draws == "keyed")
+    if int(restarts) != 1 and not (algo in ("dsa", "mgm2", "dba") or (algo == "mgm" and draws == "keyed")
                                    or (algo == "gdba" and int(best_every) >= 1)):
-        raise ValueError("restarts: algo=\"dsa\" or \"mgm2\", algo=\"mgm\" with draws=\"keyed\", or algo=\"gdba\" with "
-                         "best_every >= 1")
+        raise ValueError("restarts: algo=\"dsa\", \"mgm2\" or \"dba\", algo=\"mgm\" with draws=\"keyed\", or algo=\"gdba\" "
+                         "with best_every >= 1")
+    if dba_stop not in ("first", "each"):
+        raise ValueError("dba_stop must be \"first\" or \"each\"")
     if algo not in ("dsa", "gdba") and int(best_every) != 0:
         raise ValueError("best_every: algo=\"dsa\" or \"gdba\" only")
 
@@ -131,6 +136,16 @@ def _mgm_best(eng, algo, restarts, infinity):
     return best["idx"], {"replica": best["replica"], "replica_costs": [float(c) for c in costs]}
 
 
+def _dba_best(eng, algo, restarts):
+    """algo="dba" with restarts: (idx of the best replica's state -- fewest violated constraints, then earliest stop,
+    ranked from the device's counts --, the result's extra keys).  Else None."""
+    if algo != "dba" or int(restarts) == 1:
+        return None
+    best = eng.best()
+    return best["idx"], {"replica": best["replica"], "replica_violations": [int(v) for v in eng.violations()],
+                         "stop_rounds": eng.stop_rounds}
+
+
 def _dba_end(eng, algo):
     """DBA stops by itself: the rounds it ran and whether a termination counter reached max_distance"""
     return {"cycle": eng.cycle_count, "finished": eng.finished} if algo == "dba" else {}
@@ -155,7 +170,7 @@ def solve_dcop(dcop, cycles: int = 30, *, damping: float = 0.5, damping_nodes: s
                variant: str = "B", probability: float = 0.7, p_mode: str = "fixed", threshold: float = 0.5,
                favor: str = "unilateral", modifier: str = "A", violation: str = "NZ", increase_mode: str = "E",
                dba_infinity: int = 10000, max_distance: int = 50, restarts: int = 1, best_every: int = 0,
-               draws: str = "fixed") -> Dict:
+               draws: str = "fixed", dba_stop: str = "first") -> Dict:
     """Synchronous Max-Sum for exactly `cycles` cycles; parameters and defaults are those
     of `pydcop.algorithms.maxsum` (maxsum.py:212-220), `infinity` that of
     `pydcop.infrastructure.run.solve` (run.py:49).  `algo`: "amaxsum" (`cycles` = generations of
@@ -192,20 +207,29 @@ def solve_dcop(dcop, cycles: int = 30, *, damping: float = 0.5, damping_nodes: s
     algo="gdba": `best_every` = k > 0 and `restarts` as for DSA, rounds in place of cycles: the assignment is the best
     record of the best run and the result gains "replica", "best_cycle" and "replica_costs".  A GDBA run is not
     monotone (the breakout makes the assignment wander, its final state is usually not its best), so `restarts` > 1
-    requires `best_every` >= 1."""
-    _check_restarts(algo, restarts, best_every, draws)
+    requires `best_every` >= 1.
+
+    algo="dba": `restarts` = R seeded runs (seeds seed .. seed + R - 1) in one engine.  DBA's outcome depends entirely
+    on its start draw and tie draws, and a stop does not imply a solution, so the assignment is that of the run with
+    the fewest violated constraints (entries >= dba_infinity, counted on the device; then the earliest stop, then the
+    lowest index).  `dba_stop` = "first" (the default): the engine ends with the round in which the first run stops,
+    every run having completed it; "each": a run that stops is frozen, the others run on for `cycles` rounds or until
+    all have stopped.  The result gains "replica", "replica_violations" and "stop_rounds" (0: that run has not
+    stopped); "cycle" is the rounds the engine ran, "finished" whether it has ended.  `best_every` stays refused."""
+    _check_restarts(algo, restarts, best_every, draws, dba_stop)
     graph = compile_dcop(dcop, noise=noise if algo in ("maxsum", "amaxsum") else 0.0, seed=seed)
     params = Params(mode=dcop.objective, damping=damping, damping_nodes=damping_nodes,
                     stability=stability, start_messages=start_messages, dtype=precision)
     algo_kw = _algo_kw(algo, variant, probability, p_mode, seed, threshold, favor, modifier, violation, increase_mode,
-                       dba_infinity, max_distance, restarts, draws, best_every)
+                       dba_infinity, max_distance, restarts, draws, best_every, dba_stop)
     with _engine_for(graph, params, device, devices, lib_path, algo, algo_kw) as eng:
         if algo in ("dsa", "gdba") and int(best_every) > 0:
             eng.track_best(int(best_every), infinity)
         curve = _run_and_trace(eng, algo, cycles, cost_every, infinity)
         idx, _ = eng.assignment()
         extra = _dba_end(eng, algo)
-        best = _dsa_best(eng, algo, restarts, best_every, infinity) or _mgm_best(eng, algo, restarts, infinity)
+        best = (_dsa_best(eng, algo, restarts, best_every, infinity) or _mgm_best(eng, algo, restarts, infinity)
+                or _dba_best(eng, algo, restarts))
         if best:
             idx, more = best
             extra.update(more)
@@ -222,23 +246,24 @@ def solve_flat(graph: FlatGraph, objective: str = "min", cycles: int = 30, *, da
                probability: float = 0.7, p_mode: str = "fixed", seed: int = 0, threshold: float = 0.5,
                favor: str = "unilateral", modifier: str = "A", violation: str = "NZ", increase_mode: str = "E",
                dba_infinity: int = 10000, max_distance: int = 50, restarts: int = 1, best_every: int = 0,
-               draws: str = "fixed") -> Dict:
+               draws: str = "fixed", dba_stop: str = "first") -> Dict:
     """`solve_dcop` for an already compiled instance (`FlatGraph`, e.g. loaded from the
     .npz instance format): no pyDCOP import at all.  Cost and violations come from the
     device (`mxs_eval_cost` = DCOP.solution_cost, pydcop/dcop/dcop.py:308-367); noise, if
     wanted, is already folded into `graph.var_cost` by whoever compiled the instance."""
     params = Params(mode=objective, damping=damping, damping_nodes=damping_nodes,
                     stability=stability, start_messages=start_messages, dtype=precision)
-    _check_restarts(algo, restarts, best_every, draws)
+    _check_restarts(algo, restarts, best_every, draws, dba_stop)
     algo_kw = _algo_kw(algo, variant, probability, p_mode, seed, threshold, favor, modifier, violation, increase_mode,
-                       dba_infinity, max_distance, restarts, draws, best_every)
+                       dba_infinity, max_distance, restarts, draws, best_every, dba_stop)
     with _engine_for(graph, params, device, devices, lib_path, algo, algo_kw) as eng:
         if algo in ("dsa", "gdba") and int(best_every) > 0:
             eng.track_best(int(best_every), infinity)
         curve = _run_and_trace(eng, algo, cycles, cost_every, infinity)
         idx, _ = eng.assignment()
         extra = _dba_end(eng, algo)
-        best = _dsa_best(eng, algo, restarts, best_every, infinity) or _mgm_best(eng, algo, restarts, infinity)
+        best = (_dsa_best(eng, algo, restarts, best_every, infinity) or _mgm_best(eng, algo, restarts, infinity)
+                or _dba_best(eng, algo, restarts))
         if best:
             idx, more = best
             extra.update(more)
@@ -323,7 +348,7 @@ def main(argv=None):
              "damping_nodes": str, "start_messages": str, "precision": str, "devices": int,
              "variant": str, "probability": float, "p_mode": str, "threshold": float, "favor": str,
              "modifier": str, "violation": str, "increase_mode": str, "infinity": int, "max_distance": int,
-             "restarts": int, "best_every": int, "draws": str}
+             "restarts": int, "best_every": int, "draws": str, "dba_stop": str}
     kw = {}
     for item in args.algo_params:
         name, _, value = item.partition(":")
@@ -368,7 +393,7 @@ def main(argv=None):
            "msg_count": 0, "msg_size": 0, "agt_metrics": {}}
     if res["cost_curve"]:
         out["cost_curve"] = res["cost_curve"]
-    for key in ("replica", "best_cycle", "replica_costs"):      # (-p restarts / best_every)
+    for key in ("replica", "best_cycle", "replica_costs", "replica_violations", "stop_rounds"):  # (-p restarts / best_every)
         if key in res:
             out[key] = res[key]
     print(json.dumps(out, sort_keys=True, indent="  "))

@@ -21,6 +21,20 @@
 // The run ends with the first round in which any variable's stop condition holds: a stopper stores the round
 // number into one device word (all stoppers of a round store the same value), both kernels return at once when
 // that word holds an earlier round.  run(n) queues 2 n launches and reads the word back once.
+//
+// REPLICAS (mxs_dba_create_replicas): R seeded runs advance with the same two launches, as in gdba.h.  The phases
+// are __device__ bodies (eval_phase, eval_wide_phase, decide_phase; REP = false / true) with two sets of __global__
+// entry points and ONE host engine: k_dba_* on the plain Dev -- what an engine of mxs_dba_create launches for its one
+// replica, argument layout and grid as a single run has always had them -- and k_dbar_* on DevR, where the replica is
+// folded into blockIdx.x (block = r * bpr + b, replica_cost.h) and the block's copy of the argument moves once to
+// replica r's slices of the dynamic state and takes seeds[r] (enter_replica).  The bit rows, their offsets and
+// strides, the slot view, the domains, has_nb and the ranks are stored once; cur, cost, has_cost, counter, flags, rec
+// are [R][n_vars], weight and viol [R][n_slots], stop and error [R].  A stopper stores the round into stop[r]; under
+// the stop policy `first` it also stores it into one engine-wide word, and every replica's lanes return once that
+// word holds an earlier round: every replica completes the round in which the first one stops.  Plain stores, no
+// atomics: all stoppers of a round store the same value.  The constraints violated under every replica's assignment
+// (DBA's rule: the bit of the row, i.e. entry >= infinity) are counted on the device: k_dbar_viol_partial /
+// k_dbar_viol_final, in the fixed shape of replica_cost.h's cost reduction.
 #pragma once
 
 namespace dba {
@@ -65,6 +79,43 @@ struct Dev {
     int32_t* error;           // sticky: improve > 0 with no best value (the reference raises IndexError, :412)
 };
 
+// what the replica engine's kernels take: Dev plus the replicas.  The single-run kernels keep the plain Dev, i.e.
+// their argument layout.  The per-replica arrays of Dev -- cur, cost, has_cost, counter, flags, rec -- are
+// [replicas][n_vars], weight and viol [replicas][n_slots], stop and error [replicas]; `seed` is filled per block from
+// seeds[r] (enter_replica).
+struct DevR : Dev {
+    int32_t bpr;            // blocks per replica of the launch being made (block = replica * bpr + b)
+    int32_t n_rep;
+    int32_t stop_first;     // stop policy `first`: a stopper also stores the round into *first
+    int64_t n_slots;        // a replica's share of weight / viol
+    const uint64_t* seeds;  // [replicas]
+    int32_t* first;         // the engine-wide word: 0, or the round in which the first replica stopped (policy `first`)
+};
+
+// the replica of this block: the block's copy of DevR (kernel arguments, block-uniform) moves to the replica's slices
+// of the dynamic state and takes its seed, so that nothing below knows about replicas
+__device__ inline int enter_replica(DevR& g, int* b) {
+    const int r = repcost::replica_of_block<true>(g, b);
+    const int64_t off = (int64_t)r * g.n_vars, soff = (int64_t)r * g.n_slots;
+    g.cur += off, g.cost += off, g.has_cost += off, g.counter += off, g.flags += off, g.rec += off;
+    g.weight += soff, g.viol += soff;
+    g.stop += r, g.error += r;
+    g.seed = g.seeds[r];
+    return r;
+}
+
+// nothing of a run runs after the round of its stop; REP: nor after the round in which the first replica stopped
+template <bool REP, typename G>
+__device__ inline bool ended(const G& g) {
+    const int32_t stopped = *g.stop;
+    if (stopped != 0 && stopped < g.round) return true;
+    if constexpr (REP) {
+        const int32_t first = *g.first;
+        if (first != 0 && first < g.round) return true;
+    }
+    return false;
+}
+
 // the slot's row for the neighbours' current values: the index of its first word
 __device__ inline int64_t row_of(const Dev& g, int s, int words) {
     int64_t r = 0;
@@ -104,11 +155,9 @@ __device__ inline void finish_eval(const Dev& g, int v, int cv, int32_t cost, co
 }
 
 // domains of at most MAXD <= 32 values: one word per row, the evaluations of all values in registers
-template <int MAXD>
-__global__ void __launch_bounds__(TPB) k_dba_eval(Dev g) {
-    const int v = blockIdx.x * blockDim.x + threadIdx.x;
-    const int32_t stopped = *g.stop;
-    if (stopped != 0 && stopped < g.round) return;
+template <bool REP, int MAXD, typename G>
+__device__ inline void eval_phase(const G& g, int v) {
+    if (ended<REP>(g)) return;
     if (v >= g.n_vars || !g.has_nb[v]) return;
     const int D = g.dom[v], cv = g.cur[v];
     int32_t acc[MAXD];
@@ -162,10 +211,9 @@ __device__ inline int32_t eval_at(const Dev& g, int v, int x, int words, bool ma
     return acc;
 }
 
-__global__ void __launch_bounds__(TPB) k_dba_eval_wide(Dev g) {
-    const int v = blockIdx.x * blockDim.x + threadIdx.x;
-    const int32_t stopped = *g.stop;
-    if (stopped != 0 && stopped < g.round) return;
+template <bool REP, typename G>
+__device__ inline void eval_wide_phase(const G& g, int v) {
+    if (ended<REP>(g)) return;
     if (v >= g.n_vars || !g.has_nb[v]) return;
     const int D = g.dom[v], cv = g.cur[v], words = (D + 31) / 32;
     const int32_t cost = eval_at(g, v, cv, words, true);
@@ -183,10 +231,9 @@ __global__ void __launch_bounds__(TPB) k_dba_eval_wide(Dev g) {
     finish_eval(g, v, cv, cost, b, newv);
 }
 
-__global__ void __launch_bounds__(TPB) k_dba_decide(Dev g) {
-    const int v = blockIdx.x * blockDim.x + threadIdx.x;
-    const int32_t stopped = *g.stop;
-    if (stopped != 0 && stopped < g.round) return;
+template <bool REP, typename G>
+__device__ inline void decide_phase(const G& g, int v) {
+    if (ended<REP>(g)) return;
     if (v >= g.n_vars || !g.has_nb[v]) return;
     const Rec me = g.rec[v];
     // what improve() left (:402-415)
@@ -217,6 +264,9 @@ __global__ void __launch_bounds__(TPB) k_dba_decide(Dev g) {
     g.flags[v] = (uint8_t)((consistent ? F_CONSISTENT : 0) | (can_move ? F_CAN_MOVE : 0) | (qlm ? F_QLM : 0));
     if (stop) {
         *g.stop = g.round;
+        if constexpr (REP) {
+            if (g.stop_first) *g.first = g.round;
+        }
         return;
     }
     if (qlm)
@@ -226,6 +276,108 @@ __global__ void __launch_bounds__(TPB) k_dba_decide(Dev g) {
         g.cur[v] = me.newv;
         g.cost[v] = me.eval - me.improve;
     }
+}
+
+// ---- the entry points.  The single-run kernels: the plain Dev, the thread's index from blockIdx.x alone -- what
+// mxs_dba_create has always launched.
+template <int MAXD>
+__global__ void __launch_bounds__(TPB) k_dba_eval(Dev g) {
+    const int v = blockIdx.x * blockDim.x + threadIdx.x;
+    eval_phase<false, MAXD>(g, v);
+}
+__global__ void __launch_bounds__(TPB) k_dba_eval_wide(Dev g) {
+    const int v = blockIdx.x * blockDim.x + threadIdx.x;
+    eval_wide_phase<false>(g, v);
+}
+__global__ void __launch_bounds__(TPB) k_dba_decide(Dev g) {
+    const int v = blockIdx.x * blockDim.x + threadIdx.x;
+    decide_phase<false>(g, v);
+}
+
+// The replica kernels (mxs_dba_create_replicas): R runs per launch, whole blocks (one wave each) belong to one
+// replica (block = r * bpr + b); below enter_replica the phase code is the single run's, but for the engine-wide word.
+template <int MAXD>
+__global__ void __launch_bounds__(TPB) k_dbar_eval(DevR g) {
+    int b;
+    enter_replica(g, &b);
+    eval_phase<true, MAXD>(g, b * (int)blockDim.x + (int)threadIdx.x);
+}
+__global__ void __launch_bounds__(TPB) k_dbar_eval_wide(DevR g) {
+    int b;
+    enter_replica(g, &b);
+    eval_wide_phase<true>(g, b * (int)blockDim.x + (int)threadIdx.x);
+}
+__global__ void __launch_bounds__(TPB) k_dbar_decide(DevR g) {
+    int b;
+    enter_replica(g, &b);
+    decide_phase<true>(g, b * (int)blockDim.x + (int)threadIdx.x);
+}
+
+// the start state of every replica (on_start, :341-349), thread per (replica, index): random.choice(domain) for every
+// variable -- draw D_START of cycle 0 under seeds[r]; initial values are not looked at --, cost None, no new value;
+// every weight 1
+constexpr int AUX_TPB = rephost::AUX_TPB;
+__global__ void __launch_bounds__(AUX_TPB) k_dbar_init(DevR g) {
+    int b;
+    enter_replica(g, &b);
+    const int64_t i = (int64_t)b * (int)blockDim.x + (int)threadIdx.x;
+    if (i < g.n_vars) {
+        const int v = (int)i;
+        g.cur[v] = (int)(uniform(g.seed, v, 0, D_START) * g.dom[v]);
+        g.cost[v] = 0;
+        g.has_cost[v] = 0;
+        g.counter[v] = 0;
+        g.flags[v] = 0;
+        g.rec[v] = Rec{0, 0, 0, -1};
+    }
+    if (i < g.n_slots) {
+        g.weight[i] = 1;
+        g.viol[i] = 0;
+    }
+}
+
+// ---- the constraints violated under every replica's current assignment, DBA's rule: the entry is >= infinity,
+// compared as Plan::fill compares it (NaN: not violated) -- the bit of the row, read through one slot of a playing
+// scope variable (ref_slot / ref_var; -1: no variable of the scope plays, the constraint is in `base`).  FIXED
+// SHAPE, as repcost::k_cost_partial / k_cost_final: a thread folds VIOL_RUN consecutive constraints, the block's
+// VIOL_TPB counts are combined by one tree in LDS, the block's partial goes to part[r][b]; k_dbar_viol_final adds a
+// replica's partials in index order to base[r].  No atomics.
+constexpr int VIOL_TPB = 256, VIOL_RUN = 4;
+struct ViolArgs {
+    const int32_t *ref_slot, *ref_var;  // [n_factors]
+    int32_t n_factors;
+    long long* part;                    // [n_rep][bpr]
+};
+__global__ void __launch_bounds__(VIOL_TPB) k_dbar_viol_partial(DevR g, ViolArgs a) {
+    __shared__ long long s_viol[VIOL_TPB];
+    int b;
+    const int r = enter_replica(g, &b);
+    const int t = (int)threadIdx.x;
+    const int64_t i0 = ((int64_t)b * VIOL_TPB + t) * VIOL_RUN;
+    long long n = 0;
+    for (int64_t i = i0; i < i0 + VIOL_RUN && i < a.n_factors; ++i) {
+        const int s = a.ref_slot[i];
+        if (s < 0) continue;
+        const int v = a.ref_var[i], x = g.cur[v];
+        n += (g.masks[row_of(g, s, (g.dom[v] + 31) / 32) + (x >> 5)] >> (x & 31)) & 1u;
+    }
+    s_viol[t] = n;
+    __syncthreads();
+    for (int s = VIOL_TPB / 2; s > 0; s >>= 1) {
+        if (t < s) s_viol[t] += s_viol[t + s];
+        __syncthreads();
+    }
+    if (t == 0) a.part[(int64_t)r * g.bpr + b] = s_viol[0];
+}
+// thread per replica: base[r] (the constraints of variables that never play, constant after reset) plus the partials
+// in index order
+__global__ void __launch_bounds__(64) k_dbar_viol_final(int n_rep, int n_blocks, const long long* part,
+                                                        const long long* base, long long* viol) {
+    const int r = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+    if (r >= n_rep) return;
+    long long n = base[r];
+    for (int b = 0; b < n_blocks; ++b) n += part[(int64_t)r * n_blocks + b];
+    viol[r] = n;
 }
 
 // The host plan of the bit rows: where each playing variable's slots start, how many words there are
@@ -287,42 +439,85 @@ struct Plan {
 struct Base {
     virtual ~Base() = default;
     virtual int init(const mxs_graph& g, const mxs_params& p, const int32_t* rank, double infinity, int32_t max_distance,
-                     uint64_t seed, int64_t budget, int device) = 0;
+                     const uint64_t* seeds, int32_t n_replicas, int32_t stop_policy, bool single, int64_t budget,
+                     int device) = 0;
     virtual int reset() = 0;
     virtual int run(int32_t n) = 0;
-    virtual int get_state(int32_t* idx, int32_t* cost, uint8_t* has_cost, int32_t* eval, int32_t* improve, int32_t* newv,
-                          int32_t* counter, uint8_t* consistent) = 0;
-    virtual int get_weights(int32_t* out) = 0;
+    virtual int get_state(int32_t r, int32_t* idx, int32_t* cost, uint8_t* has_cost, int32_t* eval, int32_t* improve,
+                          int32_t* newv, int32_t* counter, uint8_t* consistent) = 0;
+    virtual int get_weights(int32_t r, int32_t* out) = 0;
     virtual int eval_cost(const int32_t* idx, double infinity, double* cost, int64_t* viol) = 0;
-    int64_t rounds = 0, stop_round = 0, mask_bytes = 0;  // stop_round 0: not stopped
+    virtual int stop_rounds(int64_t* stop_round, int64_t* rounds_of) = 0;
+    virtual int replica_violations(int64_t* viol) = 0;
+    virtual int best_replica(int32_t* replica, int64_t* stop_round, int64_t* viol) = 0;
+    int64_t rounds = 0, stop_round = 0, mask_bytes = 0;  // stop_round 0: the engine has not ended
+    int32_t n_rep = 1;
 };
 
+enum { STOP_EACH = 0, STOP_FIRST = 1 };
+
+// (violations, stop round with running = +infinity, index): the lexicographic minimum.  A stop does not imply a
+// solution when max_distance is below the graph's diameter, so the violations come first.
+inline int best_of(int n_rep, const long long* viol, const int32_t* stop) {
+    int best = 0;
+    for (int r = 1; r < n_rep; ++r) {
+        const int64_t a = stop[r] ? stop[r] : INT64_MAX, b = stop[best] ? stop[best] : INT64_MAX;
+        if (viol[r] < viol[best] || (viol[r] == viol[best] && a < b)) best = r;
+    }
+    return best;
+}
+
+// The one host engine: R >= 1 seeded runs of the instance with the launches one run needs.  The bit rows, their
+// offsets and strides, the slot view, dom, has_nb and rank are stored once; cur, cost, counter, has_cost, flags, rec are
+// [R][n_vars], weight and viol [R][n_slots], stop and error [R] (words: stop[R], error[R], then the engine-wide word);
+// the seeds are a device array.  The engine ENDS when every replica has stopped (policy `each`) or with the round in
+// which the first one stops (`first`); nothing runs after its end.
+// `single` (mxs_dba_create): one replica under seeds = {seed} whose rounds are launched through the plain entry
+// points on the Dev base of g -- replica 0's slices are the buffers' bases.
 // (T, the table type of mxs_host::create<>, has no part in DBA: nothing here is floating point)
 template <typename T>
 struct Engine : Base {
     int device = 0;
     hipStream_t stream = nullptr;
-    Dev g{};
+    DevR g{};
+    bool single = false;
+    int32_t policy = STOP_EACH;
     Plan plan;
     mxs_host::HostGraph hg;
-    std::vector<int32_t> h_nb;
+    std::vector<int32_t> h_nb, h_stop;  // h_stop [R]: the round in which the replica stopped (0: running)
+    std::vector<uint64_t> h_seeds;
     lsearch::HostSlots hs;
     mxs_host::DevSlots sl;
-    Buf<int32_t> dom, var_rowptr, has_nb, rank, row_stride, weight, cur, cost, counter, words2;  // words2: stop, error
+    Buf<int32_t> dom, var_rowptr, has_nb, rank, row_stride, weight, cur, cost, counter, words, ref_slot, ref_var;
     Buf<int64_t> mask_off;
     Buf<uint32_t> masks;
     Buf<uint8_t> viol, has_cost, flags;
     Buf<Rec> rec;
-    int max_dom = 1;
+    Buf<uint64_t> seeds;
+    Buf<long long> viol_part, viol_base, rep_viol;
+    int max_dom = 1, viol_blocks = 1;
     int64_t max_rounds = INT32_MAX;
 
     ~Engine() override {
         if (stream) (void)hipStreamDestroy(stream);
     }
 
-    int init(const mxs_graph& G, const mxs_params& p, const int32_t* rk, double infinity, int32_t max_distance, uint64_t seed,
-             int64_t budget, int dev) override {
+    // the blocks of one replica in the launches: thread per variable, the start state, the violation count
+    int var_blocks() const { return rephost::blocks_of(hg.nV, TPB); }
+    int init_blocks() const { return rephost::blocks_of(std::max<int64_t>(hg.nV, (int64_t)hs.base.size()), AUX_TPB); }
+
+    int init(const mxs_graph& G, const mxs_params& p, const int32_t* rk, double infinity, int32_t max_distance,
+             const uint64_t* sds, int32_t n_replicas, int32_t stop_policy, bool one_run, int64_t budget, int dev) override {
         device = dev;
+        single = one_run;
+        if (n_replicas < 1 || n_replicas > repcost::MAX_REPLICAS)
+            return fail(MXS_E_INVALID, "the number of replicas must be in 1 .. 4096");
+        if (!sds) return fail(MXS_E_INVALID, "null seeds");
+        if (stop_policy != STOP_EACH && stop_policy != STOP_FIRST)
+            return fail(MXS_E_INVALID, "dba: the stop policy must be 0 (each) or 1 (first)");
+        n_rep = n_replicas;
+        policy = stop_policy;
+        h_seeds.assign(sds, sds + n_replicas);
         if (int rc = mxs_host::open_device(dev, &stream)) return rc;
         if (p.mode == MXS_MODE_MAX)  // the constructor's ValueError (:295-298)
             return fail(MXS_E_INVALID, "DBA is a constraint **satisfaction** algorithm and only support minimization objective");
@@ -353,8 +548,32 @@ struct Engine : Base {
         if (plan.words > budget / (int64_t)sizeof(uint32_t))
             return fail(MXS_E_INVALID, "dba: the violation bit rows take " + std::to_string(mask_bytes) +
                                            " bytes, more than the budget of " + std::to_string(budget));
+        // every launch folds the replica into blockIdx.x: the largest grid must fit
+        viol_blocks = std::max(1, rephost::blocks_of(nF, VIOL_TPB * VIOL_RUN));
+        const int64_t most = std::max<int64_t>({var_blocks(), init_blocks(), viol_blocks});
+        if (most * (int64_t)n_rep > INT32_MAX) return fail(MXS_E_INVALID, "too many replicas for an instance of this size");
         std::vector<int32_t> h_rank(nV);
         for (int v = 0; v < nV; ++v) h_rank[v] = rk ? rk[v] : v;
+        // per constraint, one slot of a playing scope variable (the violation count reads the constraint's bit there)
+        std::vector<int32_t> h_ref_slot(nF, -1), h_ref_var(nF, -1);
+        for (int v = 0; v < nV; ++v)
+            for (int s = hg.vrow[v]; s < hg.vrow[v + 1]; ++s) {
+                const int f = hg.efac[hg.vedges[s]];
+                if (plan.mask_off[s] >= 0 && h_ref_slot[f] < 0) h_ref_slot[f] = s, h_ref_var[f] = v;
+            }
+        // the others hold no playing variable: their variables keep the start draw, their entry is constant after reset
+        std::vector<long long> h_base(n_rep, 0);
+        for (int f = 0; f < nF; ++f) {
+            if (h_ref_slot[f] >= 0) continue;
+            for (int r = 0; r < n_rep; ++r) {
+                int64_t lin = 0;
+                for (int e = hg.frow[f]; e < hg.frow[f + 1]; ++e) {
+                    const int u = hg.evar[e];
+                    lin = lin * hg.dom[u] + (int)(uniform(h_seeds[r], u, 0, D_START) * hg.dom[u]);
+                }
+                h_base[r] += hg.tables[hg.toff[f] + lin] >= infinity ? 1 : 0;
+            }
+        }
         if (int rc = sl.upload(hs, stream, nullptr, false)) return rc;
         MXS_TRY(masks.upload(plan.fill(hg.dom, hg.vrow, hs, hg.tables, infinity), stream));
         MXS_TRY(mask_off.upload(plan.mask_off, stream));
@@ -363,23 +582,30 @@ struct Engine : Base {
         MXS_TRY(var_rowptr.upload(hg.vrow, stream));
         MXS_TRY(has_nb.upload(h_nb, stream));
         MXS_TRY(rank.upload(h_rank, stream));
-        const size_t nS = hs.base.size();
-        MXS_TRY(weight.alloc(nS));
-        MXS_TRY(viol.alloc(nS));
-        MXS_TRY(cur.alloc(nV));
-        MXS_TRY(cost.alloc(nV));
-        MXS_TRY(counter.alloc(nV));
-        MXS_TRY(has_cost.alloc(nV));
-        MXS_TRY(flags.alloc(nV));
-        MXS_TRY(rec.alloc(nV));
-        MXS_TRY(words2.alloc(2));
+        MXS_TRY(ref_slot.upload(h_ref_slot, stream));
+        MXS_TRY(ref_var.upload(h_ref_var, stream));
+        MXS_TRY(seeds.upload(h_seeds, stream));
+        MXS_TRY(viol_base.upload(h_base, stream));
+        const size_t nS = hs.base.size(), R = (size_t)n_rep;
+        if (int rc = rephost::alloc_rep(weight, R * nS, "weights")) return rc;
+        if (int rc = rephost::alloc_rep(viol, R * nS, "violation flags")) return rc;
+        if (int rc = rephost::alloc_rep(cur, R * nV, "values")) return rc;
+        if (int rc = rephost::alloc_rep(cost, R * nV, "held costs")) return rc;
+        if (int rc = rephost::alloc_rep(counter, R * nV, "termination counters")) return rc;
+        if (int rc = rephost::alloc_rep(has_cost, R * nV, "cost flags")) return rc;
+        if (int rc = rephost::alloc_rep(flags, R * nV, "flags")) return rc;
+        if (int rc = rephost::alloc_rep(rec, R * nV, "improvement records")) return rc;
+        if (int rc = rephost::alloc_rep(words, 2 * R + 1, "stop words")) return rc;
+        if (int rc = rephost::alloc_rep(viol_part, R * viol_blocks, "violation partials")) return rc;
+        if (int rc = rephost::alloc_rep(rep_viol, R, "violation counts")) return rc;
         const lsearch::Slots view = sl.view();
         g.n_vars = nV;
         g.max_distance = max_distance;
         const double up = std::ceil(infinity);
         g.inf_lim = up >= (double)INT32_MAX ? INT32_MAX : (up <= (double)INT32_MIN ? INT32_MIN : (int32_t)up);
         g.inf_eq = up == infinity && up >= 0.0 && up < (double)INT32_MAX ? (int32_t)up : -1;
-        g.seed = seed;
+        g.seed = single ? h_seeds[0] : 0;  // the replica kernels: seeds[r], per block
+        g.bpr = 1, g.n_rep = n_rep, g.stop_first = policy == STOP_FIRST, g.n_slots = (int64_t)nS, g.seeds = seeds.p;
         g.dom = dom.p;
         g.var_rowptr = var_rowptr.p;
         g.has_nb = has_nb.p;
@@ -399,46 +625,39 @@ struct Engine : Base {
         g.counter = counter.p;
         g.flags = flags.p;
         g.rec = rec.p;
-        g.stop = words2.p;
-        g.error = words2.p + 1;
+        g.stop = words.p;
+        g.error = words.p + n_rep;
+        g.first = words.p + 2 * n_rep;
         return reset();
     }
 
-    // on_start (:341-349): random.choice(domain) for every variable, initial values are not looked at; cost None
+    // on_start (:341-349), every replica (k_dbar_init): random.choice(domain) for every variable, initial values are
+    // not looked at; cost None; the weights 1; the stop words cleared
     int reset() override {
         MXS_TRY(hipSetDevice(device));
-        const int nV = g.n_vars;
-        const size_t nS = hs.base.size();
-        std::vector<int32_t> c0(nV), w0(nS, 1);
-        std::vector<Rec> r0(nV, Rec{0, 0, 0, -1});
-        for (int v = 0; v < nV; ++v) c0[v] = (int)(uniform(g.seed, v, 0, D_START) * hg.dom[v]);
-        if (nV) {
-            MXS_TRY(hipMemcpyAsync(cur.p, c0.data(), 4 * (size_t)nV, hipMemcpyHostToDevice, stream));
-            MXS_TRY(hipMemcpyAsync(rec.p, r0.data(), sizeof(Rec) * (size_t)nV, hipMemcpyHostToDevice, stream));
-            MXS_TRY(hipMemsetAsync(cost.p, 0, 4 * (size_t)nV, stream));
-            MXS_TRY(hipMemsetAsync(counter.p, 0, 4 * (size_t)nV, stream));
-            MXS_TRY(hipMemsetAsync(has_cost.p, 0, (size_t)nV, stream));
-            MXS_TRY(hipMemsetAsync(flags.p, 0, (size_t)nV, stream));
+        if (g.n_vars) {
+            g.bpr = init_blocks();
+            hipLaunchKernelGGL(k_dbar_init, dim3((unsigned)(g.bpr * n_rep)), dim3(AUX_TPB), 0, stream, g);
+            MXS_TRY(hipGetLastError());
         }
-        if (nS) {
-            MXS_TRY(hipMemcpyAsync(weight.p, w0.data(), 4 * nS, hipMemcpyHostToDevice, stream));
-            MXS_TRY(hipMemsetAsync(viol.p, 0, nS, stream));
-        }
-        MXS_TRY(hipMemsetAsync(words2.p, 0, 8, stream));
+        MXS_TRY(hipMemsetAsync(words.p, 0, 4 * (2 * (size_t)n_rep + 1), stream));
         MXS_TRY(hipStreamSynchronize(stream));
+        h_stop.assign(n_rep, 0);
         rounds = 0;
         stop_round = 0;
         return MXS_OK;
     }
 
+    // the ok phase of all replicas; the single run: the plain entry points on the Dev part of g
     template <int MAXD>
     void launch_eval(const dim3& grid, const dim3& block) {
-        hipLaunchKernelGGL((k_dba_eval<MAXD>), grid, block, 0, stream, g);
+        if (single) hipLaunchKernelGGL((k_dba_eval<MAXD>), grid, block, 0, stream, (const Dev&)g);
+        else hipLaunchKernelGGL((k_dbar_eval<MAXD>), grid, block, 0, stream, g);
     }
 
     int run(int32_t n) override {
         MXS_TRY(hipSetDevice(device));
-        if (stop_round) return MXS_OK;  // the run has ended: nothing after the stop runs
+        if (stop_round) return MXS_OK;  // the engine has ended: nothing after its end runs
         if (rounds + (int64_t)n > max_rounds)
             return fail(MXS_E_INVALID, "dba: weights and evals are int32, at most " + std::to_string(max_rounds) +
                                            " rounds on this instance");
@@ -447,41 +666,103 @@ struct Engine : Base {
             rounds += n;
             return MXS_OK;
         }
-        const dim3 grid((unsigned)((nV + TPB - 1) / TPB)), block(TPB);
+        const int vbpr = var_blocks();
+        const dim3 grid((unsigned)vbpr * (unsigned)n_rep), block(TPB);
+        g.bpr = vbpr;  // (a kernel takes its argument by value: the copy is made at the launch)
         for (int32_t r = 0; r < n; ++r) {  // no read-back per round: the kernels of the rounds after a stop return at once
             g.round = (int32_t)(rounds + 1 + r);
             if (max_dom <= 4) launch_eval<4>(grid, block);
             else if (max_dom <= 8) launch_eval<8>(grid, block);
             else if (max_dom <= 32) launch_eval<32>(grid, block);
-            else hipLaunchKernelGGL(k_dba_eval_wide, grid, block, 0, stream, g);
+            else if (single) hipLaunchKernelGGL(k_dba_eval_wide, grid, block, 0, stream, (const Dev&)g);
+            else hipLaunchKernelGGL(k_dbar_eval_wide, grid, block, 0, stream, g);
             MXS_TRY(hipGetLastError());
-            hipLaunchKernelGGL(k_dba_decide, grid, block, 0, stream, g);
+            if (single) hipLaunchKernelGGL(k_dba_decide, grid, block, 0, stream, (const Dev&)g);
+            else hipLaunchKernelGGL(k_dbar_decide, grid, block, 0, stream, g);
             MXS_TRY(hipGetLastError());
         }
-        int32_t w[2] = {0, 0};
-        MXS_TRY(hipMemcpyAsync(w, words2.p, 8, hipMemcpyDeviceToHost, stream));
+        const size_t R = (size_t)n_rep;
+        std::vector<int32_t> w(2 * R + 1, 0);  // stop[R], error[R], the engine-wide word
+        MXS_TRY(hipMemcpyAsync(w.data(), words.p, 4 * w.size(), hipMemcpyDeviceToHost, stream));
         MXS_TRY(hipStreamSynchronize(stream));
-        if (w[1])
-            return fail(MXS_E_STATE, "dba: a variable improves with no best value: every eval of it is above infinity "
-                                     "(the reference raises IndexError there); infinity is too small for the weights");
-        if (w[0]) rounds = stop_round = w[0];
+        for (size_t r = 0; r < R; ++r)
+            if (w[R + r])
+                return fail(MXS_E_STATE,
+                            "dba: a variable improves with no best value: every eval of it is above infinity "
+                            "(the reference raises IndexError there); infinity is too small for the weights" +
+                                (single ? std::string() : " (replica " + std::to_string(r) + ")"));
+        // a replica that stopped in the engine's last round or before it (policy `first`: the others never ran theirs)
+        int64_t end = policy == STOP_FIRST ? w[2 * R] : 0;
+        bool all = true;
+        for (size_t r = 0; r < R; ++r) {
+            h_stop[r] = w[r];
+            all = all && w[r] != 0;
+            if (policy == STOP_EACH) end = std::max<int64_t>(end, w[r]);
+        }
+        if (policy == STOP_EACH && !all) end = 0;
+        if (end) rounds = stop_round = end;
         else rounds += n;
         return MXS_OK;
     }
 
-    int get_state(int32_t* idx, int32_t* cst, uint8_t* has, int32_t* ev, int32_t* imp, int32_t* nv, int32_t* cnt,
+    // per replica: the round in which it stopped (0: running) and the rounds it ran
+    int stop_rounds(int64_t* stop_of, int64_t* rounds_of) override {
+        for (int r = 0; r < n_rep; ++r) {
+            if (stop_of) stop_of[r] = h_stop[r];
+            if (rounds_of) rounds_of[r] = h_stop[r] ? h_stop[r] : rounds;
+        }
+        return MXS_OK;
+    }
+
+    // the violated constraints of every replica's current assignment into rep_viol, fetched
+    int violations(std::vector<long long>& hv) {
+        MXS_TRY(hipSetDevice(device));
+        g.bpr = viol_blocks;
+        const ViolArgs a{ref_slot.p, ref_var.p, hg.nF, viol_part.p};
+        hipLaunchKernelGGL(k_dbar_viol_partial, dim3((unsigned)(viol_blocks * n_rep)), dim3(VIOL_TPB), 0, stream, g, a);
+        MXS_TRY(hipGetLastError());
+        hipLaunchKernelGGL(k_dbar_viol_final, dim3((unsigned)rephost::blocks_of(n_rep, 64)), dim3(64), 0, stream, (int)n_rep,
+                           viol_blocks, (const long long*)viol_part.p, (const long long*)viol_base.p, rep_viol.p);
+        MXS_TRY(hipGetLastError());
+        hv.resize(n_rep);
+        MXS_TRY(hipMemcpyAsync(hv.data(), rep_viol.p, 8 * (size_t)n_rep, hipMemcpyDeviceToHost, stream));
+        MXS_TRY(hipStreamSynchronize(stream));
+        return MXS_OK;
+    }
+
+    int replica_violations(int64_t* out) override {
+        std::vector<long long> hv;
+        if (int rc = violations(hv)) return rc;
+        for (int r = 0; r < n_rep; ++r)
+            if (out) out[r] = (int64_t)hv[r];
+        return MXS_OK;
+    }
+
+    int best_replica(int32_t* replica, int64_t* stop_of, int64_t* viol_out) override {
+        std::vector<long long> hv;
+        if (int rc = violations(hv)) return rc;
+        const int r = best_of(n_rep, hv.data(), h_stop.data());
+        if (replica) *replica = r;
+        if (stop_of) *stop_of = h_stop[r];
+        if (viol_out) *viol_out = (int64_t)hv[r];
+        return MXS_OK;
+    }
+
+    int get_state(int32_t r, int32_t* idx, int32_t* cst, uint8_t* has, int32_t* ev, int32_t* imp, int32_t* nv, int32_t* cnt,
                   uint8_t* cons) override {
+        if (r < 0 || r >= n_rep) return fail(MXS_E_INVALID, "replica out of range");
         MXS_TRY(hipSetDevice(device));
         const int nV = g.n_vars;
         if (!nV) return MXS_OK;
         std::vector<Rec> hr(nV);
         std::vector<uint8_t> hf(nV);
-        if (idx) MXS_TRY(hipMemcpyAsync(idx, cur.p, 4 * (size_t)nV, hipMemcpyDeviceToHost, stream));
-        if (cst) MXS_TRY(hipMemcpyAsync(cst, cost.p, 4 * (size_t)nV, hipMemcpyDeviceToHost, stream));
-        if (has) MXS_TRY(hipMemcpyAsync(has, has_cost.p, (size_t)nV, hipMemcpyDeviceToHost, stream));
-        if (cnt) MXS_TRY(hipMemcpyAsync(cnt, counter.p, 4 * (size_t)nV, hipMemcpyDeviceToHost, stream));
-        MXS_TRY(hipMemcpyAsync(hr.data(), rec.p, sizeof(Rec) * (size_t)nV, hipMemcpyDeviceToHost, stream));
-        MXS_TRY(hipMemcpyAsync(hf.data(), flags.p, (size_t)nV, hipMemcpyDeviceToHost, stream));
+        const size_t roff = (size_t)r * nV;
+        if (idx) MXS_TRY(hipMemcpyAsync(idx, cur.p + roff, 4 * (size_t)nV, hipMemcpyDeviceToHost, stream));
+        if (cst) MXS_TRY(hipMemcpyAsync(cst, cost.p + roff, 4 * (size_t)nV, hipMemcpyDeviceToHost, stream));
+        if (has) MXS_TRY(hipMemcpyAsync(has, has_cost.p + roff, (size_t)nV, hipMemcpyDeviceToHost, stream));
+        if (cnt) MXS_TRY(hipMemcpyAsync(cnt, counter.p + roff, 4 * (size_t)nV, hipMemcpyDeviceToHost, stream));
+        MXS_TRY(hipMemcpyAsync(hr.data(), rec.p + roff, sizeof(Rec) * (size_t)nV, hipMemcpyDeviceToHost, stream));
+        MXS_TRY(hipMemcpyAsync(hf.data(), flags.p + roff, (size_t)nV, hipMemcpyDeviceToHost, stream));
         MXS_TRY(hipStreamSynchronize(stream));
         for (int v = 0; v < nV; ++v) {
             if (ev) ev[v] = hr[v].eval;
@@ -492,21 +773,22 @@ struct Engine : Base {
         return MXS_OK;
     }
 
-    int get_weights(int32_t* out) override {
+    int get_weights(int32_t r, int32_t* out) override {
+        if (r < 0 || r >= n_rep) return fail(MXS_E_INVALID, "replica out of range");
         MXS_TRY(hipSetDevice(device));
         const size_t nS = hs.base.size();
         if (!out || !nS) return MXS_OK;
-        MXS_TRY(hipMemcpyAsync(out, weight.p, 4 * nS, hipMemcpyDeviceToHost, stream));
+        MXS_TRY(hipMemcpyAsync(out, weight.p + (size_t)r * nS, 4 * nS, hipMemcpyDeviceToHost, stream));
         MXS_TRY(hipStreamSynchronize(stream));
         return MXS_OK;
     }
 
-    // DCOP.solution_cost of an assignment (constraints and the variables' own costs)
+    // DCOP.solution_cost of an assignment (constraints and the variables' own costs); NULL: replica 0's
     int eval_cost(const int32_t* idx, double infinity, double* cst, int64_t* viol_out) override {
         std::vector<int32_t> c;
         if (!idx) {
             c.resize(g.n_vars);
-            int rc = get_state(c.data(), nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr);
+            int rc = get_state(0, c.data(), nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr);
             if (rc) return rc;
             idx = c.data();
         }
@@ -524,7 +806,19 @@ extern "C" {
 
 int mxs_dba_create(const mxs_graph* g, const mxs_params* p, const int32_t* name_rank, double infinity, int32_t max_distance,
                    uint64_t seed, int64_t mask_budget_bytes, int32_t device, mxs_dba** out) {
-    return mxs_host::create<mxs_dba, dba::Engine>(g, p, out, name_rank, infinity, max_distance, seed, mask_budget_bytes, device);
+    return mxs_host::create<mxs_dba, dba::Engine>(g, p, out, name_rank, infinity, max_distance, (const uint64_t*)&seed, 1,
+                                                  (int32_t)dba::STOP_EACH, true, mask_budget_bytes, device);
+}
+int mxs_dba_create_replicas(const mxs_graph* g, const mxs_params* p, const int32_t* name_rank, double infinity,
+                            int32_t max_distance, const uint64_t* seeds, int32_t n_replicas, int32_t stop_policy,
+                            int64_t mask_budget_bytes, int32_t device, mxs_dba** out) {
+    return mxs_host::create<mxs_dba, dba::Engine>(g, p, out, name_rank, infinity, max_distance, seeds, n_replicas, stop_policy,
+                                                  false, mask_budget_bytes, device);
+}
+int mxs_dba_replicas(const mxs_dba* e, int32_t* n) {
+    if (!e) return mxs_host::fail(MXS_E_INVALID, "null handle");
+    if (n) *n = e->impl->n_rep;
+    return MXS_OK;
 }
 int mxs_dba_reset(mxs_dba* e) { return e ? e->impl->reset() : mxs_host::fail(MXS_E_INVALID, "null handle"); }
 int mxs_dba_run(mxs_dba* e, int32_t n_rounds) {
@@ -545,11 +839,28 @@ int mxs_dba_finished(const mxs_dba* e, int32_t* stopped, int64_t* stop_round) {
 }
 int mxs_dba_get_state(mxs_dba* e, int32_t* idx, int32_t* cost, uint8_t* has_cost, int32_t* eval, int32_t* improve,
                       int32_t* new_value, int32_t* counter, uint8_t* consistent) {
-    return e ? e->impl->get_state(idx, cost, has_cost, eval, improve, new_value, counter, consistent)
+    return e ? e->impl->get_state(0, idx, cost, has_cost, eval, improve, new_value, counter, consistent)
+             : mxs_host::fail(MXS_E_INVALID, "null handle");
+}
+int mxs_dba_get_state_replica(mxs_dba* e, int32_t replica, int32_t* idx, int32_t* cost, uint8_t* has_cost, int32_t* eval,
+                              int32_t* improve, int32_t* new_value, int32_t* counter, uint8_t* consistent) {
+    return e ? e->impl->get_state(replica, idx, cost, has_cost, eval, improve, new_value, counter, consistent)
              : mxs_host::fail(MXS_E_INVALID, "null handle");
 }
 int mxs_dba_get_weights(mxs_dba* e, int32_t* out) {
-    return e ? e->impl->get_weights(out) : mxs_host::fail(MXS_E_INVALID, "null handle");
+    return e ? e->impl->get_weights(0, out) : mxs_host::fail(MXS_E_INVALID, "null handle");
+}
+int mxs_dba_get_weights_replica(mxs_dba* e, int32_t replica, int32_t* out) {
+    return e ? e->impl->get_weights(replica, out) : mxs_host::fail(MXS_E_INVALID, "null handle");
+}
+int mxs_dba_stop_rounds(mxs_dba* e, int64_t* stop_round, int64_t* rounds) {
+    return e ? e->impl->stop_rounds(stop_round, rounds) : mxs_host::fail(MXS_E_INVALID, "null handle");
+}
+int mxs_dba_replica_violations(mxs_dba* e, int64_t* violations) {
+    return e ? e->impl->replica_violations(violations) : mxs_host::fail(MXS_E_INVALID, "null handle");
+}
+int mxs_dba_best_replica(mxs_dba* e, int32_t* replica, int64_t* stop_round, int64_t* violations) {
+    return e ? e->impl->best_replica(replica, stop_round, violations) : mxs_host::fail(MXS_E_INVALID, "null handle");
 }
 int mxs_dba_mask_bytes(const mxs_dba* e, int64_t* bytes) {
     if (!e) return mxs_host::fail(MXS_E_INVALID, "null handle");

@@ -77,6 +77,12 @@ GDBA_REPLICA_SYMBOLS = (
     "mxs_gdba_replica_costs", "mxs_gdba_track_best", "mxs_gdba_get_best",
 )
 
+# ... and DBA's replicas (include/maxsum_gpu_dba_replicas.h, for the same reason)
+DBA_REPLICA_SYMBOLS = (
+    "mxs_dba_create_replicas", "mxs_dba_replicas", "mxs_dba_get_state_replica", "mxs_dba_get_weights_replica",
+    "mxs_dba_stop_rounds", "mxs_dba_replica_violations", "mxs_dba_best_replica",
+)
+
 MAX_PEERS = 8
 
 
@@ -295,6 +301,15 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
         "mxs_gdba_replica_costs": ([vp, C.c_double, vp, vp], C.c_int),
         "mxs_gdba_track_best": ([vp, i32, C.c_double], C.c_int),
         "mxs_gdba_get_best": ([vp, i32, C.POINTER(i32), C.POINTER(i64), C.POINTER(C.c_double), C.POINTER(i64), vp], C.c_int),
+        # ... and DbaEngine(replicas=R) (pydcop_amd/dba.py)
+        "mxs_dba_create_replicas": ([C.POINTER(CGraph), C.POINTER(CParams), vp, C.c_double, i32, vp, i32, i32, i64, i32,
+                                     C.POINTER(vp)], C.c_int),
+        "mxs_dba_replicas": ([vp, C.POINTER(i32)], C.c_int),
+        "mxs_dba_get_state_replica": ([vp, i32, vp, vp, vp, vp, vp, vp, vp, vp], C.c_int),
+        "mxs_dba_get_weights_replica": ([vp, i32, vp], C.c_int),
+        "mxs_dba_stop_rounds": ([vp, vp, vp], C.c_int),
+        "mxs_dba_replica_violations": ([vp, vp], C.c_int),
+        "mxs_dba_best_replica": ([vp, C.POINTER(i32), C.POINTER(i64), C.POINTER(i64)], C.c_int),
     }
     for name, (argtypes, restype) in later.items():
         fn = getattr(lib, name, None)

@@ -1,0 +1,21 @@
+"""DBA replicas on the emulated engine build (the very same dba.h, g++ against the fake HIP runtime): the CPU twin
+of tests/test_gpu_dba_replicas.py.  The tests are those of tests/dba_replicas_common.py."""
+import pytest
+
+from dba_replicas_common import (  # noqa: F401  (collected here)
+    test_every_replica_equals_the_oracle_across_a_partial_block,
+    test_stop_first_ends_every_replica_with_the_first_stop,
+    test_all_eval_paths_arity3_initial_values_and_name_ranks,
+    test_reference_fixtures,
+    test_fixture_set_is_complete,
+    test_many_small_replicas,
+    test_explicit_seeds,
+    test_one_replica_equals_the_single_run_engine,
+    test_violations_include_a_variable_that_never_plays,
+    test_refusals)
+
+
+@pytest.fixture(scope="module")
+def lib_path():
+    from emu.build_emu import build
+    return build()

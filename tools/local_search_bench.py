@@ -39,7 +39,11 @@ side), then one "replicas" row per R.  The GDBA rows (`--replica-algos gdba`; "a
 GdbaEngine(replicas=R), gdba.h, increase modes `--gdba-modes`) follow the protocol of the MGM-2 rows with `mxs_gdba_create`
 as the single side; every timed window starts from reset() and is capped at 20 000 rounds (the counters allow 65535),
 and a row also has the rounds with the best state tracked every round and every 10th ("best_every_1_us_per_round",
-"best_every_10_us_per_round").
+"best_every_10_us_per_round").  The DBA rows (`--replica-algos dba`; "algo": "dba", DbaEngine(replicas=R), dba.h)
+follow the protocol of the MGM-2 rows with `mxs_dba_create` as the single side, on the HARD colouring (`infinity: 1000`,
+no unary noise) with a `max_distance` no counter reaches, so that nothing stops; a "replicas" row gives R times the single
+run's time beside the time of a round of all replicas ("R_singles_us_per_round") and the time of the device's violation
+count ("replica_violations_us": mxs_dba_replica_violations with its copy back).
 """
 import argparse
 import json
@@ -479,6 +483,88 @@ def gdba_replica_rows(a):
                 single.close()
 
 
+class BaselineDba:
+    """The DBA engine of ANOTHER build of the library (--baseline-lib): mxs_dba_create / _run / _destroy."""
+
+    def __init__(self, path, g, p, seed, infinity, max_distance):
+        import ctypes as C
+        from pydcop_amd.engine import load_library
+        load_library()                       # (the HIP runtime first: the libraries are linked without it)
+        self._lib = C.CDLL(os.path.abspath(path))
+        self._lib.mxs_version.restype = C.c_int32
+        self.version = int(self._lib.mxs_version())
+        self._lib.mxs_dba_create.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_int32, C.c_uint64,
+                                             C.c_int64, C.c_int32, C.c_void_p]
+        self._lib.mxs_dba_run.argtypes = [C.c_void_p, C.c_int32]
+        self._lib.mxs_dba_destroy.argtypes = [C.c_void_p]
+        self._g, self._p = g.to_c(), p.to_c()      # (kept alive)
+        self._h = C.c_void_p()
+        rc = self._lib.mxs_dba_create(C.byref(self._g), C.byref(self._p), None, float(infinity), int(max_distance), seed, 0,
+                                      0, C.byref(self._h))
+        if rc:
+            raise RuntimeError(f"mxs_dba_create of {path}: {rc}")
+
+    def run(self, n):
+        if self._lib.mxs_dba_run(self._h, int(n)):
+            raise RuntimeError("mxs_dba_run of the baseline library failed")
+
+    def close(self):
+        self._lib.mxs_dba_destroy(self._h)
+
+
+DBA_NEVER = 2 ** 31 - 1          # a max_distance no termination counter reaches: nothing stops in a window
+
+
+def dba_replica_rows(a):
+    """The protocol of the MGM-2 rows for DbaEngine(replicas=R) (dba.h) on the HARD colouring (`infinity: 1000`, no
+    unary noise), `max_distance` above any round count so that nothing stops.  A "replicas" row also has the time of
+    the device's violation count (`violations()`: mxs_dba_replica_violations, its copy back included)."""
+    from pydcop_amd.dba import DbaEngine
+    kw = dict(infinity=1000, max_distance=DBA_NEVER)
+    for n_vars in a.replica_sizes:
+        g = G.random_coloring(n_vars, seed=0, variant="hard", unary_noise=0, names=False)
+        p = Params()
+
+        def single_side():
+            if a.baseline_lib:
+                e = BaselineDba(a.baseline_lib, g, p, 1, kw["infinity"], kw["max_distance"])
+                return e, f"mxs_version {e.version}"
+            return DbaEngine(g, p, seed=1, lib_path=a.lib, **kw), "this"
+
+        base = {"algo": "dba", "instance": f"coloring_hard_{n_vars}", "dtype": "int32", "n_vars": n_vars}
+        # two engines of the single side against each other: what the protocol itself spreads
+        left, baseline = single_side()
+        right, _ = single_side()
+        one, other = alternated(a, left, right)
+        print(json.dumps(dict(base, row="instance_to_instance", baseline=baseline, left_us_per_round=one,
+                              right_us_per_round=other, ratio_right_to_left=round(median(other) / median(one), 4))),
+              flush=True)
+        right.close()
+        # this library's mxs_dba_create against the single side
+        mine = DbaEngine(g, p, seed=1, lib_path=a.lib, **kw)
+        one, new = alternated(a, left, mine)
+        print(json.dumps(dict(base, row="single_vs_baseline", baseline=baseline, single_us_per_round=one,
+                              this_us_per_round=new, ratio_this_to_single=round(median(new) / median(one), 4))), flush=True)
+        left.close(), mine.close()
+        for R in a.replicas:
+            single, baseline = single_side()
+            eng = DbaEngine(g, p, seeds=[1 + r for r in range(R)], replicas=R, lib_path=a.lib, **kw)   # (R = 1 too)
+            one, many = alternated(a, single, eng)
+            assert not eng.finished
+            row = dict(base, row="replicas", replicas=R, baseline=baseline, single_us_per_round=one,
+                       replicas_us_per_round=many, R_singles_us_per_round=round(R * median(one), 2),
+                       ratio_R_singles_to_replicas=round(R * median(one) / median(many), 2))
+            reps = max(3, min(2000, int(0.2 * a.window * 1e6 / max(many[0], 1.0))))
+            t0 = time.perf_counter()
+            for _ in range(reps):
+                viol = eng.violations()
+            row["replica_violations_us"] = round(1e6 * (time.perf_counter() - t0) / reps, 1)
+            row["violations"] = [int(v) for v in viol[:8]]
+            print(json.dumps(row), flush=True)
+            eng.close()
+            single.close()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--cycles", type=int, default=500)
@@ -495,7 +581,7 @@ def main():
     ap.add_argument("--warmup", type=float, default=0.5, help="seconds of warm-up per engine of the replica rows")
     ap.add_argument("--baseline-lib", default=None,
                     help="replica rows: the single-seed side from this other build of the library (mxs_dsa_create)")
-    ap.add_argument("--replica-algos", nargs="*", default=["dsa", "mgm"], choices=["dsa", "mgm", "mgm2", "gdba"])
+    ap.add_argument("--replica-algos", nargs="*", default=["dsa", "mgm"], choices=["dsa", "mgm", "mgm2", "gdba", "dba"])
     ap.add_argument("--gdba-modes", nargs="*", default=["T", "C"], choices=["E", "R", "C", "T"],
                     help="the increase modes of the GDBA replica rows")
     a = ap.parse_args()
@@ -508,6 +594,8 @@ def main():
             mgm2_replica_rows(a)
         if "gdba" in a.replica_algos:
             gdba_replica_rows(a)
+        if "dba" in a.replica_algos:
+            dba_replica_rows(a)
         return
     if a.dba_rounds > 0:
         return dba_rows(a)
