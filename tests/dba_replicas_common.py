@@ -6,6 +6,7 @@ is an integer and compared exactly.  The test functions live here, below the hel
 (emulated build) and tests/test_gpu_dba_replicas.py (the HIP library) import them and provide the `lib_path` fixture,
 so the two runs cannot drift apart."""
 import ctypes as C
+import functools
 import os
 
 import numpy as np
@@ -70,25 +71,31 @@ def same_run(eng, oras, replicas, infinity, what):
         np.testing.assert_array_equal(b["idx"], oras[w].state()["idx"], err_msg=f"best() {what}")
 
 
-def compare_replicas(graph, params, kw, replicas, lib_path=None, seed=5, seeds=None, check=None, steps=STEPS):
+def compare_replicas(graph, params, kw, replicas, lib_path=None, seed=5, seeds=None, check=None, steps=STEPS, states=None,
+                     each_step=None):
     """stop="each": every replica of `check` (default: all) against OracleDba(seed=seeds[r]): every key of STATE_KEYS
     and every weight after the steps, then after reset() and 5 rounds; at every step the stop rounds, the rounds run,
-    the violations and best().  Returns the engine (after those 5 rounds), the oracles' start states, and their stop
-    rounds and violations after the steps."""
+    the violations and best().  `states`: the replicas of `check` whose states and weights are compared (default: all
+    of `check`; the others' stop rounds, rounds run and violations still are).  `each_step(oras, rounds)`: called after
+    every step, for conditions on the oracle side.  Returns the engine (after those 5 rounds), the oracles' start
+    states, and their stop rounds and violations after the steps."""
     eng = DbaEngine(graph, params, seed=seed, seeds=seeds, replicas=replicas, stop="each", lib_path=lib_path, **kw)
     assert eng.replicas == replicas and len(eng.seeds) == replicas
     if seeds is None:
         assert eng.seeds == [seed + r for r in range(replicas)]
     check = list(range(replicas)) if check is None else list(check)
     oras = {r: OracleDba(graph, params, seed=eng.seeds[r], **kw) for r in check}
+    watched = oras if states is None else {r: oras[r] for r in states}
     done, starts = 0, None
     for n in steps:
         eng.run(n)
         done += n
         for ora in oras.values():
             ora.run(n)
-        same_state(eng, oras, f"after {done} rounds")
+        same_state(eng, watched, f"after {done} rounds")
         same_run(eng, oras, replicas, kw["infinity"], f"after {done} rounds")
+        if each_step is not None:
+            each_step(oras, done)
         if starts is None:
             starts = {r: o.state()["idx"] for r, o in oras.items()}
     stops = {r: o.stop_round for r, o in oras.items()}
@@ -97,11 +104,11 @@ def compare_replicas(graph, params, kw, replicas, lib_path=None, seed=5, seeds=N
     assert eng.cycle_count == 0 and not eng.finished and eng.stop_round == 0 and eng.stop_rounds == [0] * replicas
     for ora in oras.values():
         ora.reset()
-    same_state(eng, oras, "after reset()")
+    same_state(eng, watched, "after reset()")
     eng.run(5)
     for ora in oras.values():
         ora.run(5)
-    same_state(eng, oras, "after reset() and 5 rounds")
+    same_state(eng, watched, "after reset() and 5 rounds")
     same_run(eng, oras, replicas, kw["infinity"], "after reset() and 5 rounds")
     # replica 0 is what the single-state calls mean
     np.testing.assert_array_equal(eng.assignment()[0], eng.assignment(0)[0])
@@ -297,6 +304,192 @@ def test_violations_include_a_variable_that_never_plays(lib_path):
         for o in oras:
             o.reset()
         assert list(eng.violations()) == [oracle_violations(o, 1000) for o in oras]
+
+
+# ---- the boundaries of the launches: several blocks of k_dbar_viol_partial (VIOL_CHUNK constraints each) and of the
+# wide walk per replica, a second and a third block of k_dbar_viol_final (64 replicas each), the top of the replica
+# range, the ranking's ties, stop="first" with the stopper past the first 64 replicas
+
+VIOL_CHUNK = 1024                               # the constraints one block of k_dbar_viol_partial counts
+BEYOND_64 = (0, 63, 64, 65, 129)
+SMALL_KW = dict(infinity=1000, max_distance=50)
+
+
+def small_hard():
+    return G.random_coloring(12, seed=31, variant="hard", unary_noise=0)
+
+
+def chunk_violations(g, idx, infinity):
+    """the violated constraints of every VIOL_CHUNK constraints in index order: what part[r][b] must hold"""
+    counts = [count_violations_of(g, idx, infinity, f0, min(f0 + VIOL_CHUNK, g.n_factors))
+              for f0 in range(0, g.n_factors, VIOL_CHUNK)]
+    assert sum(counts) == count_violations(g, idx, infinity)
+    return counts
+
+
+def count_violations_of(g, idx, infinity, f0, f1):
+    n = 0
+    for f in range(f0, f1):
+        lin = 0
+        for e in range(g.factor_rowptr[f], g.factor_rowptr[f + 1]):
+            lin = lin * int(g.dom_size[g.edge_var[e]]) + int(idx[g.edge_var[e]])
+        n += bool(g.tables[int(g.table_off[f]) + lin] >= infinity)
+    return n
+
+
+@pytest.mark.parametrize("n_vars,replicas", [(640, 3), (1200, 2)], ids=["two_blocks", "three_blocks"])
+def test_violation_partials_of_several_blocks(n_vars, replicas, lib_path):
+    """Hard colourings of 1280 and 2400 constraints: part[r][b] with b = 1 and b = 2, the last chunk partial (256 and 352
+    constraints).  Measured on the oracle (seeds 5.., max_distance 5): after 0, 1 and 4 rounds every chunk of every
+    replica holds violations (at 640 variables [322, 96], [175, 43], [63, 15] for seed 5), and the replicas' counts
+    differ chunk by chunk."""
+    g = G.random_coloring(n_vars, seed=32, variant="hard", unary_noise=0)
+    assert -(-g.n_factors // VIOL_CHUNK) == {640: 2, 1200: 3}[n_vars] and g.n_factors % VIOL_CHUNK >= 200
+    seen = []
+
+    def chunks_hold_violations(oras, done):       # (the oracle side) a dropped, doubled or misplaced partial is seen
+        counts = {r: chunk_violations(g, o.state()["idx"], 1000) for r, o in oras.items()}
+        assert all(min(c) > 0 for c in counts.values()), (done, counts)
+        assert any(counts[r][b] != counts[0][b] for r in counts for b in range(len(counts[0]))), (done, counts)
+        seen.append(counts)
+
+    eng, *_ = compare_replicas(g, Params(), HARD_KW, replicas, lib_path=lib_path, steps=(0, 1, 3),
+                               each_step=chunks_hold_violations)
+    eng.close()
+    assert len(seen) == 3
+
+
+WIDE_DOMS = (33, 5, 40, 3, 65, 8, 34)
+
+
+def wide_instance():
+    """72 variables of domains around the word boundaries (33, 34, 40, 65 among them) on a ring with chords, 0 / 1000
+    tables at the density of dba_common.binary_big_domains: the wide walk (a domain above 32) at two blocks of 64
+    variables per replica"""
+    from gdba_common import from_scopes
+    n = 72
+    doms = [WIDE_DOMS[i % len(WIDE_DOMS)] for i in range(n)]
+    scopes = [[i, (i + 1) % n] if i % 2 else [(i + 1) % n, i] for i in range(n)]
+    scopes += [[i, (i + 29) % n] for i in range(0, n, 3)]
+    g = from_scopes(doms, scopes, np.random.default_rng(96), 0, 2)
+    g.tables = 1000.0 * (np.random.default_rng(97).random(g.tables.shape[0]) < 0.85)
+    return g
+
+
+def test_wide_domains_at_two_blocks_per_replica(lib_path):
+    g = wide_instance()
+    assert g.n_vars > 64 and g.dom_size.max() > 32
+    moved = []
+    eng, starts, *_ = compare_replicas(g, Params(), SMALL_KW, 3, lib_path=lib_path, steps=(0, 1, 3, 4),
+                                       each_step=lambda oras, done: moved.append({r: o.state()["idx"].copy() for r, o in oras.items()}))
+    eng.close()
+    # (the oracle side) variables of the second block move, and the replicas differ there
+    assert all((moved[-1][r][64:] != moved[0][r][64:]).any() for r in range(3))
+    assert all((moved[-1][r][64:] != moved[-1][0][64:]).any() for r in (1, 2))
+
+
+def lone_unary_violations(g, idx, infinity):
+    return sum(bool(g.tables[int(g.table_off[f]) + int(idx[v])] >= infinity) for f, v in never_playing(g))
+
+
+@pytest.mark.parametrize("name", ["small_hard", "never_playing"])
+def test_more_than_64_replicas(name, lib_path):
+    """130 replicas: a second and a third block of k_dbar_viol_final.  The states and weights of replicas 0, 63, 64, 65
+    and 129, the stop rounds, the violations and best() of all 130 against their oracles.  never_playing: variables with
+    a unary constraint only, counted in viol_base[r], which differs among the replicas of index 64 and above."""
+    g = small_hard() if name == "small_hard" else scaled(stars_paths_unaries(83))
+
+    def base_differs(oras, done):                 # (the oracle side) viol_base[0] for every replica would be seen
+        if name == "never_playing":
+            base = [lone_unary_violations(g, oras[r].state()["idx"], 1000) for r in range(130)]
+            assert never_playing(g) and len(set(base[64:])) > 1 and any(b != base[0] for b in base[64:]), base
+
+    eng, starts, stops, viols = compare_replicas(g, Params(), SMALL_KW, 130, lib_path=lib_path, steps=(0, 1, 3, 8),
+                                                 states=BEYOND_64, each_step=base_differs)
+    eng.close()
+    assert len(set(viols[r] for r in range(64, 130))) > 1           # (the oracle side: the counts past 64 differ)
+
+
+def test_the_top_of_the_replica_range(lib_path):
+    """4096 replicas of 12 variables: replicas 0, 64 and 4095 against their oracles; every replica's violation count
+    against count_violations of its own state, best() against the ranking of those counts and the stop rounds"""
+    g, R, check = small_hard(), 4096, (0, 64, 4095)
+    with DbaEngine(g, Params(), seed=5, replicas=R, stop="each", lib_path=lib_path, **SMALL_KW) as eng:
+        oras = {r: OracleDba(g, Params(), seed=5 + r, **SMALL_KW) for r in check}
+        done = 0
+        for n in (0, 1, 3):
+            eng.run(n)
+            done += n
+            for o in oras.values():
+                o.run(n)
+            same_state(eng, oras, f"after {done} rounds")
+            same_run(eng, oras, R, 1000, f"after {done} rounds")
+            states = [eng.state(r)["idx"] for r in range(R)]
+            counts = [count_violations(g, idx, 1000) for idx in states]
+            assert list(eng.violations()) == counts
+            assert len(set(counts)) > 1 and len({s.tobytes() for s in states}) > 64
+            stops = eng.stop_rounds
+            w, b = ranking(counts, stops), eng.best()
+            assert (b["replica"], b["stop_round"], b["violations"]) == (w, stops[w], counts[w])
+            np.testing.assert_array_equal(b["idx"], states[w])
+
+
+TIE_ROUNDS = 60
+TIE_ORDERS = [([5, 11, 10, 10, 12], [3, 3, 3, 3, 4], [0, 0, 33, 33, 0], 2),     # seeds, violations, stops, the winner
+              ([5, 11, 12], [3, 3, 4], [0, 0, 0], 0)]
+
+
+@functools.lru_cache(maxsize=None)
+def tie_oracle(seed):
+    """(violations, stop round, idx) after TIE_ROUNDS rounds on hard_instance(), the oracle's; computed once per seed"""
+    o = OracleDba(hard_instance(), Params(), seed=seed, **HARD_KW)
+    o.run(TIE_ROUNDS)
+    return oracle_violations(o, HARD_KW["infinity"]), o.stop_round, o.state()["idx"].copy()
+
+
+@pytest.mark.parametrize("order", TIE_ORDERS, ids=["stopped_beats_running", "lowest_index"])
+def test_ranking_ties_break_on_the_stop_round_then_the_index(order, lib_path):
+    """Equal violations: a run that stopped beats the running ones at lower indices, of two equal entries the lower
+    index wins; equal on both keys: the lowest index.  A best_of that ignored the stop round would answer 0 twice."""
+    seeds, viol, stops, w = order
+    assert [tie_oracle(s)[0] for s in seeds] == viol and [tie_oracle(s)[1] for s in seeds] == stops
+    assert ranking(viol, stops) == w and viol.count(viol[w]) > 1 and min(viol) == viol[0] == viol[w]
+    with DbaEngine(hard_instance(), Params(), seeds=seeds, replicas=len(seeds), stop="each", lib_path=lib_path,
+                   **HARD_KW) as eng:
+        eng.run(TIE_ROUNDS)
+        assert list(eng.violations()) == viol and eng.stop_rounds == stops
+        b = eng.best()
+        assert (b["replica"], b["stop_round"], b["violations"]) == (w, stops[w], viol[w]), b
+        np.testing.assert_array_equal(b["idx"], tie_oracle(seeds[w])[2])
+
+
+def test_stop_first_with_the_stopper_past_the_first_64_replicas(lib_path):
+    """hard_instance(), seeds 5..70 with seed 30 moved to index 65: 66 replicas, the one that stops first (round 18; the
+    next stops would be rounds 24 and 25) in the second block of 64.  Every block of every replica reads the
+    engine-wide word: all of them complete round 18 and none runs round 19."""
+    g, F, R = hard_instance(), 18, 66
+    seeds = list(range(5, 5 + R))
+    at = seeds.index(30)
+    seeds[at], seeds[R - 1] = seeds[R - 1], seeds[at]
+    oras = [OracleDba(g, Params(), seed=s, **HARD_KW) for s in seeds]
+    for o in oras:
+        o.run(F)
+    o_stops = [o.stop_round for o in oras]
+    assert o_stops == [0] * (R - 1) + [F]                           # (the oracle side: nobody stops before, one then)
+    o_viol = [oracle_violations(o, HARD_KW["infinity"]) for o in oras]
+    w = ranking(o_viol, o_stops)
+    with DbaEngine(g, Params(), seeds=seeds, replicas=R, stop="first", lib_path=lib_path, **HARD_KW) as eng:
+        eng.run(60)
+        for again in (False, True):
+            what = "at the first stop" + " and a further run" * again
+            assert eng.finished and eng.stop_round == F and eng.cycle_count == F, what
+            assert eng.stop_rounds == o_stops and eng.rounds_of == [F] * R, what
+            same_state(eng, dict(enumerate(oras)), what)
+            assert list(eng.violations()) == o_viol, what
+            b = eng.best()
+            assert (b["replica"], b["stop_round"], b["violations"]) == (w, o_stops[w], o_viol[w]), what
+            np.testing.assert_array_equal(b["idx"], oras[w].state()["idx"])
+            eng.run(10)                                             # after the end: nothing
 
 
 def test_refusals(lib_path):

@@ -7,7 +7,11 @@ third block of the thread-per-variable kernels; two or three unequal domain size
 GDBA and DBA (`fuzz_mgm2`, `fuzz_gdba`, `fuzz_dba`), `dpop_instance(seed)` (4..40 variables, sparse, forests,
 one-value variables, the caller's own tree every fourth seed) feeds DPOP (`fuzz_dpop`).  `replica_instance(seed)`
 (local_instance, every third seed 260..520 variables; 1..66 replicas) feeds the replica engines -- DSA, MGM with
-keyed draws, MGM-2 -- with their device costs and their ranking (`fuzz_replicas`).
+keyed draws, MGM-2 -- with their device costs and their ranking (`fuzz_replicas`); `gdba_replica_instance(seed)` and
+`dba_replica_instance(seed)` (the recipes of gdba_instance / dba_instance at those sizes and replica counts, on
+streams of their own) feed GDBA and DBA as replicas: modifier tables, device costs and ranking; weights, both stop
+policies, stop rounds, violations, ranking and the per-replica "no best value" error (`fuzz_gdba_replicas`,
+`fuzz_dba_replicas`).
 `python tests/fuzz_common.py FIRST LAST` runs the seeds FIRST..LAST-1 of every driver on the emulated build;
 tests/test_fuzz_emu.py runs a few of them in the CPU suite, tests/test_gpu_fuzz.py on the GPU."""
 import os
@@ -97,7 +101,8 @@ DPOP_MAX_ENTRIES = 300_000
 GDBA_STREAM = 22                         # of the streams 20..35 tried: every GDBA variant raises a modifier and moves within its two GPU seeds
 DPOP_FACTORS = (0.8, 1.8)                # constraints per variable
 GPU_SEEDS = {"mgm2": range(0, 48), "gdba": range(0, 48), "dba": range(0, 48), "dpop": range(0, 40),
-             "replicas": range(0, 48)}   # tests/test_gpu_fuzz.py
+             "replicas": range(0, 48), "gdba_replicas": range(0, 48),
+             "dba_replicas": range(0, 48)}   # tests/test_gpu_fuzz.py
 
 
 def local_instance(seed, dom_set=LOCAL_DOMS, slots=(0.8, 3.2), stream=20, n_vars=None):
@@ -140,13 +145,13 @@ def mgm2_instance(seed):
     return g, p, kw
 
 
-def gdba_instance(seed):
+def gdba_instance(seed, stream=GDBA_STREAM, n_vars=None):
     """-> (graph, Params, GDBA kwargs): the variant follows the seed, 24 consecutive seeds cover all 24"""
     import itertools
     from gdba_common import dyadic_var_costs
     from gdba_oracle import INCREASE_MODES, MODIFIERS, VIOLATIONS
     mod, vio, inc = list(itertools.product(MODIFIERS, VIOLATIONS, INCREASE_MODES))[seed % 24]
-    g, rng = local_instance(seed, stream=GDBA_STREAM)
+    g, rng = local_instance(seed, stream=stream, n_vars=n_vars)
     p = Params(mode="max" if rng.integers(0, 2) else "min", dtype="f32" if rng.integers(0, 3) == 0 else "f64")
     # the reference sums the variable costs in the order of a Python set: real-valued ones (random_mixed's) only in
     # mode T, as the pinned cases do (gdba_oracle.py, Determinism); dyadic ones or none elsewhere
@@ -174,13 +179,14 @@ def dba_slots(doms, density, infinity):
     return 0.75 * k, 1.25 * k
 
 
-def dba_instance(seed):
+def dba_instance(seed, stream=20, pre_stream=(22,), n_vars=None):
     """-> (graph, Params, DBA kwargs): tables of 0 or c at a drawn violation density; (c, infinity) = (2, 2): an
     eval can EQUAL infinity; (1000, 999.5): ceil(infinity) differs from it"""
-    pre = np.random.default_rng([seed, 22])
+    pre = np.random.default_rng([seed, *pre_stream])
     c, infinity = [(1000.0, 1000), (1000.0, 999.5), (2.0, 2)][int(pre.integers(0, 3))]
     density = float(pre.choice([0.15, 0.5, 0.85]))
-    g, rng = local_instance(seed, DBA_DOMS, slots=lambda doms: dba_slots(doms, density, infinity))
+    g, rng = local_instance(seed, DBA_DOMS, slots=lambda doms: dba_slots(doms, density, infinity), stream=stream,
+                            n_vars=n_vars)
     g.tables = c * (rng.random(g.tables.shape[0]) < density)
     g.var_cost = np.zeros_like(g.var_cost)
     return g, Params(), dict(infinity=infinity, max_distance=int(rng.choice([2, 3, 50])), seed=seed)
@@ -381,8 +387,8 @@ def fuzz_replicas(seed, lib_path):
     from replica_cost_reference import acceptable_winners, check_replica_costs, is_exact
     from replica_shapes_common import ENGINES, same_fields
     g, p, replicas, kws, compared, steps = replica_instance(seed)
-    for name, E in ENGINES.items():
-        kw = kws[name]
+    for name in ("dsa", "mgm", "mgm2"):
+        E, kw = ENGINES[name], kws[name]
         eng = E["engine"](g, p, kw, seed=seed, seeds=[seed + r for r in range(replicas)], replicas=replicas,
                           lib_path=lib_path)
         oras = {r: E["oracle"](g, p, kw, seed + r) for r in compared}
@@ -427,6 +433,191 @@ def replica_summary(seed):
                 ambiguous_winner=len(ok) > 1, compared=compared)
 
 
+# ---- GDBA and DBA as replicas: the recipes of gdba_instance / dba_instance on streams of their own -----------------
+# Picked on the oracles alone, as GDBA_STREAM was, over the 48 GPU seeds.  GDBA, of the streams 40..45: 44 gives 5 seeds
+# with two or more cost blocks and R > 1 (one of them with 66 replicas), 7 seeds with 66 replicas, replicas that start
+# and end apart in 40 of the 40 seeds with R > 1.  DBA, of the streams 40..47: 46 gives 9 seeds with two or more
+# violation blocks and R > 1 (3 of them with 66 replicas), 10 seeds with 66 replicas, 11 seeds whose replicas stop in
+# different rounds or not at all (7 of them under stop="each"), replicas apart in 40 of 40, and 6 seeds of 48 that end
+# early in the "no best value" error (the streams tried gave 6 to 14; the cap is a third of the seeds).
+GDBA_REP_STREAM = 44
+DBA_REP_STREAM = 46
+DBA_STOPS = ("each", "first")            # the stop policy alternates with the seed
+
+
+def replica_shape(seed, stream):
+    """-> (the range of variables or None, R, compared replicas, steps), as replica_instance draws them: every third
+    seed REPLICA_LARGE variables, two replicas compared over fewer rounds; R of REPLICA_COUNTS"""
+    large = seed % 3 == 2
+    replicas = int(np.random.default_rng([seed, stream, 2]).choice(REPLICA_COUNTS))
+    if large:
+        compared = sorted({0, replicas - 1})
+    else:
+        compared = list(range(replicas)) if replicas <= 5 else [0, 1, replicas - 2, replicas - 1]
+    return REPLICA_LARGE if large else None, replicas, compared, REPLICA_STEPS_LARGE if large else STEPS
+
+
+def gdba_replica_instance(seed):
+    """-> (graph, Params, GDBA kwargs, R, compared replicas, steps): gdba_instance's recipe on GDBA_REP_STREAM"""
+    n_vars, replicas, compared, steps = replica_shape(seed, GDBA_REP_STREAM)
+    g, p, kw = gdba_instance(seed, stream=GDBA_REP_STREAM, n_vars=n_vars)
+    del kw["seed"]
+    return g, p, kw, replicas, compared, steps
+
+
+def dba_replica_instance(seed):
+    """-> (graph, Params, DBA kwargs, R, compared replicas, steps, stop policy): dba_instance's recipe on
+    DBA_REP_STREAM"""
+    n_vars, replicas, compared, steps = replica_shape(seed, DBA_REP_STREAM)
+    g, p, kw = dba_instance(seed, stream=DBA_REP_STREAM, pre_stream=(DBA_REP_STREAM, 3), n_vars=n_vars)
+    del kw["seed"]
+    return g, p, kw, replicas, compared, steps, DBA_STOPS[seed % 2]
+
+
+def fuzz_gdba_replicas(seed, lib_path):
+    """GdbaEngine(replicas=R) on gdba_replica_instance(seed), seeds seed + r: EVERY replica's state against its
+    OracleGdba after every step, the stored modifier tables of the compared ones, all device costs against
+    tests/replica_cost_reference.py, best() after track_best(0) against the winner derived from the reference costs"""
+    from gdba_oracle import OracleGdba
+    from gdba_replicas_common import KEYS, n_slots
+    from pydcop_amd.gdba import GdbaEngine
+    from replica_cost_reference import acceptable_winners, check_replica_costs, is_exact
+    g, p, kw, replicas, compared, steps = gdba_replica_instance(seed)
+    seeds = [seed + r for r in range(replicas)]
+    with GdbaEngine(g, p, seeds=seeds, replicas=replicas, lib_path=lib_path, **kw) as eng:
+        oras = [OracleGdba(g, p, seed=s, **kw) for s in seeds]
+        done = 0
+        for n in steps:
+            eng.run(n)
+            done += n
+            for r, o in enumerate(oras):
+                o.run(n)
+                se, so = eng.state(r), o.state()
+                for k in KEYS:
+                    np.testing.assert_array_equal(se[k], so[k], err_msg=f"{k} of replica {r} after {done} rounds")
+            for r in compared:
+                for s in range(n_slots(g)):
+                    np.testing.assert_array_equal(eng.modifiers(s, replica=r), oras[r].modifiers(s),
+                                                  err_msg=f"modifiers of slot {s} of replica {r} after {done} rounds")
+            refs = check_replica_costs(eng, range(replicas))
+        eng.track_best(0)
+        b = eng.best()
+        w, ok = acceptable_winners([refs[r] for r in range(replicas)], p.mode == "max", is_exact(g, p))
+        assert b["replica"] in ok, (b["replica"], w, ok)
+        assert b["violations"] == refs[b["replica"]][1]
+        np.testing.assert_array_equal(b["idx"], refs[b["replica"]][4])
+
+
+def dba_replica_oracles(seed):
+    """The oracles' side of fuzz_dba_replicas(seed), one round at a time; a generator: after every call of `steps` a row
+    dict(rounds, oras, stops, ended, failed) -- the engine's round count after the call, the oracles (one per replica,
+    as they are after the call), their stop rounds, the round in which the engine ended (0: it has not), and
+    {replica: round} of the oracles that raised IndexError in this call ("no best value"; the last row then).
+    stop="each": a replica that stops is frozen, the engine ends once all have stopped.  stop="first": nothing runs
+    after the round in which the first replica stops."""
+    from dba_oracle import OracleDba
+    g, p, kw, replicas, compared, steps, stop = dba_replica_instance(seed)
+    oras = [OracleDba(g, p, seed=seed + r, **kw) for r in range(replicas)]
+    rounds, ended = 0, 0
+    for n in steps:
+        failed = {}
+        for _ in range(n):
+            if ended:
+                break
+            rounds += 1
+            for r, o in enumerate(oras):
+                if r in failed:
+                    continue
+                try:
+                    o.run(1)
+                except IndexError:
+                    failed[r] = rounds
+            stops = [o.stop_round for o in oras]
+            if not failed and (any(stops) if stop == "first" else all(stops)):
+                ended = rounds if stop == "first" else max(stops)
+        yield dict(rounds=ended or rounds, oras=oras, stops=[o.stop_round for o in oras], ended=ended, failed=failed)
+        if failed:
+            break
+
+
+def dba_failure_names(failed, stop):
+    """The replicas the engine's "no best value" error may name: the lowest that has failed by the end of the call.
+    stop="each": every replica runs the whole call whatever the others do, so that is the lowest of `failed`.
+    stop="first": a replica keeps running after its failure, on a state the reference never has, and may stop there,
+    which ends the call for all: the lowest of those that failed up to round j, for any j from the first failure on."""
+    if stop == "each":
+        return {min(failed)}
+    return {min(r for r, k in failed.items() if k <= j) for j in range(min(failed.values()), max(failed.values()) + 1)}
+
+
+def fuzz_dba_replicas(seed, lib_path):
+    """DbaEngine(replicas=R, stop=...) on dba_replica_instance(seed), seeds seed + r, an oracle for EVERY replica: the
+    states and weights of the compared ones, the stop rounds, the rounds run, the violations and best() of all after
+    every step.  Where an oracle raises IndexError, the engine returns its "no best value" error in the same run
+    call, naming the lowest replica that has failed by the end of that call (compare_dba_fallible, per replica);
+    everything before that call is compared."""
+    import re
+    import pytest
+    from dba_replicas_common import oracle_violations, ranking, same_state
+    from pydcop_amd.dba import DbaEngine
+    from pydcop_amd.engine import MaxSumGpuError
+    g, p, kw, replicas, compared, steps, stop = dba_replica_instance(seed)
+    with DbaEngine(g, p, seeds=[seed + r for r in range(replicas)], replicas=replicas, stop=stop, lib_path=lib_path,
+                   **kw) as eng:
+        for n, row in zip(steps, dba_replica_oracles(seed)):
+            oras = row["oras"]
+            if row["failed"]:
+                with pytest.raises(MaxSumGpuError, match="no best value") as err:
+                    eng.run(n)
+                named = int(re.search(r"\(replica (\d+)\)", str(err.value)).group(1))
+                assert named in dba_failure_names(row["failed"], stop), (named, row["failed"], stop)
+                return
+            eng.run(n)
+            what = f"after {row['rounds']} rounds ({stop})"
+            ran = [row["rounds"] if stop == "first" or not s else s for s in row["stops"]]
+            assert [o.cycle_count for o in oras] == ran, what
+            ended = row["ended"]
+            assert (eng.finished, eng.stop_round, eng.cycle_count) == (bool(ended), ended, row["rounds"]), what
+            assert (eng.stop_rounds, eng.rounds_of) == (row["stops"], ran), what
+            same_state(eng, {r: oras[r] for r in compared}, what)
+            viol = [oracle_violations(o, kw["infinity"]) for o in oras]
+            assert list(eng.violations()) == viol, what
+            w, b = ranking(viol, row["stops"]), eng.best()
+            assert (b["replica"], b["stop_round"], b["violations"]) == (w, row["stops"][w], viol[w]), what
+            np.testing.assert_array_equal(b["idx"], oras[w].state()["idx"], err_msg=f"best() {what}")
+
+
+def gdba_replica_summary(seed):
+    """what the oracles alone show of fuzz_gdba_replicas(seed)"""
+    from gdba_oracle import OracleGdba
+    from replica_cost_reference import CHUNK
+    g, p, kw, replicas, compared, steps = gdba_replica_instance(seed)
+    starts, finals = [], []
+    for r in range(replicas):
+        o = OracleGdba(g, p, seed=seed + r, **kw)
+        starts.append(o.state()["idx"].copy())
+        o.run(sum(steps))
+        finals.append(o.state()["idx"].copy())
+    return dict(blocks=-(-(g.n_factors + g.n_vars) // CHUNK), replicas=replicas, n_vars=g.n_vars,
+                start_apart=any((s != starts[0]).any() for s in starts),
+                end_apart=any((f != finals[0]).any() for f in finals))
+
+
+def dba_replica_summary(seed):
+    """what the oracles alone show of fuzz_dba_replicas(seed)"""
+    g, p, kw, replicas, compared, steps, stop = dba_replica_instance(seed)
+    assert steps[0] == 0
+    starts = None
+    for last in dba_replica_oracles(seed):
+        if starts is None:                  # (the first call runs no round)
+            starts = [o.state()["idx"].copy() for o in last["oras"]]
+    finals = [o.state()["idx"] for o in last["oras"]]
+    return dict(blocks=-(-g.n_factors // 1024), replicas=replicas, n_vars=g.n_vars, stop=stop,
+                failed=bool(last["failed"]), mixed_stops=len(set(last["stops"])) > 1, ended=last["ended"],
+                start_apart=any((s != starts[0]).any() for s in starts),
+                end_apart=any((f != finals[0]).any() for f in finals))
+
+
 # ---- what the oracles alone show of the sweep (tests/test_fuzz_emu.py asserts that it is not vacuous) ----
 def oracle_summary(engine, seed, steps=STEPS):
     from dba_oracle import OracleDba
@@ -435,6 +626,10 @@ def oracle_summary(engine, seed, steps=STEPS):
     from mgm2_oracle import OracleMgm2
     if engine == "replicas":
         return replica_summary(seed)
+    if engine == "gdba_replicas":
+        return gdba_replica_summary(seed)
+    if engine == "dba_replicas":
+        return dba_replica_summary(seed)
     if engine == "dba":
         g, p, kw = dba_instance(seed)
         o, failed = OracleDba(g, p, **kw), False
@@ -473,7 +668,8 @@ def small_seeds(make, n=5, max_vars=20, ok=lambda *inst: True):
     return out
 
 
-DRIVERS = (fuzz_maxsum, fuzz_others, fuzz_mgm2, fuzz_gdba, fuzz_dba, fuzz_dpop, fuzz_replicas)
+DRIVERS = (fuzz_maxsum, fuzz_others, fuzz_mgm2, fuzz_gdba, fuzz_dba, fuzz_dpop, fuzz_replicas, fuzz_gdba_replicas,
+           fuzz_dba_replicas)
 
 
 if __name__ == "__main__":

@@ -1,21 +1,26 @@
-"""The replica engines (DsaEngine, MgmEngine(draws="keyed"), Mgm2Engine with replicas=R) at the shapes where a launch
-spans several blocks per replica: two and three blocks of k_cost_partial (1024 items each), a second and a third block
+"""The replica engines (DsaEngine, MgmEngine(draws="keyed"), Mgm2Engine, GdbaEngine with replicas=R) at the shapes where a
+launch spans several blocks per replica: two and three blocks of k_cost_partial (1024 items each), a second and a third block
 of k_cost_final (64 replicas each), init and snapshot kernels over more than 256 variables, the packed and the
 thread-per-variable kernels of one cycle with different numbers of blocks per replica, the top of the replica range.
-Replica r is bit for bit its single-seed oracle; every replica's device cost is checked against the plain Python sum
-of tests/replica_cost_reference.py; ranking ties break on the lowest index.  The test functions live here, below the
+Replica r is bit for bit its single-seed oracle (GDBA: its stored modifier tables too, so that the pool
+[replicas][n_pool] is read at several blocks per replica as well); every replica's device cost is checked against the
+plain Python sum of tests/replica_cost_reference.py; ranking ties break on the lowest index; GDBA's best-state records
+of replicas past the first block of k_cost_final.  The test functions live here, below the
 helpers; tests/test_replica_shapes_emu.py (emulated build: blocks one after another) and
 tests/test_gpu_replica_shapes.py (the HIP library: a real grid) import them and provide the `lib_path` fixture."""
 import numpy as np
 import pytest
 
 import dsa_replicas_common as dsar
+import gdba_replicas_common as gdbar
 import mgm2_replicas_common as mgm2r
 import mgm_replicas_common as mgmr
+from gdba_oracle import OracleGdba
 from mgm2_oracle import OracleMgm2
 from mgm_keyed_oracle import OracleMgmKeyed
 from pydcop_amd import generators as G
 from pydcop_amd.dsa import DsaEngine
+from pydcop_amd.gdba import GdbaEngine
 from pydcop_amd.graph import Params
 from pydcop_amd.mgm import MgmEngine
 from pydcop_amd.mgm2 import Mgm2Engine
@@ -28,7 +33,9 @@ STEPS = (0, 1, 3)            # compared after rounds 0, 1 and 4, then after rese
 RESET_ROUNDS = 2
 
 
-# ---- the three engines under one face: engine, single-seed oracle, the fields compared bit for bit
+# ---- the engines under one face: engine, single-seed oracle, the fields compared bit for bit; "tracked": best() is
+# the tracker's (track_best(0, infinity) first), else the ranking of the current states (best(infinity)); "tables":
+# the stored modifier tables of every slot are compared too; "tie_kw": the engine's keywords in the tie test
 
 def dsa_oracle(g, p, kw, seed):
     from oracle.dsa_oracle import OracleDsa
@@ -42,7 +49,7 @@ def dsa_fields(x):
 
 ENGINES = {
     "dsa": dict(engine=lambda g, p, kw, **rep: DsaEngine(g, p, **kw, **rep), oracle=dsa_oracle,
-                fields=lambda eng, r: dsa_fields(eng.assignment(r)), ora_fields=dsa_fields, kw="dsa"),
+                fields=lambda eng, r: dsa_fields(eng.assignment(r)), ora_fields=dsa_fields, kw="dsa", tracked=True),
     "mgm": dict(engine=lambda g, p, kw, **rep: MgmEngine(g, p, draws="keyed", **rep),
                 oracle=lambda g, p, kw, seed: OracleMgmKeyed(g, p, draws="keyed", seed=seed),
                 fields=lambda eng, r: {k: eng.state(r)[k] for k in mgmr.KEYS},
@@ -51,7 +58,14 @@ ENGINES = {
                  oracle=lambda g, p, kw, seed: OracleMgm2(g, p, seed=seed, **kw),
                  fields=lambda eng, r: {k: eng.state(r)[k] for k in mgm2r.KEYS},
                  ora_fields=lambda o: {k: o.state()[k] for k in mgm2r.KEYS}, kw="mgm2"),
+    "gdba": dict(engine=lambda g, p, kw, **rep: GdbaEngine(g, p, **kw, **rep),
+                 oracle=lambda g, p, kw, seed: OracleGdba(g, p, seed=seed, **kw),
+                 fields=lambda eng, r: {k: eng.state(r)[k] for k in gdbar.KEYS},
+                 ora_fields=lambda o: {k: o.state()[k] for k in gdbar.KEYS}, kw="gdba", tracked=True, tables=True,
+                 tie_kw=dict(modifier="A", violation="NZ", increase_mode="T")),
 }
+# GDBA once more with the second keyword set of a case (stored tables: pool [replicas][n_pool])
+ENGINES["gdba_stored"] = dict(ENGINES["gdba"], kw="gdba_stored")
 
 
 def same_fields(E, eng, oras, what):
@@ -59,6 +73,10 @@ def same_fields(E, eng, oras, what):
         got, want = E["fields"](eng, r), E["ora_fields"](ora)
         for k in want:
             np.testing.assert_array_equal(got[k], want[k], err_msg=f"{k} of replica {r} {what}")
+        if E.get("tables"):
+            for s in range(gdbar.n_slots(ora.graph)):
+                np.testing.assert_array_equal(eng.modifiers(s, replica=r), ora.modifiers(s),
+                                              err_msg=f"modifiers of slot {s} of replica {r} {what}")
 
 
 def eval_costs_instance():
@@ -76,24 +94,33 @@ def small_hard():
     return G.random_coloring(12, seed=31, variant="hard")
 
 
-# id -> (instance, Params kwargs, {"dsa": DSA kwargs, "mgm2": MGM-2 kwargs}, infinity, R, compared replicas or None =
-# all, kind, environment, engines); kind: "float" real-valued tables, "hard" 0 / 1000 tables, "costs" integer tables
-# and real-valued variable costs
-ALL = ("dsa", "mgm", "mgm2")
+# id -> (instance, Params kwargs, {"dsa": DSA kwargs, "mgm2": MGM-2 kwargs, "gdba", "gdba_stored": GDBA kwargs}, infinity,
+# R, compared replicas or None = all, kind, environment, engines); kind: "float" real-valued tables, "hard" 0 / 1000
+# tables, "costs" integer tables and real-valued variable costs.
+# GDBA: increase mode T wherever the instance has real-valued variable costs (the reference sums them in set order in the
+# other modes: gdba_oracle.py, Determinism); on the instance without any a second run with stored tables.  GDBA has no
+# $MAXSUM_LOCAL_SEARCH_GENERIC path (gdba.h reads no environment): the two forced cases stay DSA's and MGM's.
+ALL = ("dsa", "mgm", "mgm2", "gdba")
+GDBA_T = dict(modifier="A", violation="NZ", increase_mode="T")
+GDBA_KW = {"gdba": GDBA_T}
 CASES = {
     # 1350 items: the second cost block holds 326; 2 init blocks, 8 blocks of the thread-per-variable kernels
-    "two_cost_blocks": (two_cost_blocks, {}, {}, INF, 3, None, "costs", {}, ALL),
+    "two_cost_blocks": (two_cost_blocks, {}, GDBA_KW, INF, 3, None, "costs", {}, ALL),
     # 2100 items: 3 partials, the third of variables alone; violations exact, the cost exactly 0
-    "three_cost_blocks_hard": (lambda: G.random_coloring(700, seed=32, variant="hard", unary_noise=0), {}, {}, 1000.0, 2,
-                               None, "hard", {}, ALL),
+    # (GDBA with stored tables: 2800 slots of 9 entries, 25200 pool entries per replica)
+    "three_cost_blocks_hard": (lambda: G.random_coloring(700, seed=32, variant="hard", unary_noise=0), {},
+                               {"gdba": dict(modifier="M", violation="NM", increase_mode="T"),
+                                "gdba_stored": dict(modifier="M", violation="NZ", increase_mode="E")}, 1000.0, 2,
+                               None, "hard", {}, ALL + ("gdba_stored",)),
     # 1100 items, tables that are not f32-exact; packed and rest kernels, each with its own blocks per replica
     "mixed_f32_max": (lambda: G.random_mixed(300, 800, seed=34, dom_choices=(2, 3, 4)), {"mode": "max", "dtype": "f32"},
-                      {"dsa": dict(p_mode="arity")}, INF, 3, None, "float", {}, ALL),
-    "eval_var_cost": (eval_costs_instance, {"mode": "max"}, {}, INF, 2, None, "costs", {}, ALL),
+                      {"dsa": dict(p_mode="arity"), "gdba": dict(modifier="M", violation="NM", increase_mode="T")}, INF, 3, None,
+                      "float", {}, ALL),
+    "eval_var_cost": (eval_costs_instance, {"mode": "max"}, GDBA_KW, INF, 2, None, "costs", {}, ALL),
     # a second and a third block of k_cost_final
-    "many_replicas": (small_hard, {}, {}, 1000.0, 130, (0, 63, 64, 65, 129), "hard", {}, ALL),
+    "many_replicas": (small_hard, {}, GDBA_KW, 1000.0, 130, (0, 63, 64, 65, 129), "hard", {}, ALL),
     # the top of the replica range
-    "replica_limit": (small_hard, {}, {}, 1000.0, 4096, (0, 64, 4095), "hard", {}, ALL),
+    "replica_limit": (small_hard, {}, GDBA_KW, 1000.0, 4096, (0, 64, 4095), "hard", {}, ALL),
     # the slot and the CSR-walk kernels at several blocks per replica
     "forced_generic_1": (two_cost_blocks, {}, {}, INF, 2, None, "costs", {GENERIC: "1"}, ("dsa", "mgm")),
     "forced_generic_2": (two_cost_blocks, {}, {}, INF, 2, None, "costs", {GENERIC: "2"}, ("dsa", "mgm")),
@@ -140,9 +167,9 @@ def compare_shape(name, engine, lib_path):
         same_fields(E, eng, oras, f"after {done} rounds")
         refs = check_all_costs(eng, graph, params, infinity, kind, check)
     if name == LIMIT:
-        if engine == "dsa":
+        if E.get("tracked"):
             eng.track_best(0, infinity)
-        b = eng.best() if engine == "dsa" else eng.best(infinity)
+        b = eng.best() if E.get("tracked") else eng.best(infinity)
         w, ok = acceptable_winners([refs[r] for r in range(replicas)], params.mode == "max", is_exact(graph, params))
         assert b["replica"] in ok, (b["replica"], w, ok)
         np.testing.assert_array_equal(b["idx"], refs[b["replica"]][4])
@@ -196,7 +223,7 @@ def tie_seeds(finals_of_seed, is_max):
 
 def compare_ties(engine, mode, lib_path):
     E, infinity = ENGINES[engine], 1000.0
-    graph, params, kw = tie_instance(), Params(mode=mode), {}
+    graph, params, kw = tie_instance(), Params(mode=mode), E.get("tie_kw", {})
     is_max = mode == "max"
     by_seed = {}
     for s in TIE_SEEDS:
@@ -210,11 +237,13 @@ def compare_ties(engine, mode, lib_path):
     finals = [by_seed[s] for s in seeds]
     w = dsar.winner(finals, is_max)
     assert w == 1 and finals[1][:2] == finals[3][:2] and dsar.better(finals[1], finals[0], is_max)
+    if engine == "gdba":             # (measured on the oracle, A / NZ / T)
+        assert [f[0] for f in finals] == {"min": [7, 4, 6, 4, 6], "max": [38, 27, 32, 27, 32]}[mode]
     with E["engine"](graph, params, kw, seeds=seeds, replicas=len(seeds), lib_path=lib_path) as eng:
         eng.run(TIE_ROUNDS)
         cost, viol = eng.replica_costs(infinity)
         assert [(int(v), float(c)) for v, c in zip(viol, cost)] == [f[:2] for f in finals]
-        if engine == "dsa":
+        if E.get("tracked"):
             eng.track_best(0, infinity)
             b = eng.best()
         else:
@@ -285,7 +314,66 @@ def test_tracked_run_with_three_different_blocks_per_replica(forced, oracle_buil
             ora.close()
 
 
+RECORD_ROUNDS = 12
+
+
+def reference_records(graph, params, kw, seeds, rounds, infinity):
+    """Per seed, from the oracle's states and reference_cost alone: the record (violations, cost, round, idx, sum of the
+    items' magnitudes) of a run stepped one round at a time, replaced on strict improvement only; the final
+    (violations, cost, idx); and whether every decision was clear -- two states of as many violations and different costs lie further apart than their two
+    bounds, so that a sum in another order decides the same way."""
+    is_max, exact = params.mode == "max", is_exact(graph, params)
+    records, finals, clear = [], [], True
+    for s in seeds:
+        ora, rec = OracleGdba(graph, params, seed=s, **kw), None
+        for c in range(rounds + 1):
+            if c:
+                ora.run(1)
+            idx = ora.state()["idx"].copy()
+            cost, viol, sum_abs, items = reference_cost(graph, params, idx, infinity)
+            if rec is not None and not exact and viol == rec[0] and cost != rec[1]:
+                clear = clear and abs(cost - rec[1]) > 2.0 * cost_bound(items, max(sum_abs, rec[4]))
+            if rec is None or dsar.better((viol, cost), rec[:2], is_max):
+                rec = (viol, cost, c, idx, sum_abs)
+        records.append(rec)
+        finals.append((viol, cost, idx))
+        ora.close()
+    return records, finals, clear
+
+
+def test_gdba_best_state_records_beyond_the_first_block_of_the_final_reduction(lib_path):
+    """130 replicas of small_hard() under track_best(1), 12 rounds: the `improved` flag and the record of a replica
+    index of 64 or more (the second and third block of k_cost_final).  The records of replicas 0, 63, 64, 65 and 129,
+    and best() against the winner over the records of all 130, derived from the oracle's states and reference_cost.
+    Violations, round and snapshot are compared exactly; the cost to cost_bound (small_hard() has real-valued variable
+    costs, which the device adds in its own order; exactly where is_exact).  M / NM / T, seeds 5..134; measured on
+    the oracle: the records of replicas 63, 65 and 129 are of rounds 6, 9 and 2 and differ from the final states, 93 of
+    the 130 records do."""
+    graph, params, kw, inf, R = small_hard(), Params(), gdbar.BEST_KW, 1000.0, 130
+    seeds, compared = [5 + r for r in range(R)], (0, 63, 64, 65, 129)
+    records, finals, clear = reference_records(graph, params, kw, seeds, RECORD_ROUNDS, inf)
+    assert clear, "a record's replacement hangs on a difference within the bound"
+    # the oracle side: the final state returned as the record would be seen
+    early = [r for r in compared if records[r][2] < RECORD_ROUNDS and (records[r][3] != finals[r][2]).any()]
+    assert len(early) >= 2 and any(r >= 64 for r in early), early
+    n, exact = graph.n_factors + graph.n_vars, is_exact(graph, params)
+    bound = [0.0 if exact else cost_bound(n, rec[4]) for rec in records]
+    w = dsar.winner(records, False)
+    rivals = [r for r in range(R) if r != w and records[r][0] == records[w][0]
+              and abs(records[r][1] - records[w][1]) <= 2.0 * (bound[r] + bound[w]) and (records[r][3] != records[w][3]).any()]
+    assert not rivals, f"the winner {w} is not clear of {rivals}"
+    with GdbaEngine(graph, params, seeds=seeds, replicas=R, lib_path=lib_path, **kw) as eng:
+        eng.track_best(1, inf)
+        eng.run(RECORD_ROUNDS)
+        for asked, r in [(r, r) for r in compared] + [(-1, w)]:        # (-1: the best replica's record)
+            viol, cost, rnd, idx, _ = records[r]
+            b = eng.best(asked)
+            assert (b["replica"], b["violations"], b["cycle"]) == (r, viol, rnd), (asked, b, viol, cost, rnd)
+            assert abs(b["cost"] - cost) <= bound[r], (asked, b["cost"], cost, bound[r])
+            np.testing.assert_array_equal(b["idx"], idx, err_msg=f"snapshot of replica {r}")
+
+
 @pytest.mark.parametrize("mode", ["min", "max"])
-@pytest.mark.parametrize("engine", ["dsa", "mgm", "mgm2"])
+@pytest.mark.parametrize("engine", ["dsa", "mgm", "mgm2", "gdba"])
 def test_ranking_ties_break_on_the_lowest_index(engine, mode, oracle_built, lib_path):
     compare_ties(engine, mode, lib_path)

@@ -2,7 +2,8 @@
 oracles, bit for bit): the Max-Sum sweep, asynchronous Max-Sum, DSA and MGM on domains 1..17, arities 1..4,
 every mode / precision / start / damping choice; MGM-2, GDBA, DBA and DPOP on the instances of
 `local_instance` / `dpop_instance` and on every constructed instance of tests/edge_shapes.py; the replica engines
-(DSA, MGM with keyed draws, MGM-2: replicas, device costs, ranking) on those of `replica_instance`; and what the
+(DSA, MGM with keyed draws, MGM-2: replicas, device costs, ranking) on those of `replica_instance`, GDBA and DBA as
+replicas on those of `gdba_replica_instance` / `dba_replica_instance`; and what the
 oracles alone must show over the seeds of tests/test_gpu_fuzz.py for that sweep to prove anything."""
 import pytest
 
@@ -62,6 +63,16 @@ def test_fuzz_dpop_emu(seed, emu_lib):
 @pytest.mark.parametrize("seed", range(0, 12))
 def test_fuzz_replicas_emu(seed, emu_lib, oracle_built):
     fuzz_common.fuzz_replicas(seed, emu_lib)
+
+
+@pytest.mark.parametrize("seed", range(0, 12))
+def test_fuzz_gdba_replicas_emu(seed, emu_lib):
+    fuzz_common.fuzz_gdba_replicas(seed, emu_lib)
+
+
+@pytest.mark.parametrize("seed", range(0, 12))
+def test_fuzz_dba_replicas_emu(seed, emu_lib):
+    fuzz_common.fuzz_dba_replicas(seed, emu_lib)
 
 
 @pytest.mark.parametrize("edge", edge_shapes.all_edges(), ids=lambda e: e[0])
@@ -128,6 +139,26 @@ def test_the_sweep_is_not_vacuous(engine, oracle_built):
         assert 2 * len(apart) >= len([r for r in rows if r["replicas"] > 1])
         assert 10 * len(ambiguous) < n
         assert {r["replicas"] for r in rows} == set(fuzz_common.REPLICA_COUNTS)
+    elif engine in ("gdba_replicas", "dba_replicas"):
+        multi = [r for r in rows if r["replicas"] > 1]
+        blocks = [s for s, r in zip(seeds, rows) if r["blocks"] >= 2 and r["replicas"] > 1]
+        many = [s for s, r in zip(seeds, rows) if r["replicas"] == 66]
+        apart = [s for s, r in zip(seeds, rows) if r["replicas"] > 1 and r["start_apart"] and r["end_apart"]]
+        print(f"{engine}: {len(blocks)} of {n} seeds with two or more blocks of the reduction and R > 1 {blocks}, "
+              f"{len(many)} with 66 replicas {many}, {len(apart)} of {len(multi)} with R > 1 whose replicas start apart "
+              f"and end apart")
+        assert blocks and many and 2 * len(apart) >= len(multi)
+        assert len([s for s in seeds if rows[s - seeds[0]]["n_vars"] >= 260]) == len([s for s in seeds if s % 3 == 2])
+        assert {r["replicas"] for r in rows} == set(fuzz_common.REPLICA_COUNTS)
+        if engine == "dba_replicas":
+            mixed = [s for s, r in zip(seeds, rows) if r["mixed_stops"]]
+            mixed_each = [s for s, r in zip(seeds, rows) if r["mixed_stops"] and r["stop"] == "each"]
+            failed = [s for s, r in zip(seeds, rows) if r["failed"]]
+            print(f"dba_replicas: {len(mixed)} seeds whose replicas stop in different rounds or not at all {mixed} "
+                  f"({len(mixed_each)} under stop='each'), {len(failed)} end early in the 'no best value' error {failed}")
+            assert mixed and mixed_each
+            assert {r["stop"] for r in rows if r["ended"]} == set(fuzz_common.DBA_STOPS)    # both policies end an engine
+            assert failed and 3 * len(failed) <= n
     else:
         wide = sum(r["widest"] >= 2 for r in rows)
         ones = sum(r["one_value_in_separator"] for r in rows)

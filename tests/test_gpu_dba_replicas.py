@@ -14,6 +14,12 @@ from dba_replicas_common import (  # noqa: F401  (collected here)
     test_explicit_seeds,
     test_one_replica_equals_the_single_run_engine,
     test_violations_include_a_variable_that_never_plays,
+    test_violation_partials_of_several_blocks,
+    test_wide_domains_at_two_blocks_per_replica,
+    test_more_than_64_replicas,
+    test_the_top_of_the_replica_range,
+    test_ranking_ties_break_on_the_stop_round_then_the_index,
+    test_stop_first_with_the_stopper_past_the_first_64_replicas,
     test_refusals)
 
 pytestmark = pytest.mark.gpu

@@ -2,9 +2,9 @@
 sweep, asynchronous Max-Sum, DSA, MGM, MGM-2, GDBA, DBA, DPOP) against its oracle, bit for bit, on
 instances nobody picked (domains 1..17, arities 1..4, every mode / precision / start / damping choice,
 random layout flags; for the four newer engines up to 200 variables, unequal neighbour domains up to 65
-values and every algorithm parameter; DSA, MGM with keyed draws and MGM-2 as 1..66 replicas of one engine on up
-to 520 variables, with their device costs and their ranking), and the constructed edge instances of
-tests/edge_shapes.py."""
+values and every algorithm parameter; DSA, MGM with keyed draws, MGM-2, GDBA and DBA as 1..66 replicas of one
+engine on up to 520 variables, with their device costs or violation counts and their ranking, DBA under both stop
+policies), and the constructed edge instances of tests/edge_shapes.py."""
 import pytest
 
 import edge_shapes
@@ -55,6 +55,16 @@ def test_fuzz_dpop(seed):
 @pytest.mark.parametrize("seed", fuzz_common.GPU_SEEDS["replicas"])
 def test_fuzz_replicas(seed, oracle_built):
     fuzz_common.fuzz_replicas(seed, None)
+
+
+@pytest.mark.parametrize("seed", fuzz_common.GPU_SEEDS["gdba_replicas"])
+def test_fuzz_gdba_replicas(seed):
+    fuzz_common.fuzz_gdba_replicas(seed, None)
+
+
+@pytest.mark.parametrize("seed", fuzz_common.GPU_SEEDS["dba_replicas"])
+def test_fuzz_dba_replicas(seed):
+    fuzz_common.fuzz_dba_replicas(seed, None)
 
 
 @pytest.mark.parametrize("edge", edge_shapes.all_edges(), ids=lambda e: e[0])

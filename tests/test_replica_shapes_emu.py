@@ -7,6 +7,7 @@ from replica_shapes_common import (  # noqa: F401  (collected here)
     test_replicas_equal_their_oracles_at_several_blocks,
     test_best_state_snapshots_span_blocks,
     test_tracked_run_with_three_different_blocks_per_replica,
+    test_gdba_best_state_records_beyond_the_first_block_of_the_final_reduction,
     test_ranking_ties_break_on_the_lowest_index)
 
 
