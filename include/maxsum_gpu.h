@@ -410,6 +410,10 @@ int mxs_peer_connect(mxs_engine *e, const mxs_peer_info *all /* [world] */);
  *                    slower than the two-launch schedule). */
 int mxs_shard_mode(const mxs_engine *e, int32_t *fused_launch, int32_t *direct_exchange);
 
+/* BEST STATE and COST TRACE: the best assignment a run has passed through and its cost-versus-cycle curve, kept on
+ * the device (track_best, get_best, get_cost_trace), are declared and documented in maxsum_gpu_anytime.h. */
+#include "maxsum_gpu_anytime.h"
+
 int mxs_destroy(mxs_engine *e);
 
 /* Message of the last error on this thread ("" if none). */

@@ -23,7 +23,7 @@ from pydcop_amd.algorithms.maxsum_gpu import (MaxSumGpuFactorComputation, MaxSum
 
 GRAPH_TYPE = "factor_graph"
 
-algo_params = [p for p in _base.algo_params if p.name != "devices"]
+algo_params = [p for p in _base.algo_params if p.name not in ("devices", "best_every")]   # (one GPU; no record kept)
 
 
 class _GenerationEngine:

@@ -28,6 +28,15 @@ Extra parameters
               k > 1 runs `pydcop_amd.sharded.LocalShardedMaxSum` -- one engine per GPU,
               boundary V->F messages exchanged once per cycle by the engines' own RCCL
               all-to-all -- and gives the same result as one GPU
+  best_every  int, default 0   k > 0: the engine keeps, on the device, the best assignment seen at cycle 0 and
+                               after every k-th cycle (fewest entries equal to infinity, then the solution cost;
+                               `MaxSumEngine.track_best`): Max-Sum on a loopy graph is not monotone, its last
+                               assignment is usually not its best.  The values the variable proxies report are
+                               then the record's -- the last report, at `stop_cycle`, is the best state of the
+                               run; the cost published beside a value stays the variable's CURRENT belief (the
+                               engine keeps no snapshot of those).  The module has no `infinity` parameter (the
+                               orchestrator applies its own to the values it collects): every table entry is a
+                               cost.  One device only: with `devices` > 1 it raises ValueError
 
 Only thread mode with all computations in one process can be served (the whole
 graph must be visible to one engine); anything else raises ComputationException.
@@ -64,6 +73,7 @@ algo_params = [
     AlgoParameterDef("seed", "int", None, 0),
     AlgoParameterDef("chunk", "int", None, 10),
     AlgoParameterDef("devices", "int", None, 1),
+    AlgoParameterDef("best_every", "int", None, 0),
 ]
 
 def computation_memory(computation: Union[FactorComputationNode, VariableComputationNode]) -> float:
@@ -107,6 +117,7 @@ class _Session:
         self.done = False
         self.stopped = False
         self.error: Optional[Exception] = None
+        self.best_every = 0    # > 0: the reported values are the engine's best record (maxsum_gpu only)
 
     def register(self, comp_def: ComputationDef):
         with self.lock:
@@ -154,6 +165,11 @@ class _Session:
     def _make_engine(self, params, p):
         """The engine of this kind of session (amaxsum_gpu overrides it)."""
         n_dev = int(p.get("devices", 1) or 1)
+        best_every = int(p.get("best_every", 0) or 0)
+        if best_every < 0:
+            raise ValueError("maxsum_gpu: best_every must be at least 0")
+        if best_every > 0 and n_dev > 1:
+            raise ValueError("maxsum_gpu: best_every needs devices:1 (a shard's cost is partial)")
         if n_dev > 1:
             from pydcop_amd.engine import device_count
             from pydcop_amd.sharded import LocalShardedMaxSum
@@ -163,7 +179,16 @@ class _Session:
             return LocalShardedMaxSum(self.graph, params, list(range(n_dev)))
         # (DynamicMaxSum = a MaxSumEngine that survives scope changes of its factors)
         from pydcop_amd.dynamic import DynamicMaxSum
-        return DynamicMaxSum(self.graph, params)
+        if best_every == 0:
+            return DynamicMaxSum(self.graph, params)
+        self.best_every = best_every
+
+        def tracking_engine(graph, prm):   # (a scope change makes a new engine: it tracks too, from the carried state)
+            from pydcop_amd.engine import MaxSumEngine
+            eng = MaxSumEngine(graph, prm)
+            eng.track_best(best_every, float("inf"))
+            return eng
+        return DynamicMaxSum(self.graph, params, engine_factory=tracking_engine)
 
     @property
     def cycles(self) -> int:
@@ -175,6 +200,8 @@ class _Session:
 
     def _fetch(self):
         idx, belief = self.engine.assignment()
+        if self.best_every > 0:          # the record's values; the beliefs stay the current ones
+            idx = self.engine.engine.best()["idx"]
         self.snapshot = (idx, belief, self.engine.cycle_count, self.snapshot[3] + 1)
 
     def advance(self):

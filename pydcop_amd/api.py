@@ -109,8 +109,42 @@ def _check_restarts(algo, restarts, best_every, draws="fixed", dba_stop="first")
                          "with best_every >= 1")
     if dba_stop not in ("first", "each"):
         raise ValueError("dba_stop must be \"first\" or \"each\"")
-    if algo not in ("dsa", "gdba") and int(best_every) != 0:
-        raise ValueError("best_every: algo=\"dsa\" or \"gdba\" only")
+    if algo not in ("dsa", "gdba", "maxsum") and int(best_every) != 0:
+        raise ValueError("best_every: algo=\"dsa\", \"gdba\" or \"maxsum\" only")
+
+
+def _check_maxsum_tracking(algo, cost_every, best_every, devices):
+    """the refusals of algo="maxsum" with best_every, before an engine exists"""
+    if algo != "maxsum" or int(best_every) <= 0:
+        return
+    if int(cost_every) > 0 and int(best_every) != int(cost_every):
+        raise ValueError("maxsum: cost_every and best_every are one evaluation period: give one, or the same value")
+    if devices and int(devices) > 1:
+        raise ValueError("best_every: maxsum on one device only (a shard's cost is partial)")
+
+
+def _maxsum_track(eng, algo, cycles, cost_every, best_every, infinity, devices=1):
+    """algo="maxsum" with cost_every / best_every: switch the engine's device-side tracking on (one evaluation period
+    for both: the record and the curve come from the same evaluations).  -> the period, 0 when there is none."""
+    every = int(best_every) or int(cost_every)
+    if algo != "maxsum" or every <= 0:
+        return 0
+    if devices and int(devices) > 1:
+        return 0                     # (the sharded engine keeps the host loop of _run_and_trace)
+    eng.track_best(every, infinity, trace=int(cycles) // every + 2)
+    return every
+
+
+def _maxsum_result(eng, cycles, cost_every, best_every, infinity):
+    """-> (the curve of the device trace without its cycle-0 entry, or []; (idx, extra keys) of the record, or None)"""
+    cyc, cost, viol, _ = eng.cost_trace()
+    curve = [(int(c), float(x), int(v)) for c, x, v in zip(cyc, cost, viol) if c > 0] if int(cost_every) > 0 else []
+    if int(cost_every) > 0 and int(cycles) % int(cost_every):      # (the curve ends with the last cycle, as ever)
+        curve.append((int(cycles),) + tuple(eng.eval_cost(infinity=infinity)))
+    if int(best_every) <= 0:
+        return curve, None
+    best = eng.best()
+    return curve, (best["idx"], {"best_cycle": best["cycle"]})
 
 
 def _dsa_best(eng, algo, restarts, best_every, infinity):
@@ -183,6 +217,12 @@ def solve_dcop(dcop, cycles: int = 30, *, damping: float = 0.5, damping_nodes: s
     stopped in and "finished" is true; `seed` keys its draws); the local-search
     algorithms take no noise (their variable costs enter as the reference's do).
 
+    algo="maxsum": Max-Sum on a loopy graph is not monotone, its last assignment is usually not its best.
+    `best_every` = k > 0 keeps the best assignment seen at cycle 0 and after every k-th cycle on the device
+    (MaxSumEngine.track_best: fewest violations, then cost): the assignment, cost and violation are then the record's
+    and the result gains "best_cycle".  `cost_every` fills `cost_curve` from the same device trace, in one run call;
+    alone it still reports the final state.  Both given and different: ValueError.  One device only.
+
     Returns {"assignment", "cost", "violation", "cycle", "cost_curve"}: the first three
     as `DCOP.solution_cost` computes them for the selected values; `cost_curve` (when
     `cost_every` > 0) = [(cycle, cost, violations)] evaluated on the device every
@@ -217,6 +257,7 @@ def solve_dcop(dcop, cycles: int = 30, *, damping: float = 0.5, damping_nodes: s
     all have stopped.  The result gains "replica", "replica_violations" and "stop_rounds" (0: that run has not
     stopped); "cycle" is the rounds the engine ran, "finished" whether it has ended.  `best_every` stays refused."""
     _check_restarts(algo, restarts, best_every, draws, dba_stop)
+    _check_maxsum_tracking(algo, cost_every, best_every, devices)
     graph = compile_dcop(dcop, noise=noise if algo in ("maxsum", "amaxsum") else 0.0, seed=seed)
     params = Params(mode=dcop.objective, damping=damping, damping_nodes=damping_nodes,
                     stability=stability, start_messages=start_messages, dtype=precision)
@@ -225,11 +266,14 @@ def solve_dcop(dcop, cycles: int = 30, *, damping: float = 0.5, damping_nodes: s
     with _engine_for(graph, params, device, devices, lib_path, algo, algo_kw) as eng:
         if algo in ("dsa", "gdba") and int(best_every) > 0:
             eng.track_best(int(best_every), infinity)
-        curve = _run_and_trace(eng, algo, cycles, cost_every, infinity)
+        tracked = _maxsum_track(eng, algo, cycles, cost_every, best_every, infinity, devices)
+        curve = _run_and_trace(eng, algo, cycles, 0 if tracked else cost_every, infinity)    # (tracked: ONE run call)
         idx, _ = eng.assignment()
         extra = _dba_end(eng, algo)
         best = (_dsa_best(eng, algo, restarts, best_every, infinity) or _mgm_best(eng, algo, restarts, infinity)
                 or _dba_best(eng, algo, restarts))
+        if tracked:
+            curve, best = _maxsum_result(eng, cycles, cost_every, best_every, infinity)
         if best:
             idx, more = best
             extra.update(more)
@@ -254,16 +298,20 @@ def solve_flat(graph: FlatGraph, objective: str = "min", cycles: int = 30, *, da
     params = Params(mode=objective, damping=damping, damping_nodes=damping_nodes,
                     stability=stability, start_messages=start_messages, dtype=precision)
     _check_restarts(algo, restarts, best_every, draws, dba_stop)
+    _check_maxsum_tracking(algo, cost_every, best_every, devices)
     algo_kw = _algo_kw(algo, variant, probability, p_mode, seed, threshold, favor, modifier, violation, increase_mode,
                        dba_infinity, max_distance, restarts, draws, best_every, dba_stop)
     with _engine_for(graph, params, device, devices, lib_path, algo, algo_kw) as eng:
         if algo in ("dsa", "gdba") and int(best_every) > 0:
             eng.track_best(int(best_every), infinity)
-        curve = _run_and_trace(eng, algo, cycles, cost_every, infinity)
+        tracked = _maxsum_track(eng, algo, cycles, cost_every, best_every, infinity, devices)
+        curve = _run_and_trace(eng, algo, cycles, 0 if tracked else cost_every, infinity)    # (tracked: ONE run call)
         idx, _ = eng.assignment()
         extra = _dba_end(eng, algo)
         best = (_dsa_best(eng, algo, restarts, best_every, infinity) or _mgm_best(eng, algo, restarts, infinity)
                 or _dba_best(eng, algo, restarts))
+        if tracked:
+            curve, best = _maxsum_result(eng, cycles, cost_every, best_every, infinity)
         if best:
             idx, more = best
             extra.update(more)

@@ -25,6 +25,7 @@
 
 #include "../../include/maxsum_gpu.h"
 #include "kernels.h"
+#include "anytime.h"
 #include "nary_box.h"
 #include "bin_box.h"
 #include "small_box.h"
@@ -182,6 +183,12 @@ struct EngineBase {
     virtual int update_table(int32_t factor, const double* table, int64_t n) = 0;
     virtual int set_parent(int32_t factor, const double* parent, int32_t nd, const int32_t* dims, const uint8_t* ext) = 0;
     virtual int slice_factor(int32_t factor, const int32_t* ext_idx) = 0;
+    // best state and cost trace on the device (include/maxsum_gpu_anytime.h)
+    virtual int track_best(int32_t every, double infinity, int32_t trace_cap) = 0;
+    virtual int get_best(int64_t* cycle, double* cost, int64_t* viol, int32_t* idx) = 0;
+    virtual int get_cost_trace(int64_t* cycle, double* cost, int64_t* viol, int32_t cap, int32_t* n, int64_t* evals) = 0;
+    virtual int track_restart() = 0;  // the state or the cost function has changed: the record starts again from here
+    virtual bool tracking() const = 0;
     Layout L;
     mxs_params params{};
     int64_t cycles = 0;
@@ -242,6 +249,18 @@ struct Engine : EngineBase {
     T* recv_buf = nullptr;  // halo_recv) or caller-owned memory (mxs_halo_bind)
     bool halo_ready = false;
     static constexpr int EVAL_BLOCKS = 1024;
+    static_assert(EVAL_BLOCKS <= ANY_MAX_PARTS, "k_any_final stages every partial of k_eval in LDS");
+    // mxs_track_best: the best state and the cost trace, on the device (anytime.h)
+    struct Anytime {
+        bool on = false;
+        int every = 0;         // evaluate after every cycle c with c % every == 0
+        double infinity = 0;
+        int graph_phase = 0;   // cycle count % every at the start of the captured chunk
+        DevBuf<AnyState> st;
+        DevBuf<int32_t> snap;  // [n_vars] internal order
+        DevBuf<long long> tr_cycle, tr_viol;
+        DevBuf<double> tr_cost;
+    } any;
     static constexpr int FUSED_MAX_CUT_BLOCKS = 1024;  // half of the 2048 resident workgroup slots
 
     ~Engine() override {
@@ -872,16 +891,41 @@ struct Engine : EngineBase {
             rc = pack();
             if (rc) return rc;
         }
+        if (any.on) {  // the record and the trace start again: the first record is the start state
+            HIP_TRY(hipMemsetAsync(any.st.p, 0, sizeof(AnyState), stream));
+            rc = launch_track(0);
+            if (rc) return rc;
+        }
         return sync();
     }
 
     // Capture `chunk` (even) cycles into a hipGraph: launch-bound loops replay it.
-    void try_build_graph() {
+    // The cycles a captured chunk holds while tracking: the configured chunk rounded to a multiple of `every` (and of 2,
+    // the parity), 0 where no graph is built (graph_chunk 0, or evaluations more than 256 cycles apart: eager).
+    int tracked_chunk() const {
+        int chunk = params.graph_chunk < 0 ? 32 : params.graph_chunk;
+        if (chunk < 2) return 0;
+        chunk &= ~1;
+        const int64_t unit = any.every % 2 ? 2 * (int64_t)any.every : any.every;
+        if (unit > 256) return 0;
+        return (int)(std::max<int64_t>(1, chunk / unit) * unit);
+    }
+    // is a graph worth capturing for n cycles?  Twice the chunk, as ever; while tracking, twice the REAL chunk
+    bool worth_graph(int n) const {
+        if (any.on) return tracked_chunk() >= 2 && n >= 2 * tracked_chunk();
+        return n >= 2 * std::max(2, params.graph_chunk < 0 ? 32 : params.graph_chunk);
+    }
+    // `at`: the engine's cycle count where the capture starts.  While tracking, the captured chunk is a multiple of
+    // `every` and holds the tracking launches at the positions that follow from `at` (any.graph_phase): a replay is
+    // only started at a cycle count with the same remainder (run_async aligns, as it does for the parity).
+    void try_build_graph(int64_t at) {
         graph_tried = true;
         int chunk = params.graph_chunk;
         if (chunk < 0) chunk = 32;
         if (chunk < 2) return;
         chunk &= ~1;
+        if (any.on) chunk = tracked_chunk();
+        if (chunk < 2) return;
         if (cur != 0) return;  // captured with parity 0; run() aligns first
         hipGraph_t graph = nullptr;
         if (hipStreamBeginCapture(stream, hipStreamCaptureModeThreadLocal) != hipSuccess) {
@@ -894,6 +938,7 @@ struct Engine : EngineBase {
         for (int i = 0; i < chunk && ok; ++i) {
             ok = launch_cycle(from, false) == MXS_OK;
             from ^= 1;
+            if (ok && any.on && (at + i + 1) % any.every == 0) ok = launch_track(-1) == MXS_OK;
         }
         capturing = false;
         if (hipStreamEndCapture(stream, &graph) != hipSuccess || !ok || !graph) {
@@ -906,6 +951,7 @@ struct Engine : EngineBase {
             graph_exec = nullptr;
         } else {
             graph_cycles = chunk;
+            if (any.on) any.graph_phase = (int)(at % any.every);
         }
         (void)hipGraphDestroy(graph);
     }
@@ -916,6 +962,7 @@ struct Engine : EngineBase {
         if (halo_ready)
             return fail(MXS_E_STATE, "a sharded engine must be stepped with mxs_step_compute/pack/unpack");
         int left = n;
+        if (any.on) return run_tracked(n);
         if (left > 0 && cur != 0) {  // align to the parity the graph was captured with
             int rc = launch_cycle(cur, false);
             if (rc) return rc;
@@ -923,7 +970,7 @@ struct Engine : EngineBase {
             --left;
         }
         if (!graph_tried && left >= 2 * std::max(2, params.graph_chunk < 0 ? 32 : params.graph_chunk))
-            try_build_graph();
+            try_build_graph(cycles + (n - left));
         while (graph_exec && left >= graph_cycles) {
             HIP_TRY(hipGraphLaunch(graph_exec, stream));
             left -= graph_cycles;
@@ -934,6 +981,43 @@ struct Engine : EngineBase {
             cur ^= 1;
         }
         cycles += n;
+        return MXS_OK;
+    }
+
+    // run_async while tracking: the same cycles, an evaluation queued behind every cycle c with c % every == 0.
+    // A replay holds its evaluations at fixed places, so it starts only where the parity AND the remainder of the
+    // cycle count are those of the capture; the cycles before that, and the tail, are eager.
+    int run_tracked(int n) {
+        int left = n;
+        int64_t c = cycles;
+        auto eager = [&]() {
+            int rc = launch_cycle(cur, false);
+            if (rc) return rc;
+            cur ^= 1;
+            --left;
+            ++c;
+            return c % any.every == 0 ? launch_track(-1) : (int)MXS_OK;
+        };
+        if (left > 0 && cur != 0) {
+            int rc = eager();
+            if (rc) return rc;
+        }
+        if (!graph_tried && worth_graph(left)) try_build_graph(c);
+        auto aligned = [&]() { return cur == 0 && c % any.every == any.graph_phase; };
+        for (int64_t tries = 2 * (int64_t)any.every; graph_exec && left >= graph_cycles && !aligned() && tries > 0; --tries) {
+            int rc = eager();
+            if (rc) return rc;
+        }
+        while (graph_exec && aligned() && left >= graph_cycles) {
+            HIP_TRY(hipGraphLaunch(graph_exec, stream));
+            left -= graph_cycles;
+            c += graph_cycles;
+        }
+        while (left > 0) {
+            int rc = eager();
+            if (rc) return rc;
+        }
+        cycles = c;
         return MXS_OK;
     }
 
@@ -969,8 +1053,7 @@ struct Engine : EngineBase {
     int run_timed(int n, float* ms) override {
         HIP_TRY(hipSetDevice(device));
         // build the graph outside the timed region
-        if (!graph_tried && cur == 0 && n >= 2 * std::max(2, params.graph_chunk < 0 ? 32 : params.graph_chunk))
-            try_build_graph();
+        if (!graph_tried && cur == 0 && worth_graph(n)) try_build_graph(cycles);
         HIP_TRY(hipEventRecord(ev0, stream));
         int rc = run_async(n);
         if (rc) return rc;
@@ -989,8 +1072,7 @@ struct Engine : EngineBase {
         HIP_TRY(hipSetDevice(device));
         if (n < 1 || reps < 1 || reps > 100000) return fail(MXS_E_INVALID, "mxs_run_reps: n >= 1, 1 <= reps <= 100000");
         if (halo_ready || p2p) return fail(MXS_E_STATE, "mxs_run_reps: not on a sharded engine");
-        if (!graph_tried && cur == 0 && n >= 2 * std::max(2, params.graph_chunk < 0 ? 32 : params.graph_chunk))
-            try_build_graph();
+        if (!graph_tried && cur == 0 && worth_graph(n)) try_build_graph(cycles);
         std::vector<hipEvent_t> evs((size_t)reps + 1, nullptr);
         int rc = MXS_OK;
         hipError_t he = hipSuccess;
@@ -1141,21 +1223,8 @@ struct Engine : EngineBase {
         return MXS_OK;
     }
 
-    int eval_cost(const int32_t* idx, double infinity, double* cost, int64_t* viol) override {
-        HIP_TRY(hipSetDevice(device));
-        { int rc = sync(); if (rc) return rc; }
-        const int nV = L.n_vars;
-        const int32_t* didx = sel.p;
-        if (idx) {
-            std::vector<int32_t> h(nV);
-            for (int vi = 0; vi < nV; ++vi) {
-                const int32_t x = idx[L.var_i2e[vi]];
-                if (x < 0 || x >= L.vdom[vi]) return fail(MXS_E_INVALID, "assignment index out of the domain");
-                h[vi] = x;
-            }
-            HIP_TRY(copy_sync(eval_idx.p, h.data(), sizeof(int32_t) * nV, hipMemcpyHostToDevice, stream));
-            didx = eval_idx.p;
-        }
+    // the one k_eval launch of mxs_eval_cost and of a tracked evaluation: the same arguments, the same grid
+    EvalArgs eval_args(const int32_t* didx, double infinity) const {
         EvalArgs a{};
         a.frowptr = frowptr.p;
         a.edge_var_int = edge_var_int.p;
@@ -1171,10 +1240,128 @@ struct Engine : EngineBase {
         a.part_cost = part_cost.p;
         a.part_viol = part_viol.p;
         a.n_factors = L.n_factors;
-        a.n_vars = nV;
+        a.n_vars = L.n_vars;
         a.infinity = infinity;
-        const int total = L.n_factors + nV;
-        const int nb = std::max(1, std::min(EVAL_BLOCKS, (total + BLOCK - 1) / BLOCK));
+        return a;
+    }
+    int eval_blocks() const {
+        const int total = L.n_factors + L.n_vars;
+        return std::max(1, std::min(EVAL_BLOCKS, (total + BLOCK - 1) / BLOCK));
+    }
+
+    // ---- best state and cost trace (include/maxsum_gpu_anytime.h, anytime.h) ----------------------------------
+    // One evaluation of `sel`, queued on the compute stream with no read-back: k_eval, k_any_final, k_any_copy.
+    // Behind launch_cycle it comes after the join of the wide-variable side stream (k_variable_wide writes `sel`
+    // too) and before the next cycle's sweep; inside a capture it is three more nodes of the one captured stream.
+    // first_cycle >= 0: a first record at that cycle (never captured: the argument is the host's cycle count);
+    // < 0: the periodic evaluation, whose cycle number the device keeps (AnyState::next_cycle) because a
+    // captured graph freezes kernel arguments.
+    int launch_track(long long first_cycle) {
+        const int nb = eval_blocks(), nV = L.n_vars;
+        hipLaunchKernelGGL(k_eval, dim3(nb), dim3(BLOCK), 0, stream, eval_args(sel.p, any.infinity));
+        AnyTrace tr{any.tr_cycle.p, any.tr_cost.p, any.tr_viol.p, (int32_t)any.tr_cycle.n};
+        hipLaunchKernelGGL(k_any_final, dim3(1), dim3(ANY_TPB), 0, stream, nb, L.is_max ? 1 : 0, (const double*)part_cost.p,
+                           (const unsigned long long*)part_viol.p, first_cycle, any.every, any.st.p, tr);
+        hipLaunchKernelGGL(k_any_copy, dim3((unsigned)std::max(1, (nV + ANY_TPB - 1) / ANY_TPB)), dim3(ANY_TPB), 0, stream, nV,
+                           (const int32_t*)sel.p, any.snap.p, any.st.p);
+        HIP_TRY(hipGetLastError());
+        return MXS_OK;
+    }
+    void drop_graph() {  // the captured cycle loop has (or lacks) the tracking launches of the old setting
+        if (graph_exec) {
+            (void)hipGraphExecDestroy(graph_exec);
+            graph_exec = nullptr;
+        }
+        graph_tried = false;
+    }
+    bool tracking() const override { return any.on; }
+    int track_best(int32_t every, double infinity, int32_t trace_cap) override {
+        HIP_TRY(hipSetDevice(device));
+        if (every < 0 || trace_cap < 0) return fail(MXS_E_INVALID, "mxs_track_best: every >= 0 and trace_capacity >= 0");
+        if (halo_ready || nccl_comm || p2p)
+            return fail(MXS_E_STATE, "mxs_track_best: not on a sharded engine (a shard's cost is partial)");
+        { int rc = sync(); if (rc) return rc; }
+        auto release = [](auto& b) {
+            if (b.p) (void)hipFree(b.p);
+            b.p = nullptr;
+            b.n = 0;
+        };
+        if (every == 0) {
+            if (any.on) drop_graph();
+            any.on = false;
+            any.every = 0;
+            release(any.st), release(any.snap), release(any.tr_cycle), release(any.tr_viol), release(any.tr_cost);
+            return MXS_OK;
+        }
+        {   // all the new buffers first: a call that fails leaves the old setting as it was
+            Anytime fresh;
+            HIP_TRY(fresh.st.alloc(1));
+            HIP_TRY(fresh.snap.alloc((size_t)L.n_vars));
+            HIP_TRY(fresh.tr_cycle.alloc((size_t)trace_cap));
+            HIP_TRY(fresh.tr_viol.alloc((size_t)trace_cap));
+            HIP_TRY(fresh.tr_cost.alloc((size_t)trace_cap));
+            auto swap = [](auto& a, auto& b) { std::swap(a.p, b.p); std::swap(a.n, b.n); };
+            swap(any.st, fresh.st), swap(any.snap, fresh.snap), swap(any.tr_cycle, fresh.tr_cycle);
+            swap(any.tr_viol, fresh.tr_viol), swap(any.tr_cost, fresh.tr_cost);
+        }
+        any.on = true;
+        any.every = every;
+        any.infinity = infinity;
+        drop_graph();
+        HIP_TRY(hipMemsetAsync(any.st.p, 0, sizeof(AnyState), stream));
+        return launch_track(cycles);
+    }
+    int track_restart() override { return any.on ? launch_track(cycles) : MXS_OK; }
+    int get_best(int64_t* cycle, double* cost, int64_t* viol, int32_t* idx) override {
+        HIP_TRY(hipSetDevice(device));
+        if (!any.on) return fail(MXS_E_STATE, "mxs_get_best needs mxs_track_best (every > 0) first");
+        { int rc = sync(); if (rc) return rc; }
+        AnyState h{};
+        HIP_TRY(copy_sync(&h, any.st.p, sizeof(h), hipMemcpyDeviceToHost, stream));
+        if (cycle) *cycle = h.best_cycle;
+        if (cost) *cost = h.best_cost;
+        if (viol) *viol = h.best_viol;
+        if (idx && L.n_vars) {
+            std::vector<int32_t> hs((size_t)L.n_vars);
+            HIP_TRY(copy_sync(hs.data(), any.snap.p, sizeof(int32_t) * hs.size(), hipMemcpyDeviceToHost, stream));
+            for (int vi = 0; vi < L.n_vars; ++vi) idx[L.var_i2e[vi]] = hs[vi];
+        }
+        return MXS_OK;
+    }
+    int get_cost_trace(int64_t* cycle, double* cost, int64_t* viol, int32_t cap, int32_t* n, int64_t* evals) override {
+        HIP_TRY(hipSetDevice(device));
+        if (!any.on) return fail(MXS_E_STATE, "mxs_get_cost_trace needs mxs_track_best (every > 0) first");
+        if (cap < 0 || (cap > 0 && (!cycle || !cost || !viol))) return fail(MXS_E_INVALID, "mxs_get_cost_trace: bad capacity or null arrays");
+        { int rc = sync(); if (rc) return rc; }
+        AnyState h{};
+        HIP_TRY(copy_sync(&h, any.st.p, sizeof(h), hipMemcpyDeviceToHost, stream));
+        const size_t k = (size_t)std::min<long long>(h.evals, std::min<long long>((long long)any.tr_cycle.n, cap));
+        static_assert(sizeof(long long) == sizeof(int64_t), "the trace is copied out as it is stored");
+        HIP_TRY(copy_sync(cycle, any.tr_cycle.p, sizeof(int64_t) * k, hipMemcpyDeviceToHost, stream));
+        HIP_TRY(copy_sync(cost, any.tr_cost.p, sizeof(double) * k, hipMemcpyDeviceToHost, stream));
+        HIP_TRY(copy_sync(viol, any.tr_viol.p, sizeof(int64_t) * k, hipMemcpyDeviceToHost, stream));
+        if (n) *n = (int32_t)k;
+        if (evals) *evals = h.evals;
+        return MXS_OK;
+    }
+
+    int eval_cost(const int32_t* idx, double infinity, double* cost, int64_t* viol) override {
+        HIP_TRY(hipSetDevice(device));
+        { int rc = sync(); if (rc) return rc; }
+        const int nV = L.n_vars;
+        const int32_t* didx = sel.p;
+        if (idx) {
+            std::vector<int32_t> h(nV);
+            for (int vi = 0; vi < nV; ++vi) {
+                const int32_t x = idx[L.var_i2e[vi]];
+                if (x < 0 || x >= L.vdom[vi]) return fail(MXS_E_INVALID, "assignment index out of the domain");
+                h[vi] = x;
+            }
+            HIP_TRY(copy_sync(eval_idx.p, h.data(), sizeof(int32_t) * nV, hipMemcpyHostToDevice, stream));
+            didx = eval_idx.p;
+        }
+        const EvalArgs a = eval_args(didx, infinity);
+        const int nb = eval_blocks();
         hipLaunchKernelGGL(k_eval, dim3(nb), dim3(BLOCK), 0, stream, a);
         HIP_TRY(hipGetLastError());
         std::vector<double> pc(nb);
@@ -1198,6 +1385,7 @@ struct Engine : EngineBase {
     int debug_timeline(int64_t* out, int32_t cap, int32_t* n_blocks) override {
         HIP_TRY(hipSetDevice(device));
         if (halo_ready) return fail(MXS_E_STATE, "mxs_debug_timeline: not on a sharded engine");
+        if (any.on) return fail(MXS_E_STATE, "mxs_debug_timeline: not while mxs_track_best is on (its cycle would go unrecorded)");
         const int nb = L.n_blocks_sweep;
         if (n_blocks) *n_blocks = nb;
         if (!out) return MXS_OK;
@@ -2055,7 +2243,8 @@ int mxs_get_messages(mxs_engine* e, double* v2f, double* f2v, uint8_t* cv, uint8
 int mxs_set_state(mxs_engine* e, const double* v2f, const double* f2v, const uint8_t* cv, const uint8_t* cf,
                   const int32_t* idx, const double* belief, int64_t cycles) {
     CHECK_HANDLE(e);
-    return e->impl->set_state(v2f, f2v, cv, cf, idx, belief, cycles);
+    int rc = e->impl->set_state(v2f, f2v, cv, cf, idx, belief, cycles);
+    return rc ? rc : e->impl->track_restart();
 }
 
 int mxs_table_storage(const mxs_engine* e, int64_t factors[4], int64_t* table_bytes) {
@@ -2086,12 +2275,14 @@ int mxs_table_storage(const mxs_engine* e, int64_t factors[4], int64_t* table_by
 int mxs_set_parent_table(mxs_engine* e, int32_t factor, const double* parent, int32_t n_dims,
                          const int32_t* dims, const uint8_t* is_external) {
     CHECK_HANDLE(e);
-    return e->impl->set_parent(factor, parent, n_dims, dims, is_external);
+    int rc = e->impl->set_parent(factor, parent, n_dims, dims, is_external);
+    return rc ? rc : e->impl->track_restart();
 }
 
 int mxs_slice_factor(mxs_engine* e, int32_t factor, const int32_t* external_idx) {
     CHECK_HANDLE(e);
-    return e->impl->slice_factor(factor, external_idx);
+    int rc = e->impl->slice_factor(factor, external_idx);
+    return rc ? rc : e->impl->track_restart();
 }
 
 int mxs_eval_cost(mxs_engine* e, const int32_t* idx, double infinity, double* cost, int64_t* viol) {
@@ -2160,6 +2351,7 @@ int mxs_variable_kernels(const mxs_engine* e, int64_t counts[6]) {
 int mxs_halo_setup(mxs_engine* e, const int32_t* se, int64_t ns, const int32_t* re, int64_t nr) {
     CHECK_HANDLE(e);
     if ((ns && !se) || (nr && !re) || ns < 0 || nr < 0) return fail(MXS_E_INVALID, "bad halo lists");
+    if (e->impl->tracking()) return fail(MXS_E_STATE, "mxs_halo_setup: not while mxs_track_best is on (a shard's cost is partial)");
     return e->impl->halo_setup(se, ns, re, nr);
 }
 
@@ -2170,9 +2362,27 @@ int mxs_halo_buffers(mxs_engine* e, void** s, int64_t* sb, void** r, int64_t* rb
 
 int mxs_halo_bind(mxs_engine* e, void* s, void* r) { CHECK_HANDLE(e); return e->impl->halo_bind(s, r); }
 
-int mxs_step_compute(mxs_engine* e) { CHECK_HANDLE(e); return e->impl->step_compute(); }
-int mxs_step_pack(mxs_engine* e) { CHECK_HANDLE(e); return e->impl->step_pack(); }
-int mxs_step_unpack(mxs_engine* e) { CHECK_HANDLE(e); return e->impl->step_unpack(); }
+#define CHECK_UNTRACKED(e, what)                                                                              \
+    do {                                                                                                      \
+        if ((e)->impl->tracking()) return fail(MXS_E_STATE, what ": not while mxs_track_best is on");         \
+    } while (0)
+int mxs_step_compute(mxs_engine* e) { CHECK_HANDLE(e); CHECK_UNTRACKED(e, "mxs_step_compute"); return e->impl->step_compute(); }
+int mxs_step_pack(mxs_engine* e) { CHECK_HANDLE(e); CHECK_UNTRACKED(e, "mxs_step_pack"); return e->impl->step_pack(); }
+int mxs_step_unpack(mxs_engine* e) { CHECK_HANDLE(e); CHECK_UNTRACKED(e, "mxs_step_unpack"); return e->impl->step_unpack(); }
+
+int mxs_track_best(mxs_engine* e, int32_t every, double infinity, int32_t trace_capacity) {
+    CHECK_HANDLE(e);
+    return e->impl->track_best(every, infinity, trace_capacity);
+}
+int mxs_get_best(mxs_engine* e, int64_t* cycle, double* cost, int64_t* violations, int32_t* idx) {
+    CHECK_HANDLE(e);
+    return e->impl->get_best(cycle, cost, violations, idx);
+}
+int mxs_get_cost_trace(mxs_engine* e, int64_t* cycle, double* cost, int64_t* violations, int32_t capacity, int32_t* n,
+                       int64_t* evaluations) {
+    CHECK_HANDLE(e);
+    return e->impl->get_cost_trace(cycle, cost, violations, capacity, n, evaluations);
+}
 
 int mxs_comm_unique_id(const char* rccl_path, uint8_t* id) {
     if (!id) return fail(MXS_E_INVALID, "null argument");
@@ -2225,7 +2435,8 @@ int mxs_debug_timeline(mxs_engine* e, int64_t* out, int32_t cap, int32_t* n_bloc
 
 int mxs_update_factor_table(mxs_engine* e, int32_t factor, const double* table, int64_t n) {
     CHECK_HANDLE(e);
-    return e->impl->update_table(factor, table, n);
+    int rc = e->impl->update_table(factor, table, n);
+    return rc ? rc : e->impl->track_restart();
 }
 
 int mxs_destroy(mxs_engine* e) {

@@ -83,6 +83,9 @@ DBA_REPLICA_SYMBOLS = (
     "mxs_dba_stop_rounds", "mxs_dba_replica_violations", "mxs_dba_best_replica",
 )
 
+# ... and Max-Sum's best state and cost trace (include/maxsum_gpu_anytime.h, for the same reason)
+ANYTIME_SYMBOLS = ("mxs_track_best", "mxs_get_best", "mxs_get_cost_trace")
+
 MAX_PEERS = 8
 
 
@@ -310,6 +313,10 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
         "mxs_dba_stop_rounds": ([vp, vp, vp], C.c_int),
         "mxs_dba_replica_violations": ([vp, vp], C.c_int),
         "mxs_dba_best_replica": ([vp, C.POINTER(i32), C.POINTER(i64), C.POINTER(i64)], C.c_int),
+        # ... and MaxSumEngine.track_best / best / cost_trace
+        "mxs_track_best": ([vp, i32, C.c_double, i32], C.c_int),
+        "mxs_get_best": ([vp, C.POINTER(i64), C.POINTER(C.c_double), C.POINTER(i64), vp], C.c_int),
+        "mxs_get_cost_trace": ([vp, vp, vp, vp, i32, C.POINTER(i32), C.POINTER(i64)], C.c_int),
     }
     for name, (argtypes, restype) in later.items():
         fn = getattr(lib, name, None)
@@ -478,6 +485,43 @@ class MaxSumEngine:
             p = idx.ctypes.data
         self._check(self._lib.mxs_eval_cost(self._h, p, float(infinity), C.byref(cost), C.byref(viol)))
         return float(cost.value), int(viol.value)
+
+    # -- best state and cost trace, kept on the device ------------------------------------
+    def _anytime(self, name: str):
+        fn = getattr(self._lib, name, None)
+        if fn is None:
+            missing = [n for n in ANYTIME_SYMBOLS if getattr(self._lib, n, None) is None]
+            raise MaxSumGpuError(f"track_best: this build of the library lacks {', '.join(missing)} "
+                                 "(include/maxsum_gpu_anytime.h): rebuild it from the current sources")
+        return fn
+
+    def track_best(self, every: int, infinity: float = float("inf"), trace: int = 0):
+        """every > 0: keep the best state seen now and after every cycle c with c % every == 0 (strict improvement:
+        fewer violations, then a better cost -- the cost of `eval_cost()` with this `infinity`, bit for bit), and the
+        first `trace` evaluations as a (cycle, cost, violations) curve, all on the device; every = 0: off
+        (mxs_track_best).  `reset()` starts again at cycle 0; a new table or state restarts the record where it is."""
+        fn = self._anytime("mxs_track_best")
+        self._check(fn(self._h, int(every), float(infinity), int(trace)))
+        self._trace_cap = int(trace) if int(every) > 0 else 0
+
+    def best(self) -> dict:
+        """{"cycle", "cost", "violations", "idx"}: the record (mxs_get_best); idx in the graph's variable order."""
+        fn = self._anytime("mxs_get_best")
+        cyc, cost, viol = C.c_int64(0), C.c_double(0), C.c_int64(0)
+        idx = np.empty(self.graph.n_vars, dtype=np.int32)
+        self._check(fn(self._h, C.byref(cyc), C.byref(cost), C.byref(viol), idx.ctypes.data))
+        return {"cycle": int(cyc.value), "cost": float(cost.value), "violations": int(viol.value), "idx": idx}
+
+    def cost_trace(self):
+        """(cycles, costs, violations, evaluations): the stored evaluations, the first record included, and how many
+        were made since the trace was cleared (mxs_get_cost_trace)."""
+        fn = self._anytime("mxs_get_cost_trace")
+        cap = getattr(self, "_trace_cap", 0)
+        cyc, cost, viol = np.zeros(cap, dtype=np.int64), np.zeros(cap, dtype=np.float64), np.zeros(cap, dtype=np.int64)
+        n, evals = C.c_int32(0), C.c_int64(0)
+        self._check(fn(self._h, cyc.ctypes.data, cost.ctypes.data, viol.ctypes.data, cap, C.byref(n), C.byref(evals)))
+        k = int(n.value)
+        return cyc[:k], cost[:k], viol[:k], int(evals.value)
 
     def cycle_bytes(self) -> Tuple[int, int]:
         """(algorithmic bytes per cycle, kernel launches per cycle)."""
