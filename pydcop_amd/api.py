@@ -123,6 +123,27 @@ def _check_maxsum_tracking(algo, cost_every, best_every, devices):
         raise ValueError("best_every: maxsum on one device only (a shard's cost is partial)")
 
 
+def _check_until_quiescent(algo, until_quiescent, devices):
+    """the refusals of until_quiescent, before an engine exists"""
+    if int(until_quiescent) < 0:
+        raise ValueError("until_quiescent must be at least 0")
+    if int(until_quiescent) == 0:
+        return
+    if algo != "maxsum":
+        raise ValueError("until_quiescent: algo=\"maxsum\" only (amaxsum ends by itself, the others have no send rule)")
+    if devices and int(devices) > 1:
+        raise ValueError("until_quiescent: maxsum on one device only (a shard sees its own edges only)")
+
+
+def _run_until_quiescent(eng, cycles, until_quiescent):
+    """algo="maxsum" with until_quiescent = W: watch on the device, run until a cycle is found to have sent nothing,
+    `cycles` at the most.  -> (the cycles run, the result's extra keys)"""
+    eng.watch_quiescence(int(until_quiescent))
+    ran = eng.run_until_quiescent(int(cycles))["cycles_run"]
+    q = eng.quiescence()
+    return ran, {"quiescent": q["quiescent"], "quiescent_cycle": q["cycle"], "active_edges": q["active"]}
+
+
 def _maxsum_track(eng, algo, cycles, cost_every, best_every, infinity, devices=1):
     """algo="maxsum" with cost_every / best_every: switch the engine's device-side tracking on (one evaluation period
     for both: the record and the curve come from the same evaluations).  -> the period, 0 when there is none."""
@@ -204,7 +225,7 @@ def solve_dcop(dcop, cycles: int = 30, *, damping: float = 0.5, damping_nodes: s
                variant: str = "B", probability: float = 0.7, p_mode: str = "fixed", threshold: float = 0.5,
                favor: str = "unilateral", modifier: str = "A", violation: str = "NZ", increase_mode: str = "E",
                dba_infinity: int = 10000, max_distance: int = 50, restarts: int = 1, best_every: int = 0,
-               draws: str = "fixed", dba_stop: str = "first") -> Dict:
+               draws: str = "fixed", dba_stop: str = "first", until_quiescent: int = 0) -> Dict:
     """Synchronous Max-Sum for exactly `cycles` cycles; parameters and defaults are those
     of `pydcop.algorithms.maxsum` (maxsum.py:212-220), `infinity` that of
     `pydcop.infrastructure.run.solve` (run.py:49).  `algo`: "amaxsum" (`cycles` = generations of
@@ -222,6 +243,12 @@ def solve_dcop(dcop, cycles: int = 30, *, damping: float = 0.5, damping_nodes: s
     (MaxSumEngine.track_best: fewest violations, then cost): the assignment, cost and violation are then the record's
     and the result gains "best_cycle".  `cost_every` fills `cost_curve` from the same device trace, in one run call;
     alone it still reports the final state.  Both given and different: ValueError.  One device only.
+    `until_quiescent` = W > 0 makes `cycles` a cap: the engine counts, on the device, the directed edges whose send
+    counter is not at rest after every cycle c with c % W == 0 or c % W == 1 (MaxSumEngine.watch_quiescence) and the
+    run ends once a cycle is found to have sent nothing -- every later cycle would repeat it.  "cycle" is then the
+    number of cycles run and the result gains "quiescent", "quiescent_cycle" (None when the cap came first) and
+    "active_edges" (the count of the last check); with `best_every` / `cost_every` the curve ends where the run ends.
+    Any other algorithm, or `devices` > 1: ValueError.
 
     Returns {"assignment", "cost", "violation", "cycle", "cost_curve"}: the first three
     as `DCOP.solution_cost` computes them for the selected values; `cost_curve` (when
@@ -258,6 +285,7 @@ def solve_dcop(dcop, cycles: int = 30, *, damping: float = 0.5, damping_nodes: s
     stopped); "cycle" is the rounds the engine ran, "finished" whether it has ended.  `best_every` stays refused."""
     _check_restarts(algo, restarts, best_every, draws, dba_stop)
     _check_maxsum_tracking(algo, cost_every, best_every, devices)
+    _check_until_quiescent(algo, until_quiescent, devices)
     graph = compile_dcop(dcop, noise=noise if algo in ("maxsum", "amaxsum") else 0.0, seed=seed)
     params = Params(mode=dcop.objective, damping=damping, damping_nodes=damping_nodes,
                     stability=stability, start_messages=start_messages, dtype=precision)
@@ -267,9 +295,13 @@ def solve_dcop(dcop, cycles: int = 30, *, damping: float = 0.5, damping_nodes: s
         if algo in ("dsa", "gdba") and int(best_every) > 0:
             eng.track_best(int(best_every), infinity)
         tracked = _maxsum_track(eng, algo, cycles, cost_every, best_every, infinity, devices)
-        curve = _run_and_trace(eng, algo, cycles, 0 if tracked else cost_every, infinity)    # (tracked: ONE run call)
+        if int(until_quiescent) > 0:
+            cycles, ended = _run_until_quiescent(eng, cycles, until_quiescent)
+            curve = []
+        else:
+            curve, ended = _run_and_trace(eng, algo, cycles, 0 if tracked else cost_every, infinity), {}  # (tracked: ONE run call)
         idx, _ = eng.assignment()
-        extra = _dba_end(eng, algo)
+        extra = {**_dba_end(eng, algo), **ended}
         best = (_dsa_best(eng, algo, restarts, best_every, infinity) or _mgm_best(eng, algo, restarts, infinity)
                 or _dba_best(eng, algo, restarts))
         if tracked:
@@ -290,7 +322,7 @@ def solve_flat(graph: FlatGraph, objective: str = "min", cycles: int = 30, *, da
                probability: float = 0.7, p_mode: str = "fixed", seed: int = 0, threshold: float = 0.5,
                favor: str = "unilateral", modifier: str = "A", violation: str = "NZ", increase_mode: str = "E",
                dba_infinity: int = 10000, max_distance: int = 50, restarts: int = 1, best_every: int = 0,
-               draws: str = "fixed", dba_stop: str = "first") -> Dict:
+               draws: str = "fixed", dba_stop: str = "first", until_quiescent: int = 0) -> Dict:
     """`solve_dcop` for an already compiled instance (`FlatGraph`, e.g. loaded from the
     .npz instance format): no pyDCOP import at all.  Cost and violations come from the
     device (`mxs_eval_cost` = DCOP.solution_cost, pydcop/dcop/dcop.py:308-367); noise, if
@@ -299,15 +331,20 @@ def solve_flat(graph: FlatGraph, objective: str = "min", cycles: int = 30, *, da
                     stability=stability, start_messages=start_messages, dtype=precision)
     _check_restarts(algo, restarts, best_every, draws, dba_stop)
     _check_maxsum_tracking(algo, cost_every, best_every, devices)
+    _check_until_quiescent(algo, until_quiescent, devices)
     algo_kw = _algo_kw(algo, variant, probability, p_mode, seed, threshold, favor, modifier, violation, increase_mode,
                        dba_infinity, max_distance, restarts, draws, best_every, dba_stop)
     with _engine_for(graph, params, device, devices, lib_path, algo, algo_kw) as eng:
         if algo in ("dsa", "gdba") and int(best_every) > 0:
             eng.track_best(int(best_every), infinity)
         tracked = _maxsum_track(eng, algo, cycles, cost_every, best_every, infinity, devices)
-        curve = _run_and_trace(eng, algo, cycles, 0 if tracked else cost_every, infinity)    # (tracked: ONE run call)
+        if int(until_quiescent) > 0:
+            cycles, ended = _run_until_quiescent(eng, cycles, until_quiescent)
+            curve = []
+        else:
+            curve, ended = _run_and_trace(eng, algo, cycles, 0 if tracked else cost_every, infinity), {}  # (tracked: ONE run call)
         idx, _ = eng.assignment()
-        extra = _dba_end(eng, algo)
+        extra = {**_dba_end(eng, algo), **ended}
         best = (_dsa_best(eng, algo, restarts, best_every, infinity) or _mgm_best(eng, algo, restarts, infinity)
                 or _dba_best(eng, algo, restarts))
         if tracked:
@@ -389,6 +426,8 @@ def main(argv=None):
                     help="name:value, e.g. damping:0.7 noise:0 precision:f32 (maxsum.py:212-220)")
     ap.add_argument("--infinity", type=float, default=float("inf"))   # pydcop/commands/solve.py:316-324
     ap.add_argument("--cost_every", type=int, default=0)
+    ap.add_argument("--until_quiescent", type=int, default=0, metavar="W",
+                    help="maxsum: -c is a cap; stop once a cycle sent nothing, checked on the device every W cycles")
     ap.add_argument("--export", metavar="OUT.npz", default=None,
                     help="compile the YAML DCOP (noise folded in) and write it as an instance file")
     args = ap.parse_args(argv)
@@ -426,7 +465,7 @@ def main(argv=None):
                                   precision=kw.get("precision", "f64"))
         else:
             res = solve_flat(graph, header.get("objective", "min"), args.cycles, infinity=args.infinity,
-                             cost_every=args.cost_every, algo=args.algo, **kw)
+                             cost_every=args.cost_every, algo=args.algo, until_quiescent=args.until_quiescent, **kw)
     elif args.algo == "dpop":
         from . import plugin
         plugin.install()
@@ -435,13 +474,14 @@ def main(argv=None):
                               precision=kw.get("precision", "f64"))
     else:
         res = solve_yaml(args.dcop_files, args.cycles, infinity=args.infinity,
-                         cost_every=args.cost_every, algo=args.algo, **kw)
+                         cost_every=args.cost_every, algo=args.algo, until_quiescent=args.until_quiescent, **kw)
     out = {"assignment": res["assignment"], "cost": res["cost"], "violation": res["violation"],
            "cycle": res["cycle"], "status": "FINISHED", "time": time.perf_counter() - t0,
            "msg_count": 0, "msg_size": 0, "agt_metrics": {}}
     if res["cost_curve"]:
         out["cost_curve"] = res["cost_curve"]
-    for key in ("replica", "best_cycle", "replica_costs", "replica_violations", "stop_rounds"):  # (-p restarts / best_every)
+    for key in ("replica", "best_cycle", "replica_costs", "replica_violations", "stop_rounds",  # (-p restarts / best_every)
+                "quiescent", "quiescent_cycle", "active_edges"):                                # (--until_quiescent)
         if key in res:
             out[key] = res[key]
     print(json.dumps(out, sort_keys=True, indent="  "))

@@ -24,8 +24,10 @@
 #include <vector>
 
 #include "../../include/maxsum_gpu.h"
+#include "../../include/maxsum_gpu_quiescence.h"
 #include "kernels.h"
 #include "anytime.h"
+#include "quiescence.h"
 #include "nary_box.h"
 #include "bin_box.h"
 #include "small_box.h"
@@ -189,6 +191,12 @@ struct EngineBase {
     virtual int get_cost_trace(int64_t* cycle, double* cost, int64_t* viol, int32_t cap, int32_t* n, int64_t* evals) = 0;
     virtual int track_restart() = 0;  // the state or the cost function has changed: the record starts again from here
     virtual bool tracking() const = 0;
+    // the end condition on the device (include/maxsum_gpu_quiescence.h)
+    virtual int watch_quiescence(int32_t every) = 0;
+    virtual int quiescence(int32_t* quiescent, int64_t* cycle, int64_t* checks, int64_t* active, int64_t* last_check) = 0;
+    virtual int run_until_quiescent(int32_t max_cycles, int32_t poll, int32_t* quiescent, int64_t* cycle, int64_t* ran) = 0;
+    virtual int quiet_restart() = 0;  // the state or the cost function has changed: the fixed point no longer holds
+    virtual bool watching() const = 0;
     Layout L;
     mxs_params params{};
     int64_t cycles = 0;
@@ -261,6 +269,17 @@ struct Engine : EngineBase {
         DevBuf<long long> tr_cycle, tr_viol;
         DevBuf<double> tr_cost;
     } any;
+    // mxs_watch_quiescence: the end condition, on the device (quiescence.h)
+    struct Quiet {
+        bool on = false;
+        int every = 0;        // check after every cycle c with c % every == 0 or c % every == 1
+        int graph_phase = 0;  // cycle count % every at the start of the captured chunk
+        int blocks = 1;       // the grid of k_quiet_count
+        QuietLists lists{};   // (device pointers into `tiles` and `gather`)
+        DevBuf<QuietState> st;
+        DevBuf<QuietTile> tiles;
+        DevBuf<uint32_t> gather, part;
+    } quiet;
     static constexpr int FUSED_MAX_CUT_BLOCKS = 1024;  // half of the 2048 resident workgroup slots
 
     ~Engine() override {
@@ -896,35 +915,46 @@ struct Engine : EngineBase {
             rc = launch_track(0);
             if (rc) return rc;
         }
+        rc = quiet_restart();
+        if (rc) return rc;
         return sync();
     }
 
     // Capture `chunk` (even) cycles into a hipGraph: launch-bound loops replay it.
     // The cycles a captured chunk holds while tracking: the configured chunk rounded to a multiple of `every` (and of 2,
     // the parity), 0 where no graph is built (graph_chunk 0, or evaluations more than 256 cycles apart: eager).
+    // The same while watching for quiescence: a multiple of its `every` too, so that the checks sit at fixed places.
     int tracked_chunk() const {
         int chunk = params.graph_chunk < 0 ? 32 : params.graph_chunk;
         if (chunk < 2) return 0;
         chunk &= ~1;
-        const int64_t unit = any.every % 2 ? 2 * (int64_t)any.every : any.every;
+        auto lcm = [](int64_t a, int64_t b) {
+            int64_t x = a, y = b;
+            while (y) { const int64_t r = x % y; x = y; y = r; }
+            return a / x * b;
+        };
+        int64_t unit = 2;
+        if (any.on) unit = lcm(unit, any.every);
+        if (unit <= 256 && quiet.on) unit = lcm(unit, quiet.every);
         if (unit > 256) return 0;
         return (int)(std::max<int64_t>(1, chunk / unit) * unit);
     }
-    // is a graph worth capturing for n cycles?  Twice the chunk, as ever; while tracking, twice the REAL chunk
+    // is a graph worth capturing for n cycles?  Twice the chunk, as ever; while tracking or watching, twice the REAL chunk
     bool worth_graph(int n) const {
-        if (any.on) return tracked_chunk() >= 2 && n >= 2 * tracked_chunk();
+        if (any.on || quiet.on) return tracked_chunk() >= 2 && n >= 2 * tracked_chunk();
         return n >= 2 * std::max(2, params.graph_chunk < 0 ? 32 : params.graph_chunk);
     }
     // `at`: the engine's cycle count where the capture starts.  While tracking, the captured chunk is a multiple of
     // `every` and holds the tracking launches at the positions that follow from `at` (any.graph_phase): a replay is
-    // only started at a cycle count with the same remainder (run_async aligns, as it does for the parity).
+    // only started at a cycle count with the same remainder (run_async aligns, as it does for the parity).  The checks
+    // of mxs_watch_quiescence likewise (quiet.graph_phase).
     void try_build_graph(int64_t at) {
         graph_tried = true;
         int chunk = params.graph_chunk;
         if (chunk < 0) chunk = 32;
         if (chunk < 2) return;
         chunk &= ~1;
-        if (any.on) chunk = tracked_chunk();
+        if (any.on || quiet.on) chunk = tracked_chunk();
         if (chunk < 2) return;
         if (cur != 0) return;  // captured with parity 0; run() aligns first
         hipGraph_t graph = nullptr;
@@ -938,7 +968,7 @@ struct Engine : EngineBase {
         for (int i = 0; i < chunk && ok; ++i) {
             ok = launch_cycle(from, false) == MXS_OK;
             from ^= 1;
-            if (ok && any.on && (at + i + 1) % any.every == 0) ok = launch_track(-1) == MXS_OK;
+            if (ok) ok = after_cycle(at + i + 1, from) == MXS_OK;
         }
         capturing = false;
         if (hipStreamEndCapture(stream, &graph) != hipSuccess || !ok || !graph) {
@@ -952,6 +982,7 @@ struct Engine : EngineBase {
         } else {
             graph_cycles = chunk;
             if (any.on) any.graph_phase = (int)(at % any.every);
+            if (quiet.on) quiet.graph_phase = (int)(at % quiet.every);
         }
         (void)hipGraphDestroy(graph);
     }
@@ -962,7 +993,7 @@ struct Engine : EngineBase {
         if (halo_ready)
             return fail(MXS_E_STATE, "a sharded engine must be stepped with mxs_step_compute/pack/unpack");
         int left = n;
-        if (any.on) return run_tracked(n);
+        if (any.on || quiet.on) return run_tracked(n);
         if (left > 0 && cur != 0) {  // align to the parity the graph was captured with
             int rc = launch_cycle(cur, false);
             if (rc) return rc;
@@ -984,9 +1015,21 @@ struct Engine : EngineBase {
         return MXS_OK;
     }
 
-    // run_async while tracking: the same cycles, an evaluation queued behind every cycle c with c % every == 0.
-    // A replay holds its evaluations at fixed places, so it starts only where the parity AND the remainder of the
-    // cycle count are those of the capture; the cycles before that, and the tail, are eager.
+    // What is queued behind cycle c (its messages are in buffer `now`): the evaluation of mxs_track_best when
+    // c % every == 0, the check of mxs_watch_quiescence when c % every is 0 or 1.
+    int after_cycle(int64_t c, int now) {
+        if (any.on && c % any.every == 0) {
+            int rc = launch_track(-1);
+            if (rc) return rc;
+        }
+        if (quiet.on && c % quiet.every <= 1) return launch_quiet(now);
+        return MXS_OK;
+    }
+
+    // run_async while tracking or watching: the same cycles, an evaluation queued behind every cycle c with
+    // c % every == 0 (a check behind every c with c % every <= 1).  A replay holds these at fixed places, so it starts only
+    // where the parity AND the remainders of the cycle count are those of the capture; the cycles before that, and the
+    // tail, are eager.
     int run_tracked(int n) {
         int left = n;
         int64_t c = cycles;
@@ -996,15 +1039,17 @@ struct Engine : EngineBase {
             cur ^= 1;
             --left;
             ++c;
-            return c % any.every == 0 ? launch_track(-1) : (int)MXS_OK;
+            return after_cycle(c, cur);
         };
         if (left > 0 && cur != 0) {
             int rc = eager();
             if (rc) return rc;
         }
         if (!graph_tried && worth_graph(left)) try_build_graph(c);
-        auto aligned = [&]() { return cur == 0 && c % any.every == any.graph_phase; };
-        for (int64_t tries = 2 * (int64_t)any.every; graph_exec && left >= graph_cycles && !aligned() && tries > 0; --tries) {
+        auto aligned = [&]() {
+            return cur == 0 && (!any.on || c % any.every == any.graph_phase) && (!quiet.on || c % quiet.every == quiet.graph_phase);
+        };
+        for (int64_t tries = graph_cycles; graph_exec && left >= graph_cycles && !aligned() && tries > 0; --tries) {
             int rc = eager();
             if (rc) return rc;
         }
@@ -1345,6 +1390,154 @@ struct Engine : EngineBase {
         return MXS_OK;
     }
 
+    // ---- quiescence (include/maxsum_gpu_quiescence.h, quiescence.h) ------------------------------------------
+    // Where the 2*E send counters live (the places get_messages reads them from), listed once: tiles of whole 16-byte
+    // quads of cF / cV in which every byte is an edge's counter, a gather list for the other bytes and for the
+    // counters kept behind a message record.  cV slots that belong to no edge, and the cF bytes of edges whose counter
+    // rides in the message, are in neither.
+    int build_quiet_lists(Quiet& q) {
+        const int nE = L.n_edges;
+        if (L.n_cv >= (int64_t)QUIET_IN_CV || L.f2v_elems > INT32_MAX || L.v2f_elems > INT32_MAX)
+            return fail(MXS_E_INVALID, "mxs_watch_quiescence: the counter arrays are beyond 2^31 entries");
+        std::vector<uint8_t> useF((size_t)nE, 0), useV((size_t)L.n_cv, 0);
+        std::vector<uint32_t> in_f2v, in_v2f;
+        for (int ei = 0; ei < nE; ++ei) {
+            if (L.edge_fcim[ei]) in_f2v.push_back((uint32_t)(L.f2v_off[ei] + L.edge_dom[ei]));
+            else useF[ei] = 1;
+        }
+        for (int k = 0; k < nE; ++k) {
+            const int ei = L.vslot_edge[k];
+            if (L.edge_vcim[ei]) in_v2f.push_back((uint32_t)(L.v2f_off[ei] + L.edge_dom[ei]));
+            else useV[(size_t)L.vslot_cv[k]] = 1;
+        }
+        std::vector<QuietTile> tiles;
+        std::vector<uint32_t> gather;
+        auto scan = [&](const std::vector<uint8_t>& use, uint32_t flag) {
+            const size_t n = use.size(), nq = n / 16;
+            auto whole = [&](size_t quad) {
+                for (size_t b = 0; b < 16; ++b)
+                    if (!use[quad * 16 + b]) return false;
+                return true;
+            };
+            size_t quad = 0;
+            while (quad < nq) {
+                if (!whole(quad)) {
+                    for (size_t b = 0; b < 16; ++b)
+                        if (use[quad * 16 + b]) gather.push_back((uint32_t)(quad * 16 + b) | flag);
+                    ++quad;
+                    continue;
+                }
+                size_t len = 1;
+                while (len < 64 && quad + len < nq && whole(quad + len)) ++len;
+                tiles.push_back(QuietTile{(uint32_t)quad, (uint32_t)len | flag});
+                quad += len;
+            }
+            for (size_t b = nq * 16; b < n; ++b)
+                if (use[b]) gather.push_back((uint32_t)b | flag);
+        };
+        scan(useF, 0u);
+        scan(useV, QUIET_IN_CV);
+        q.lists.n_tiles = (int32_t)tiles.size();
+        q.lists.n_bytes = (int32_t)gather.size();
+        q.lists.n_f2v = (int32_t)in_f2v.size();
+        q.lists.n_v2f = (int32_t)in_v2f.size();
+        gather.insert(gather.end(), in_f2v.begin(), in_f2v.end());
+        gather.insert(gather.end(), in_v2f.begin(), in_v2f.end());
+        const int64_t threads = std::max<int64_t>((int64_t)tiles.size() * 64, (int64_t)gather.size());
+        q.blocks = (int)std::max<int64_t>(1, std::min<int64_t>(QUIET_MAX_PARTS, (threads + QUIET_TPB - 1) / QUIET_TPB));
+        // the most one lane can count: 16 per tile of its wave, 1 per gather entry of its own
+        const int64_t waves = (int64_t)q.blocks * (QUIET_TPB / 64), grid = (int64_t)q.blocks * QUIET_TPB;
+        const int64_t most = 16 * (((int64_t)tiles.size() + waves - 1) / waves) + ((int64_t)gather.size() + grid - 1) / grid;
+        q.lists.bits = 0;
+        while (q.lists.bits < 32 && (most >> q.lists.bits) != 0) ++q.lists.bits;
+        HIP_TRY(q.tiles.upload(tiles, stream));
+        HIP_TRY(q.gather.upload(gather, stream));
+        HIP_TRY(q.part.alloc((size_t)QUIET_MAX_PARTS));
+        HIP_TRY(q.st.alloc(1));
+        q.lists.tiles = q.tiles.p;
+        q.lists.gather = q.gather.p;
+        return MXS_OK;
+    }
+    // One check, queued on the compute stream with no read-back: k_quiet_count, k_quiet_final.  `now`: the buffers that
+    // hold the messages of the cycle just queued (a fixed place of a captured chunk has a fixed parity).  Behind
+    // launch_cycle it comes after the join of the wide-variable side stream and before the next cycle's sweep.
+    int launch_quiet(int now) {
+        hipLaunchKernelGGL(k_quiet_count<T>, dim3((unsigned)quiet.blocks), dim3(QUIET_TPB), 0, stream, quiet.lists,
+                           (const uint8_t*)cF.p, (const uint8_t*)cV.p, (const T*)f2v[now].p, (const T*)v2f[now].p, quiet.part.p);
+        hipLaunchKernelGGL(k_quiet_final, dim3(1), dim3(QUIET_TPB), 0, stream, quiet.blocks, (const uint32_t*)quiet.part.p,
+                           quiet.every, quiet.st.p);
+        HIP_TRY(hipGetLastError());
+        return MXS_OK;
+    }
+    bool watching() const override { return quiet.on; }
+    int quiet_restart() override {
+        if (!quiet.on) return MXS_OK;
+        hipLaunchKernelGGL(k_quiet_restart, dim3(1), dim3(1), 0, stream, quiet.st.p, (long long)cycles, quiet.every, 0);
+        HIP_TRY(hipGetLastError());
+        return MXS_OK;
+    }
+    int watch_quiescence(int32_t every) override {
+        HIP_TRY(hipSetDevice(device));
+        if (every < 0) return fail(MXS_E_INVALID, "mxs_watch_quiescence: every >= 0");
+        if (halo_ready || nccl_comm || p2p)
+            return fail(MXS_E_STATE, "mxs_watch_quiescence: not on a sharded engine (a shard sees its own edges only)");
+        { int rc = sync(); if (rc) return rc; }
+        auto swap = [](auto& a, auto& b) { std::swap(a.p, b.p); std::swap(a.n, b.n); };
+        Quiet fresh;  // every == 0: the old buffers go with it
+        if (every > 0) {  // all the new buffers first: a call that fails leaves the old setting as it was
+            int rc = build_quiet_lists(fresh);
+            if (rc) return rc;
+        }
+        if (quiet.on || every > 0) drop_graph();
+        swap(quiet.st, fresh.st), swap(quiet.tiles, fresh.tiles), swap(quiet.gather, fresh.gather), swap(quiet.part, fresh.part);
+        quiet.lists = fresh.lists;
+        quiet.blocks = fresh.blocks;
+        quiet.on = every > 0;
+        quiet.every = every;
+        if (!quiet.on) return MXS_OK;
+        hipLaunchKernelGGL(k_quiet_restart, dim3(1), dim3(1), 0, stream, quiet.st.p, (long long)cycles, quiet.every, 1);
+        HIP_TRY(hipGetLastError());
+        return MXS_OK;
+    }
+    int quiet_read(QuietState* h) {
+        { int rc = sync(); if (rc) return rc; }
+        HIP_TRY(copy_sync(h, quiet.st.p, sizeof(*h), hipMemcpyDeviceToHost, stream));
+        return MXS_OK;
+    }
+    int quiescence(int32_t* quiescent, int64_t* cycle, int64_t* checks, int64_t* active, int64_t* last_check) override {
+        HIP_TRY(hipSetDevice(device));
+        if (!quiet.on) return fail(MXS_E_STATE, "mxs_quiescence needs mxs_watch_quiescence (every > 0) first");
+        QuietState h{};
+        { int rc = quiet_read(&h); if (rc) return rc; }
+        if (quiescent) *quiescent = h.quiescent_at >= 0 ? 1 : 0;
+        if (cycle) *cycle = h.quiescent_at;
+        if (checks) *checks = h.checks;
+        if (active) *active = h.active;
+        if (last_check) *last_check = h.last_check;
+        return MXS_OK;
+    }
+    int run_until_quiescent(int32_t max_cycles, int32_t poll, int32_t* quiescent, int64_t* cycle, int64_t* ran) override {
+        HIP_TRY(hipSetDevice(device));
+        if (!quiet.on) return fail(MXS_E_STATE, "mxs_run_until_quiescent needs mxs_watch_quiescence (every > 0) first");
+        if (max_cycles < 0) return fail(MXS_E_INVALID, "mxs_run_until_quiescent: max_cycles >= 0");
+        if (poll <= 0) poll = std::max(64, 2 * tracked_chunk());
+        QuietState h{};
+        { int rc = quiet_read(&h); if (rc) return rc; }
+        int64_t done = 0;
+        while (h.quiescent_at < 0 && done < max_cycles) {
+            const int span = (int)std::min<int64_t>(poll, max_cycles - done);
+            int rc = run_async(span);
+            if (rc) return rc;
+            done += span;
+            rc = quiet_read(&h);
+            if (rc) return rc;
+        }
+        if (quiescent) *quiescent = h.quiescent_at >= 0 ? 1 : 0;
+        if (cycle) *cycle = h.quiescent_at;
+        if (ran) *ran = done;
+        return MXS_OK;
+    }
+
     int eval_cost(const int32_t* idx, double infinity, double* cost, int64_t* viol) override {
         HIP_TRY(hipSetDevice(device));
         { int rc = sync(); if (rc) return rc; }
@@ -1386,6 +1579,7 @@ struct Engine : EngineBase {
         HIP_TRY(hipSetDevice(device));
         if (halo_ready) return fail(MXS_E_STATE, "mxs_debug_timeline: not on a sharded engine");
         if (any.on) return fail(MXS_E_STATE, "mxs_debug_timeline: not while mxs_track_best is on (its cycle would go unrecorded)");
+        if (quiet.on) return fail(MXS_E_STATE, "mxs_debug_timeline: not while mxs_watch_quiescence is on (its cycle would go unchecked)");
         const int nb = L.n_blocks_sweep;
         if (n_blocks) *n_blocks = nb;
         if (!out) return MXS_OK;
@@ -2244,7 +2438,8 @@ int mxs_set_state(mxs_engine* e, const double* v2f, const double* f2v, const uin
                   const int32_t* idx, const double* belief, int64_t cycles) {
     CHECK_HANDLE(e);
     int rc = e->impl->set_state(v2f, f2v, cv, cf, idx, belief, cycles);
-    return rc ? rc : e->impl->track_restart();
+    if (!rc) rc = e->impl->track_restart();
+    return rc ? rc : e->impl->quiet_restart();
 }
 
 int mxs_table_storage(const mxs_engine* e, int64_t factors[4], int64_t* table_bytes) {
@@ -2276,13 +2471,15 @@ int mxs_set_parent_table(mxs_engine* e, int32_t factor, const double* parent, in
                          const int32_t* dims, const uint8_t* is_external) {
     CHECK_HANDLE(e);
     int rc = e->impl->set_parent(factor, parent, n_dims, dims, is_external);
-    return rc ? rc : e->impl->track_restart();
+    if (!rc) rc = e->impl->track_restart();
+    return rc ? rc : e->impl->quiet_restart();
 }
 
 int mxs_slice_factor(mxs_engine* e, int32_t factor, const int32_t* external_idx) {
     CHECK_HANDLE(e);
     int rc = e->impl->slice_factor(factor, external_idx);
-    return rc ? rc : e->impl->track_restart();
+    if (!rc) rc = e->impl->track_restart();
+    return rc ? rc : e->impl->quiet_restart();
 }
 
 int mxs_eval_cost(mxs_engine* e, const int32_t* idx, double infinity, double* cost, int64_t* viol) {
@@ -2352,6 +2549,7 @@ int mxs_halo_setup(mxs_engine* e, const int32_t* se, int64_t ns, const int32_t* 
     CHECK_HANDLE(e);
     if ((ns && !se) || (nr && !re) || ns < 0 || nr < 0) return fail(MXS_E_INVALID, "bad halo lists");
     if (e->impl->tracking()) return fail(MXS_E_STATE, "mxs_halo_setup: not while mxs_track_best is on (a shard's cost is partial)");
+    if (e->impl->watching()) return fail(MXS_E_STATE, "mxs_halo_setup: not while mxs_watch_quiescence is on (a shard sees its own edges only)");
     return e->impl->halo_setup(se, ns, re, nr);
 }
 
@@ -2365,6 +2563,7 @@ int mxs_halo_bind(mxs_engine* e, void* s, void* r) { CHECK_HANDLE(e); return e->
 #define CHECK_UNTRACKED(e, what)                                                                              \
     do {                                                                                                      \
         if ((e)->impl->tracking()) return fail(MXS_E_STATE, what ": not while mxs_track_best is on");         \
+        if ((e)->impl->watching()) return fail(MXS_E_STATE, what ": not while mxs_watch_quiescence is on");   \
     } while (0)
 int mxs_step_compute(mxs_engine* e) { CHECK_HANDLE(e); CHECK_UNTRACKED(e, "mxs_step_compute"); return e->impl->step_compute(); }
 int mxs_step_pack(mxs_engine* e) { CHECK_HANDLE(e); CHECK_UNTRACKED(e, "mxs_step_pack"); return e->impl->step_pack(); }
@@ -2382,6 +2581,20 @@ int mxs_get_cost_trace(mxs_engine* e, int64_t* cycle, double* cost, int64_t* vio
                        int64_t* evaluations) {
     CHECK_HANDLE(e);
     return e->impl->get_cost_trace(cycle, cost, violations, capacity, n, evaluations);
+}
+
+int mxs_watch_quiescence(mxs_engine* e, int32_t every) {
+    CHECK_HANDLE(e);
+    return e->impl->watch_quiescence(every);
+}
+int mxs_quiescence(mxs_engine* e, int32_t* quiescent, int64_t* cycle, int64_t* checks, int64_t* active, int64_t* last_check_cycle) {
+    CHECK_HANDLE(e);
+    return e->impl->quiescence(quiescent, cycle, checks, active, last_check_cycle);
+}
+int mxs_run_until_quiescent(mxs_engine* e, int32_t max_cycles, int32_t poll, int32_t* quiescent, int64_t* cycle,
+                            int64_t* cycles_run) {
+    CHECK_HANDLE(e);
+    return e->impl->run_until_quiescent(max_cycles, poll, quiescent, cycle, cycles_run);
 }
 
 int mxs_comm_unique_id(const char* rccl_path, uint8_t* id) {
@@ -2436,7 +2649,8 @@ int mxs_debug_timeline(mxs_engine* e, int64_t* out, int32_t cap, int32_t* n_bloc
 int mxs_update_factor_table(mxs_engine* e, int32_t factor, const double* table, int64_t n) {
     CHECK_HANDLE(e);
     int rc = e->impl->update_table(factor, table, n);
-    return rc ? rc : e->impl->track_restart();
+    if (!rc) rc = e->impl->track_restart();
+    return rc ? rc : e->impl->quiet_restart();
 }
 
 int mxs_destroy(mxs_engine* e) {

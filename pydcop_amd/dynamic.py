@@ -175,6 +175,7 @@ class DynamicMaxSum:
         self.engine = self._factory(graph, self.params)
         self._parents = {}
         self.relayouts = 0
+        self._watch_every = 0
 
     def _default_factory(self, graph, params):
         from .engine import MaxSumEngine
@@ -196,6 +197,21 @@ class DynamicMaxSum:
     @property
     def cycle_count(self) -> int:
         return self.engine.cycle_count
+
+    # -- the end condition, detected on the device (MaxSumEngine.watch_quiescence) ---------------
+    def watch_quiescence(self, every: int):
+        self.engine.watch_quiescence(every)
+        self._watch_every = int(every)
+
+    def quiescence(self) -> dict:
+        return self.engine.quiescence()
+
+    @property
+    def quiescent(self) -> bool:
+        return bool(self._watch_every) and self.engine.quiescent
+
+    def run_until_quiescent(self, max_cycles: int, poll: Optional[int] = None) -> dict:
+        return self.engine.run_until_quiescent(max_cycles, poll)
 
     def close(self):
         self.engine.close()
@@ -226,6 +242,8 @@ class DynamicMaxSum:
         ng, ns = rescope_factor(g, self.engine.state(), factor, scope, table, self.params.mode, self.params.dtype)
         new_engine = self._factory(ng, self.params)
         new_engine.set_state(**ns)
+        if self._watch_every:   # (the new engine watches too, from the carried state: not quiescent)
+            new_engine.watch_quiescence(self._watch_every)
         self.engine.close()
         self.engine, self.graph = new_engine, ng
         self._parents.pop(int(factor), None)

@@ -86,6 +86,9 @@ DBA_REPLICA_SYMBOLS = (
 # ... and Max-Sum's best state and cost trace (include/maxsum_gpu_anytime.h, for the same reason)
 ANYTIME_SYMBOLS = ("mxs_track_best", "mxs_get_best", "mxs_get_cost_trace")
 
+# ... and Max-Sum's end condition, detected on the device (include/maxsum_gpu_quiescence.h, for the same reason)
+QUIESCENCE_SYMBOLS = ("mxs_watch_quiescence", "mxs_quiescence", "mxs_run_until_quiescent")
+
 MAX_PEERS = 8
 
 
@@ -317,6 +320,10 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
         "mxs_track_best": ([vp, i32, C.c_double, i32], C.c_int),
         "mxs_get_best": ([vp, C.POINTER(i64), C.POINTER(C.c_double), C.POINTER(i64), vp], C.c_int),
         "mxs_get_cost_trace": ([vp, vp, vp, vp, i32, C.POINTER(i32), C.POINTER(i64)], C.c_int),
+        # ... and MaxSumEngine.watch_quiescence / quiescence / run_until_quiescent
+        "mxs_watch_quiescence": ([vp, i32], C.c_int),
+        "mxs_quiescence": ([vp, C.POINTER(i32), C.POINTER(i64), C.POINTER(i64), C.POINTER(i64), C.POINTER(i64)], C.c_int),
+        "mxs_run_until_quiescent": ([vp, i32, i32, C.POINTER(i32), C.POINTER(i64), C.POINTER(i64)], C.c_int),
     }
     for name, (argtypes, restype) in later.items():
         fn = getattr(lib, name, None)
@@ -522,6 +529,48 @@ class MaxSumEngine:
         self._check(fn(self._h, cyc.ctypes.data, cost.ctypes.data, viol.ctypes.data, cap, C.byref(n), C.byref(evals)))
         k = int(n.value)
         return cyc[:k], cost[:k], viol[:k], int(evals.value)
+
+    # -- the end condition, detected on the device -----------------------------------------
+    def _quiescence(self, name: str):
+        fn = getattr(self._lib, name, None)
+        if fn is None:
+            missing = [n for n in QUIESCENCE_SYMBOLS if getattr(self._lib, n, None) is None]
+            raise MaxSumGpuError(f"watch_quiescence: this build of the library lacks {', '.join(missing)} "
+                                 "(include/maxsum_gpu_quiescence.h): rebuild it from the current sources")
+        return fn
+
+    def watch_quiescence(self, every: int):
+        """every = W > 0: count, on the device, the send counters that are not at rest after every cycle c with
+        c % W == 0 or c % W == 1, and note the first cycle found to have sent nothing (two consecutive checks with
+        none active: from then on every cycle repeats itself); every = 0: off (mxs_watch_quiescence).  `reset()`, a
+        new table or a new state end the fixed point: detection starts again from there."""
+        fn = self._quiescence("mxs_watch_quiescence")
+        self._check(fn(self._h, int(every)))
+        self._watch_every = int(every)
+
+    def quiescence(self) -> dict:
+        """{"quiescent", "cycle" (None while there is none), "checks", "active", "last_check_cycle"}: one small copy
+        from the device (mxs_quiescence)."""
+        fn = self._quiescence("mxs_quiescence")
+        q, cyc, checks, active, last = C.c_int32(0), C.c_int64(0), C.c_int64(0), C.c_int64(0), C.c_int64(0)
+        self._check(fn(self._h, C.byref(q), C.byref(cyc), C.byref(checks), C.byref(active), C.byref(last)))
+        return {"quiescent": bool(q.value), "cycle": int(cyc.value) if q.value else None, "checks": int(checks.value),
+                "active": int(active.value), "last_check_cycle": int(last.value)}
+
+    @property
+    def quiescent(self) -> bool:
+        """Has a cycle been found to have sent nothing?  False, without touching the device, when not watching."""
+        if not getattr(self, "_watch_every", 0):
+            return False
+        return self.quiescence()["quiescent"]
+
+    def run_until_quiescent(self, max_cycles: int, poll: Optional[int] = None) -> dict:
+        """Run spans of `poll` cycles (None: the larger of 64 and twice the captured chunk) until a span ends
+        quiescent, `max_cycles` at the most -> {"quiescent", "cycle", "cycles_run"} (mxs_run_until_quiescent)."""
+        fn = self._quiescence("mxs_run_until_quiescent")
+        q, cyc, ran = C.c_int32(0), C.c_int64(0), C.c_int64(0)
+        self._check(fn(self._h, int(max_cycles), 0 if poll is None else int(poll), C.byref(q), C.byref(cyc), C.byref(ran)))
+        return {"quiescent": bool(q.value), "cycle": int(cyc.value) if q.value else None, "cycles_run": int(ran.value)}
 
     def cycle_bytes(self) -> Tuple[int, int]:
         """(algorithmic bytes per cycle, kernel launches per cycle)."""
