@@ -16,9 +16,8 @@ a run is reproducible, and value for value the reference's own DbaComputation un
 from pydcop.algorithms import AlgoParameterDef
 
 from pydcop_amd.algorithms import maxsum_gpu as _base
-from pydcop_amd.algorithms.mgm2_gpu import _compile_hypergraph
-from pydcop_amd.algorithms.mgm_gpu import _MgmSession
 from pydcop_amd.graph import Params
+from pydcop_amd.local_search import EngineAdapter, LocalSearchSession, computation_for
 
 GRAPH_TYPE = "constraints_hypergraph"
 HEADER_SIZE = 100
@@ -44,64 +43,34 @@ def communication_load(src, target: str) -> float:
     return 2 * UNIT_SIZE + HEADER_SIZE
 
 
-class _RoundEngine:
+class _RoundEngine(EngineAdapter):
     """DbaEngine behind the surface the session drives."""
 
     def __init__(self, graph, params, p):
         from pydcop_amd.dba import DbaEngine
-        self.graph = graph
-        self._e = DbaEngine(graph, params, infinity=p["infinity"], max_distance=int(p["max_distance"]), seed=int(p["seed"]))
-
-    def run(self, n: int):
-        self._e.run(int(n))
+        super().__init__(graph, DbaEngine(graph, params, infinity=p["infinity"], max_distance=int(p["max_distance"]),
+                                          seed=int(p["seed"])))
 
     @property
     def quiescent(self) -> bool:
         """the engine has stopped: the session ends the run FINISHED, as the reference's does"""
         return self._e.finished
 
-    def assignment(self):
-        return self._e.assignment()
 
-    @property
-    def cycle_count(self) -> int:
-        return self._e.cycle_count
-
-    def close(self):
-        self._e.close()
+def _min_only(algo):
+    if algo.mode != "min":   # the constructor of DbaComputation (dba.py:295-298)
+        raise ValueError("DBA is a constraint **satisfaction** algorithm and only support minimization objective")
 
 
-class _DbaSession(_MgmSession):      # (same compilation of the hypergraph nodes and stop_cycle as mgm_gpu)
-    ALGO = "dba_gpu"
-
-    def _compile_graph(self, p):
-        return _compile_hypergraph(cd.node for cd in self.comp_defs.values())
+class _DbaSession(LocalSearchSession):
+    ALGO, ENGINE = "dba_gpu", _RoundEngine
 
     def _engine_params(self, algo, p):
-        if algo.mode != "min":   # the constructor of DbaComputation (dba.py:295-298)
-            raise ValueError("DBA is a constraint **satisfaction** algorithm and only support minimization objective")
+        _min_only(algo)
         return Params(mode=algo.mode)
-
-    def _make_engine(self, params, p):
-        return _RoundEngine(self.graph, params, p)
-
-    def update_factor(self, name, old, fn):
-        raise ValueError("dba_gpu: change_factor_function is a maxsum_gpu feature")
 
 
 _base.SESSION_CLASSES["dba_gpu"] = _DbaSession
-
-
-class DbaGpuComputation(_base.MaxSumGpuVariableComputation):
-    """Stands for a DbaComputation (pydcop/algorithms/dba.py:272)."""
-
-    def footprint(self) -> float:
-        return computation_memory(self.computation_def.node)
-
-
-def build_computation(comp_def):
-    if comp_def.node.type != "VariableComputationNode":
-        raise ValueError("dba_gpu: unsupported computation node type " + str(comp_def.node.type))
-    if comp_def.algo.mode != "min":   # dba.py:295-298
-        raise ValueError("DBA is a constraint **satisfaction** algorithm and only support minimization objective")
-    return DbaGpuComputation(comp_def)
+DbaGpuComputation, build_computation = computation_for(
+    "dba_gpu", "DbaGpuComputation", "Stands for a DbaComputation (pydcop/algorithms/dba.py:272).", computation_memory,
+    check=lambda comp_def: _min_only(comp_def.algo))

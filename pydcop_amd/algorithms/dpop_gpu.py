@@ -9,17 +9,13 @@ proxy computation then selects its value with the cost its DpopAlgo would report
 Extra parameters: `precision` (f64 | f32) and `max_bytes` (the budget of the UTIL tables; 0 = a share of
 the free device memory): an instance whose tables do not fit is refused with the bytes it needs.
 """
-from types import SimpleNamespace
-
-import numpy as np
-
 from pydcop.algorithms import AlgoParameterDef
 from pydcop.computations_graph.pseudotree import get_dfs_relations
 from pydcop.infrastructure.computations import ComputationException
 
 from pydcop_amd.algorithms import maxsum_gpu as _base
-from pydcop_amd.compile import compile_nodes
 from pydcop_amd.graph import Params
+from pydcop_amd.local_search import _compile_hypergraph, computation_for
 
 GRAPH_TYPE = "pseudotree"
 
@@ -42,15 +38,7 @@ def compile_pseudotree(nodes):
     variable's constraints in its node's order, the tree as the nodes' links give it."""
     from pydcop_amd.dpop import pack_tree
     nodes = sorted(nodes, key=lambda n: n.name)
-    constraints = {}
-    for n in nodes:
-        for c in n.constraints:
-            constraints.setdefault(c.name, c)
-    fac_nodes = [SimpleNamespace(name=name, factor=constraints[name]) for name in sorted(constraints)]
-    var_nodes = [SimpleNamespace(name=n.name, variable=n.variable,
-                                 links=[SimpleNamespace(factor_node=c.name) for c in n.constraints])
-                 for n in nodes]
-    graph = compile_nodes(var_nodes, fac_nodes, noise=0.0)
+    graph = _compile_hypergraph(nodes)       # (a pseudo-tree node has the name, variable and constraints it reads)
     index = {name: i for i, name in enumerate(graph.var_names)}
     parent, children = [-1] * len(nodes), [[] for _ in nodes]
     for n in nodes:
@@ -101,16 +89,6 @@ class _DpopSession(_base._Session):
 
 
 _base.SESSION_CLASSES["dpop_gpu"] = _DpopSession
-
-
-class DpopGpuComputation(_base.MaxSumGpuVariableComputation):
-    """Stands for a DpopAlgo (pydcop/algorithms/dpop.py:115)."""
-
-    def footprint(self) -> float:
-        return computation_memory(self.computation_def.node)
-
-
-def build_computation(comp_def):
-    if comp_def.node.type != "PseudoTreeComputation":
-        raise ValueError("dpop_gpu: unsupported computation node type " + str(comp_def.node.type))
-    return DpopGpuComputation(comp_def)
+DpopGpuComputation, build_computation = computation_for(
+    "dpop_gpu", "DpopGpuComputation", "Stands for a DpopAlgo (pydcop/algorithms/dpop.py:115).", computation_memory,
+    node_type="PseudoTreeComputation")

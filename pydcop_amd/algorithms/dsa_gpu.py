@@ -23,8 +23,7 @@ an earlier cycle, the held costs are still the current ones -- the engine keeps 
 from pydcop.algorithms import AlgoParameterDef
 
 from pydcop_amd.algorithms import maxsum_gpu as _base
-from pydcop_amd.algorithms.mgm_gpu import _MgmSession
-from pydcop_amd.graph import Params
+from pydcop_amd.local_search import EngineAdapter, LocalSearchSession, computation_for
 
 GRAPH_TYPE = "constraints_hypergraph"
 HEADER_SIZE = 0
@@ -54,20 +53,16 @@ def communication_load(src, target: str) -> float:
     return UNIT_SIZE + HEADER_SIZE
 
 
-class _CycleEngine:
+class _CycleEngine(EngineAdapter):
     """DsaEngine behind the surface the session drives."""
 
     def __init__(self, graph, params, p):
         from pydcop_amd.dsa import DsaEngine
-        self.graph = graph
-        self._e = DsaEngine(graph, params, variant=p["variant"], probability=float(p["probability"]),
-                            p_mode=p["p_mode"], seed=int(p["seed"]), replicas=int(p["restarts"]))
-        self._many = int(p["restarts"]) > 1 or int(p["best_every"]) > 0
+        super().__init__(graph, DsaEngine(graph, params, variant=p["variant"], probability=float(p["probability"]),
+                                          p_mode=p["p_mode"], seed=int(p["seed"]), replicas=int(p["restarts"])),
+                         many=int(p["restarts"]) > 1 or int(p["best_every"]) > 0)
         if self._many:
             self._e.track_best(int(p["best_every"]), float("inf"))
-
-    def run(self, n: int):
-        self._e.run(int(n))
 
     def assignment(self):
         if not self._many:
@@ -75,41 +70,14 @@ class _CycleEngine:
         best = self._e.best()               # the best replica: its record (best_every > 0) or its state
         return best["idx"], self._e.assignment(best["replica"])[1]   # (held costs: the current ones, see above)
 
-    @property
-    def cycle_count(self) -> int:
-        return self._e.cycle_count
 
-    def close(self):
-        self._e.close()
-
-
-class _DsaSession(_MgmSession):      # (same compilation of the hypergraph nodes as mgm_gpu)
-    ALGO = "dsa_gpu"
-
-    def _engine_params(self, algo, p):
-        return Params(mode=algo.mode, dtype=p["precision"])
-
-    def _make_engine(self, params, p):
-        return _CycleEngine(self.graph, params, p)
+class _DsaSession(LocalSearchSession):
+    ALGO, ENGINE = "dsa_gpu", _CycleEngine
 
     def _cycles_to_run(self, p) -> int:
         return int(p["stop_cycle"])
 
-    def update_factor(self, name, old, fn):
-        raise ValueError("dsa_gpu: change_factor_function is a maxsum_gpu feature")
-
 
 _base.SESSION_CLASSES["dsa_gpu"] = _DsaSession
-
-
-class DsaGpuComputation(_base.MaxSumGpuVariableComputation):
-    """Stands for a DsaComputation (pydcop/algorithms/dsa.py:214)."""
-
-    def footprint(self) -> float:
-        return computation_memory(self.computation_def.node)
-
-
-def build_computation(comp_def):
-    if comp_def.node.type != "VariableComputationNode":
-        raise ValueError("dsa_gpu: unsupported computation node type " + str(comp_def.node.type))
-    return DsaGpuComputation(comp_def)
+DsaGpuComputation, build_computation = computation_for(
+    "dsa_gpu", "DsaGpuComputation", "Stands for a DsaComputation (pydcop/algorithms/dsa.py:214).", computation_memory)

@@ -14,8 +14,7 @@ same generator.
 from pydcop.algorithms import AlgoParameterDef
 
 from pydcop_amd.algorithms import maxsum_gpu as _base
-from pydcop_amd.algorithms.mgm2_gpu import _compile_hypergraph
-from pydcop_amd.algorithms.mgm_gpu import _MgmSession
+from pydcop_amd.local_search import EngineAdapter, LocalSearchSession, computation_for
 
 GRAPH_TYPE = "constraints_hypergraph"
 HEADER_SIZE = 100
@@ -45,15 +44,15 @@ def communication_load(src, target: str) -> float:
     return 2 * UNIT_SIZE + HEADER_SIZE
 
 
-class _RoundEngine:
+class _RoundEngine(EngineAdapter):
     """GdbaEngine behind the surface the session drives."""
+    FIRST_CYCLE = 1          # the reference's counter starts at 1 (gdba.py:420)
 
     def __init__(self, graph, params, p):
         from pydcop_amd.gdba import MAX_ROUNDS, GdbaEngine
-        self.graph = graph
         self._max = MAX_ROUNDS
-        self._e = GdbaEngine(graph, params, modifier=p["modifier"], violation=p["violation"],
-                             increase_mode=p["increase_mode"], seed=int(p["seed"]))
+        super().__init__(graph, GdbaEngine(graph, params, modifier=p["modifier"], violation=p["violation"],
+                                           increase_mode=p["increase_mode"], seed=int(p["seed"])))
 
     def run(self, n: int):
         left = self._max - self._e.cycle_count
@@ -68,41 +67,11 @@ class _RoundEngine:
         """the session ends a `stop_cycle: 0` run (status FINISHED) once no further round can be run"""
         return self._e.cycle_count >= self._max
 
-    def assignment(self):
-        return self._e.assignment()
 
-    @property
-    def cycle_count(self) -> int:
-        return self._e.cycle_count + 1          # the reference's counter starts at 1 (gdba.py:420)
-
-    def close(self):
-        self._e.close()
-
-
-class _GdbaSession(_MgmSession):      # (same compilation of the hypergraph nodes and stop_cycle as mgm_gpu)
-    ALGO = "gdba_gpu"
-
-    def _compile_graph(self, p):
-        return _compile_hypergraph(cd.node for cd in self.comp_defs.values())
-
-    def _make_engine(self, params, p):
-        return _RoundEngine(self.graph, params, p)
-
-    def update_factor(self, name, old, fn):
-        raise ValueError("gdba_gpu: change_factor_function is a maxsum_gpu feature")
+class _GdbaSession(LocalSearchSession):
+    ALGO, ENGINE = "gdba_gpu", _RoundEngine
 
 
 _base.SESSION_CLASSES["gdba_gpu"] = _GdbaSession
-
-
-class GdbaGpuComputation(_base.MaxSumGpuVariableComputation):
-    """Stands for a GdbaComputation (pydcop/algorithms/gdba.py:189)."""
-
-    def footprint(self) -> float:
-        return computation_memory(self.computation_def.node)
-
-
-def build_computation(comp_def):
-    if comp_def.node.type != "VariableComputationNode":
-        raise ValueError("gdba_gpu: unsupported computation node type " + str(comp_def.node.type))
-    return GdbaGpuComputation(comp_def)
+GdbaGpuComputation, build_computation = computation_for(
+    "gdba_gpu", "GdbaGpuComputation", "Stands for a GdbaComputation (pydcop/algorithms/gdba.py:189).", computation_memory)

@@ -14,14 +14,11 @@ seed .. seed + R - 1) in the one engine and publishes the best replica's values 
 to infinity, then the best solution cost, evaluated on the device; the ranking takes no `infinity` (the module has no
 such parameter: every table entry, however large, is a cost).  With the defaults the module is the single run above.
 """
-from types import SimpleNamespace
-
 from pydcop.algorithms import AlgoParameterDef
 
 from pydcop_amd.algorithms import maxsum_gpu as _base
-from pydcop_amd.algorithms.mgm_gpu import _MgmSession
-from pydcop_amd.compile import compile_nodes
-from pydcop_amd.graph import Params
+from pydcop_amd.local_search import (EngineAdapter, LocalSearchSession, compile_dcop_for_local_search,  # noqa: F401
+                                     computation_for)                          # (compile_dcop_...: importable from here)
 
 GRAPH_TYPE = "constraints_hypergraph"
 HEADER_SIZE = 100
@@ -57,77 +54,20 @@ def communication_load(src, target: str) -> float:
     return nb_pairs * UNIT_SIZE * 3 + HEADER_SIZE
 
 
-def compile_dcop_for_local_search(dcop):
-    """A DCOP compiled as this plug-in compiles it: the nodes of the reference's constraints
-    hypergraph by name, each variable's constraints in the node's order."""
-    from pydcop.computations_graph import constraints_hypergraph as chg
-    cg = chg.build_computation_graph(dcop)
-    return _compile_hypergraph(list(cg.nodes))
-
-
-def _compile_hypergraph(nodes):
-    nodes = sorted(nodes, key=lambda n: n.name)
-    constraints = {}
-    for n in nodes:
-        for c in n.constraints:
-            constraints.setdefault(c.name, c)
-    fac_nodes = [SimpleNamespace(name=name, factor=constraints[name]) for name in sorted(constraints)]
-    var_nodes = [SimpleNamespace(name=n.name, variable=n.variable,
-                                 links=[SimpleNamespace(factor_node=c.name) for c in n.constraints])
-                 for n in nodes]
-    return compile_nodes(var_nodes, fac_nodes, noise=0.0)
-
-
-class _RoundEngine:
+class _RoundEngine(EngineAdapter):
     """Mgm2Engine behind the surface the session drives."""
+    FIRST_CYCLE = 1          # the reference's counter starts at 1 (mgm2.py:659)
 
     def __init__(self, graph, params, p):
         from pydcop_amd.mgm2 import Mgm2Engine
-        self.graph = graph
-        self._many = int(p["restarts"]) > 1
-        self._e = Mgm2Engine(graph, params, threshold=p["threshold"], favor=p["favor"], seed=int(p["seed"]),
-                             replicas=int(p["restarts"]))
-
-    def run(self, n: int):
-        self._e.run(int(n))
-
-    def assignment(self):
-        if not self._many:
-            return self._e.assignment()
-        return self._e.assignment(self._e.best()["replica"])     # the best replica's values and held costs
-
-    @property
-    def cycle_count(self) -> int:
-        return self._e.cycle_count + 1          # the reference's counter starts at 1 (mgm2.py:659)
-
-    def close(self):
-        self._e.close()
+        super().__init__(graph, Mgm2Engine(graph, params, threshold=p["threshold"], favor=p["favor"], seed=int(p["seed"]),
+                                           replicas=int(p["restarts"])), many=int(p["restarts"]) > 1)
 
 
-class _Mgm2Session(_MgmSession):      # (same compilation of the hypergraph nodes and stop_cycle as mgm_gpu)
-    ALGO = "mgm2_gpu"
-
-    def _compile_graph(self, p):
-        return _compile_hypergraph(cd.node for cd in self.comp_defs.values())
-
-    def _make_engine(self, params, p):
-        return _RoundEngine(self.graph, params, p)
-
-    def update_factor(self, name, old, fn):
-        raise ValueError("mgm2_gpu: change_factor_function is a maxsum_gpu feature")
+class _Mgm2Session(LocalSearchSession):
+    ALGO, ENGINE = "mgm2_gpu", _RoundEngine
 
 
 _base.SESSION_CLASSES["mgm2_gpu"] = _Mgm2Session
-
-
-class Mgm2GpuComputation(_base.MaxSumGpuVariableComputation):
-    """Stands for an Mgm2Computation (pydcop/algorithms/mgm2.py:399)."""
-
-    def footprint(self) -> float:
-        return computation_memory(self.computation_def.node)
-
-
-def build_computation(comp_def):
-    if comp_def.node.type != "VariableComputationNode":
-        raise ValueError("mgm2_gpu: unsupported computation node type " + str(comp_def.node.type))
-    return Mgm2GpuComputation(comp_def)
+Mgm2GpuComputation, build_computation = computation_for(
+    "mgm2_gpu", "Mgm2GpuComputation", "Stands for an Mgm2Computation (pydcop/algorithms/mgm2.py:399).", computation_memory)

@@ -20,13 +20,10 @@ cost, evaluated on the device.  MGM's own sum never rises, so a replica's final 
 `best_every`.  The ranking takes no `infinity` (the module has no such parameter: every table entry, however large, is
 a cost).  With the defaults the module is the single fixed-draw run above.
 """
-from types import SimpleNamespace
-
 from pydcop.algorithms import AlgoParameterDef
 
 from pydcop_amd.algorithms import maxsum_gpu as _base
-from pydcop_amd.compile import compile_nodes
-from pydcop_amd.graph import Params
+from pydcop_amd.local_search import EngineAdapter, LocalSearchSession, computation_for
 
 GRAPH_TYPE = "constraints_hypergraph"
 HEADER_SIZE = 100
@@ -54,79 +51,26 @@ def communication_load(src, target: str) -> float:
     return UNIT_SIZE + HEADER_SIZE
 
 
-class _RoundEngine:
+class _RoundEngine(EngineAdapter):
     """MgmEngine behind the surface the session drives."""
+    FIRST_CYCLE = 1          # the reference's counter starts at 1 (mgm.py:407)
 
-    def __init__(self, graph, params, p=None):
+    def __init__(self, graph, params, p):
         from pydcop_amd.mgm import MgmEngine
-        self.graph = graph
-        draws = p["draws"] if p else "fixed"
-        self._many = bool(p) and int(p["restarts"]) > 1
-        if draws == "fixed":
-            if self._many:
+        many = int(p["restarts"]) > 1
+        if p["draws"] == "fixed":
+            if many:
                 raise ValueError("mgm_gpu: restarts needs draws:keyed (with the fixed draws every run is the same run)")
-            self._e = MgmEngine(graph, params)
+            engine = MgmEngine(graph, params)
         else:
-            self._e = MgmEngine(graph, params, draws=draws, seed=int(p["seed"]), replicas=int(p["restarts"]))
-
-    def run(self, n: int):
-        self._e.run(int(n))
-
-    def assignment(self):
-        if not self._many:
-            return self._e.assignment()
-        return self._e.assignment(self._e.best()["replica"])     # the best replica's values and held costs
-
-    @property
-    def cycle_count(self) -> int:
-        return self._e.cycle_count + 1          # the reference's counter starts at 1 (mgm.py:407)
-
-    def close(self):
-        self._e.close()
+            engine = MgmEngine(graph, params, draws=p["draws"], seed=int(p["seed"]), replicas=int(p["restarts"]))
+        super().__init__(graph, engine, many)
 
 
-class _MgmSession(_base._Session):
-    ALGO = "mgm_gpu"
-
-    def _compile_graph(self, p):
-        nodes = sorted((cd.node for cd in self.comp_defs.values()), key=lambda n: n.name)
-        constraints = {}
-        for n in nodes:
-            for c in n.constraints:
-                constraints.setdefault(c.name, c)
-        fac_nodes = [SimpleNamespace(name=name, factor=constraints[name]) for name in sorted(constraints)]
-        var_nodes = [SimpleNamespace(name=n.name, variable=n.variable,
-                                     links=[SimpleNamespace(factor_node=c.name) for c in n.constraints])
-                     for n in nodes]
-        return compile_nodes(var_nodes, fac_nodes, noise=0.0)
-
-    def _engine_params(self, algo, p):
-        return Params(mode=algo.mode, dtype=p["precision"])
-
-    def _make_engine(self, params, p):
-        return _RoundEngine(self.graph, params, p)
-
-    def _cycles_to_run(self, p) -> int:
-        stop = int(p["stop_cycle"])
-        if stop == 1:          # the reference finishes before the first exchange of values
-            self.done = True
-        return max(0, stop - 1)
-
-    def update_factor(self, name, old, fn):
-        raise ValueError("mgm_gpu: change_factor_function is a maxsum_gpu feature")
+class _MgmSession(LocalSearchSession):
+    ALGO, ENGINE = "mgm_gpu", _RoundEngine
 
 
 _base.SESSION_CLASSES["mgm_gpu"] = _MgmSession
-
-
-class MgmGpuComputation(_base.MaxSumGpuVariableComputation):
-    """Stands for an MgmComputation (pydcop/algorithms/mgm.py:213)."""
-
-    def footprint(self) -> float:
-        return computation_memory(self.computation_def.node)
-
-
-def build_computation(comp_def):
-    if comp_def.node.type != "VariableComputationNode":
-        raise ValueError("mgm_gpu: unsupported computation node type " + str(comp_def.node.type))
-    return MgmGpuComputation(comp_def)
+MgmGpuComputation, build_computation = computation_for(
+    "mgm_gpu", "MgmGpuComputation", "Stands for an MgmComputation (pydcop/algorithms/mgm.py:213).", computation_memory)

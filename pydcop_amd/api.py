@@ -10,7 +10,8 @@ to the engine -- O(E) graph build, flat arrays, T cycles, values back -- and rep
 with the reference's own `DCOP.solution_cost` (pydcop/dcop/dcop.py:308-367).
 pyDCOP must be importable; nothing of it is modified.
 """
-from typing import Dict, List, Optional, Tuple
+from importlib import import_module
+from typing import Callable, Dict, List, NamedTuple, Optional, Tuple
 
 import numpy as np
 
@@ -18,76 +19,159 @@ from .compile import assignment_to_values, compile_nodes
 from .graph import FlatGraph, Params
 
 
-ALGOS = ("maxsum", "amaxsum", "dsa", "mgm", "mgm2", "gdba", "dba")    # the iterative ones: `cycles` of them
-CLI_ALGOS = ALGOS + ("dpop",)                              # DPOP has no cycles: solve_dcop_dpop / solve_flat_dpop
+class _Algo(NamedTuple):
+    """What the front end knows of one algorithm.  `o` below: the keyword options of solve_dcop / solve_flat, by name."""
+    engine: str = ""                                   # "module:class" in this package, imported when it is used
+    engine_kw: Callable = lambda o: {}                 # o -> the keyword arguments of the engine's constructor
+    seeded: bool = True                                # `seed` keys its draws (Max-Sum's only seeds the noise)
+    noisy: bool = False                                # takes solve_dcop's `noise`
+    restarts: Callable = lambda o: False               # o -> may `restarts` differ from 1
+    best_every: bool = False                           # takes `best_every`
+    draws: bool = False                                # takes `draws` other than "fixed"
+    start: Callable = lambda eng, o: 0                 # before the run -> the period the engine traces by itself, or 0
+    best: Callable = lambda eng, o: None               # after it -> (idx, the result's extra keys) in place of the
+    #                                                    engine's assignment, or None
+    end: Callable = lambda eng: {}                     # -> the extra keys of every result
+    from_start: bool = False                           # run(n) counts from the start, not from where the engine is
 
 
-def _engine_for(graph: FlatGraph, params: Params, device: int, devices: int, lib_path, algo: str = "maxsum",
-                algo_kw: Optional[dict] = None):
-    """One engine on `device`, or -- Max-Sum with devices > 1 -- the graph partitioned over GPUs
+def _many(o):
+    return int(o["restarts"]) != 1
+
+
+def _dsa_kw(o):
+    return dict(variant=o["variant"], probability=o["probability"], p_mode=o["p_mode"], seed=o["seed"],
+                replicas=int(o["restarts"]))
+
+
+def _mgm_kw(o):
+    return dict(draws=o["draws"], seed=o["seed"], replicas=int(o["restarts"])) if o["draws"] != "fixed" else {}
+
+
+def _mgm2_kw(o):
+    kw = dict(threshold=o["threshold"], favor=o["favor"], seed=o["seed"])
+    return dict(kw, replicas=int(o["restarts"])) if _many(o) else kw          # (one run: mxs_mgm2_create, as ever)
+
+
+def _gdba_kw(o):
+    kw = dict(modifier=o["modifier"], violation=o["violation"], increase_mode=o["increase_mode"], seed=o["seed"])
+    if _many(o) or int(o["best_every"]) != 0:                                 # (else one run: mxs_gdba_create, as ever)
+        kw.update(seeds=[int(o["seed"]) + r for r in range(int(o["restarts"]))])
+    return kw
+
+
+def _dba_kw(o):
+    kw = dict(infinity=o["dba_infinity"], max_distance=o["max_distance"], seed=o["seed"])
+    # (one run: mxs_dba_create, as ever -- the two stop policies are the same thing there)
+    return dict(kw, replicas=int(o["restarts"]), stop=o["dba_stop"]) if _many(o) else kw
+
+
+def _track_records(eng, o):
+    """algo="dsa" or "gdba" with best_every: every replica keeps its best state"""
+    if int(o["best_every"]) > 0:
+        eng.track_best(int(o["best_every"]), o["infinity"])
+    return 0
+
+
+def _best_record(eng, o):
+    """algo="dsa" or "gdba" with restarts / best_every: (idx of the best replica -- its record when tracking, else its
+    final state --, the result's extra keys); the device cost only ranks.  Else None."""
+    if not _many(o) and int(o["best_every"]) == 0:
+        return None
+    if int(o["best_every"]) == 0:
+        eng.track_best(0, o["infinity"])         # (no records: ranks the final states)
+    best = eng.best()
+    costs, _ = eng.replica_costs(o["infinity"])
+    return best["idx"], {"replica": best["replica"], "best_cycle": best["cycle"],
+                         "replica_costs": [float(c) for c in costs]}
+
+
+def _best_final(eng, o):
+    """algo="mgm" (keyed draws) or "mgm2" with restarts: (idx of the best replica's final state, the result's extra
+    keys); the device cost only ranks.  Else None."""
+    if not _many(o):
+        return None
+    best = eng.best(o["infinity"])
+    costs, _ = eng.replica_costs(o["infinity"])
+    return best["idx"], {"replica": best["replica"], "replica_costs": [float(c) for c in costs]}
+
+
+def _dba_best(eng, o):
+    """algo="dba" with restarts: (idx of the best replica's state -- fewest violated constraints, then earliest stop,
+    ranked from the device's counts --, the result's extra keys).  Else None."""
+    if not _many(o):
+        return None
+    best = eng.best()
+    return best["idx"], {"replica": best["replica"], "replica_violations": [int(v) for v in eng.violations()],
+                         "stop_rounds": eng.stop_rounds}
+
+
+def _dba_end(eng):
+    """DBA stops by itself: the rounds it ran and whether a termination counter reached max_distance"""
+    return {"cycle": eng.cycle_count, "finished": eng.finished}
+
+
+def _maxsum_track(eng, o):
+    """algo="maxsum" with cost_every / best_every: switch the engine's device-side tracking on (one evaluation period
+    for both: the record and the curve come from the same evaluations).  -> the period, 0 when there is none."""
+    every = int(o["best_every"]) or int(o["cost_every"])
+    if every <= 0 or (o["devices"] and int(o["devices"]) > 1):      # (the sharded engine keeps the host loop of _run_and_trace)
+        return 0
+    eng.track_best(every, o["infinity"], trace=int(o["cycles"]) // every + 2)
+    return every
+
+
+# the one description of every algorithm of `solve_dcop` / `solve_flat`; ALGOS is its order
+_ALGOS = {
+    "maxsum": _Algo("engine:MaxSumEngine", seeded=False, noisy=True, best_every=True, start=_maxsum_track),
+    "amaxsum": _Algo("amaxsum:AMaxSumEngine", seeded=False, noisy=True, from_start=True),
+    "dsa": _Algo("dsa:DsaEngine", _dsa_kw, restarts=lambda o: True, best_every=True, start=_track_records,
+                 best=_best_record),
+    "mgm": _Algo("mgm:MgmEngine", _mgm_kw, restarts=lambda o: o["draws"] == "keyed", draws=True, best=_best_final),
+    "mgm2": _Algo("mgm2:Mgm2Engine", _mgm2_kw, restarts=lambda o: True, best=_best_final),
+    # (a GDBA run's final state is usually not its best: restarts without records would rank wandering states)
+    "gdba": _Algo("gdba:GdbaEngine", _gdba_kw, restarts=lambda o: int(o["best_every"]) >= 1, best_every=True,
+                  start=_track_records, best=_best_record),
+    "dba": _Algo("dba:DbaEngine", _dba_kw, restarts=lambda o: True, best=_dba_best, end=_dba_end),
+}
+_NO_ALGO = _Algo(seeded=False)             # (an unknown name takes no option; _engine_for refuses it)
+ALGOS = tuple(_ALGOS)                      # the iterative ones: `cycles` of them
+CLI_ALGOS = ALGOS + ("dpop",)              # DPOP has no cycles: solve_dcop_dpop / solve_flat_dpop
+
+# `-p name:value` of the command line: the options of solve_flat / solve_yaml by name (`infinity`: dba_infinity)
+CLI_PARAMS = {"damping": float, "stability": float, "noise": float, "seed": int,
+              "damping_nodes": str, "start_messages": str, "precision": str, "devices": int,
+              "variant": str, "probability": float, "p_mode": str, "threshold": float, "favor": str,
+              "modifier": str, "violation": str, "increase_mode": str, "infinity": int, "max_distance": int,
+              "restarts": int, "best_every": int, "draws": str, "dba_stop": str}
+
+
+def _engine_for(graph: FlatGraph, params: Params, o: dict):
+    """One engine on o["device"], or -- Max-Sum with devices > 1 -- the graph partitioned over GPUs
     0..devices-1 of this node (pydcop_amd.sharded.LocalShardedMaxSum: same surface, same result).
     Every engine has run / assignment / eval_cost / close."""
-    algo_kw = algo_kw or {}
-    if algo not in ALGOS:
+    algo, devices = o["algo"], o["devices"]
+    if algo not in _ALGOS:
         raise ValueError(f"algo must be one of {ALGOS}" + (
             " (DPOP runs no cycles: solve_dcop_dpop / solve_flat_dpop)" if algo == "dpop" else ""))
-    if algo != "maxsum":
-        if devices and int(devices) > 1:
-            raise ValueError("devices > 1: synchronous Max-Sum only")
-        if algo == "amaxsum":
-            from .amaxsum import AMaxSumEngine
-            return AMaxSumEngine(graph, params, device=device, lib_path=lib_path)
-        if algo == "dsa":
-            from .dsa import DsaEngine
-            return DsaEngine(graph, params, device=device, lib_path=lib_path, **algo_kw)
-        if algo == "mgm2":
-            from .mgm2 import Mgm2Engine
-            return Mgm2Engine(graph, params, device=device, lib_path=lib_path, **algo_kw)
-        if algo == "gdba":
-            from .gdba import GdbaEngine
-            return GdbaEngine(graph, params, device=device, lib_path=lib_path, **algo_kw)
-        if algo == "dba":
-            from .dba import DbaEngine
-            return DbaEngine(graph, params, device=device, lib_path=lib_path, **algo_kw)
-        from .mgm import MgmEngine
-        return MgmEngine(graph, params, device=device, lib_path=lib_path, **algo_kw)
-    from .engine import MaxSumEngine
     if devices and int(devices) > 1:
+        if algo != "maxsum":
+            raise ValueError("devices > 1: synchronous Max-Sum only")
         from .sharded import LocalShardedMaxSum
-        return LocalShardedMaxSum(graph, params, list(range(int(devices))), lib_path=lib_path)
-    return MaxSumEngine(graph, params, device=device, lib_path=lib_path)
+        return LocalShardedMaxSum(graph, params, list(range(int(devices))), lib_path=o["lib_path"])
+    module, name = _ALGOS[algo].engine.split(":")
+    engine = getattr(import_module("." + module, __package__), name)
+    return engine(graph, params, device=o["device"], lib_path=o["lib_path"], **_ALGOS[algo].engine_kw(o))
 
 
-def _algo_kw(algo, variant, probability, p_mode, seed, threshold, favor, modifier="A", violation="NZ",
-             increase_mode="E", dba_infinity=10000, max_distance=50, restarts=1, draws="fixed", best_every=0,
-             dba_stop="first"):
-    if algo == "dba":
-        kw = dict(infinity=dba_infinity, max_distance=max_distance, seed=seed)
-        # (one run: mxs_dba_create, as ever -- the two stop policies are the same thing there)
-        return dict(kw, replicas=int(restarts), stop=dba_stop) if int(restarts) != 1 else kw
-    if algo == "gdba":
-        kw = dict(modifier=modifier, violation=violation, increase_mode=increase_mode, seed=seed)
-        if int(restarts) != 1 or int(best_every) != 0:      # (else one run: mxs_gdba_create, as ever)
-            kw.update(seeds=[int(seed) + r for r in range(int(restarts))])
-        return kw
-    if algo == "dsa":
-        return dict(variant=variant, probability=probability, p_mode=p_mode, seed=seed, replicas=int(restarts))
-    if algo == "mgm2":
-        kw = dict(threshold=threshold, favor=favor, seed=seed)
-        return dict(kw, replicas=int(restarts)) if int(restarts) != 1 else kw     # (one run: mxs_mgm2_create, as ever)
-    if algo == "mgm" and draws != "fixed":
-        return dict(draws=draws, seed=seed, replicas=int(restarts))
-    return None
-
-
-def _run_and_trace(eng, algo: str, cycles: int, cost_every: int, infinity: float):
+def _run_and_trace(eng, from_start: bool, cycles: int, cost_every: int, infinity: float):
     """`cycles` cycles (amaxsum: generations of messages, its run() counts from the start), the
     cost evaluated on the device every `cost_every` of them."""
     curve: List[Tuple[int, float, int]] = []
     done = 0
     while done < cycles:
         n = min(cost_every, cycles - done) if cost_every > 0 else cycles - done
-        eng.run(done + n if algo == "amaxsum" else n)
+        eng.run(done + n if from_start else n)
         done += n
         if cost_every > 0:
             c, v = eng.eval_cost(infinity=infinity)
@@ -95,44 +179,51 @@ def _run_and_trace(eng, algo: str, cycles: int, cost_every: int, infinity: float
     return curve
 
 
-def _check_restarts(algo, restarts, best_every, draws="fixed", dba_stop="first"):
+def _check_restarts(o):
+    A, restarts, best_every, draws = _ALGOS.get(o["algo"], _NO_ALGO), o["restarts"], o["best_every"], o["draws"]
     if int(restarts) < 1 or int(best_every) < 0:
         raise ValueError("restarts must be at least 1 and best_every at least 0")
     if draws not in ("fixed", "keyed"):
         raise ValueError("draws must be \"fixed\" or \"keyed\"")
-    if draws != "fixed" and algo != "mgm":
+    if draws != "fixed" and not A.draws:
         raise ValueError("draws: algo=\"mgm\" only (the other local searches always key their draws on `seed`)")
-    # (a GDBA run's final state is usually not its best: restarts without records would rank wandering states)
-    if int(restarts) != 1 and not (algo in ("dsa", "mgm2", "dba") or (algo == "mgm" and draws == "keyed")
-                                   or (algo == "gdba" and int(best_every) >= 1)):
+    if int(restarts) != 1 and not A.restarts(o):
         raise ValueError("restarts: algo=\"dsa\", \"mgm2\" or \"dba\", algo=\"mgm\" with draws=\"keyed\", or algo=\"gdba\" "
                          "with best_every >= 1")
-    if dba_stop not in ("first", "each"):
+    if o["dba_stop"] not in ("first", "each"):
         raise ValueError("dba_stop must be \"first\" or \"each\"")
-    if algo not in ("dsa", "gdba", "maxsum") and int(best_every) != 0:
+    if not A.best_every and int(best_every) != 0:
         raise ValueError("best_every: algo=\"dsa\", \"gdba\" or \"maxsum\" only")
 
 
-def _check_maxsum_tracking(algo, cost_every, best_every, devices):
+def _check_maxsum_tracking(o):
     """the refusals of algo="maxsum" with best_every, before an engine exists"""
-    if algo != "maxsum" or int(best_every) <= 0:
+    if o["algo"] != "maxsum" or int(o["best_every"]) <= 0:
         return
-    if int(cost_every) > 0 and int(best_every) != int(cost_every):
+    if int(o["cost_every"]) > 0 and int(o["best_every"]) != int(o["cost_every"]):
         raise ValueError("maxsum: cost_every and best_every are one evaluation period: give one, or the same value")
-    if devices and int(devices) > 1:
+    if o["devices"] and int(o["devices"]) > 1:
         raise ValueError("best_every: maxsum on one device only (a shard's cost is partial)")
 
 
-def _check_until_quiescent(algo, until_quiescent, devices):
+def _check_until_quiescent(o):
     """the refusals of until_quiescent, before an engine exists"""
-    if int(until_quiescent) < 0:
+    if int(o["until_quiescent"]) < 0:
         raise ValueError("until_quiescent must be at least 0")
-    if int(until_quiescent) == 0:
+    if int(o["until_quiescent"]) == 0:
         return
-    if algo != "maxsum":
+    if o["algo"] != "maxsum":
         raise ValueError("until_quiescent: algo=\"maxsum\" only (amaxsum ends by itself, the others have no send rule)")
-    if devices and int(devices) > 1:
+    if o["devices"] and int(o["devices"]) > 1:
         raise ValueError("until_quiescent: maxsum on one device only (a shard sees its own edges only)")
+
+
+def _checked(**o):
+    """-> o, the options of one solve by name, after every refusal that needs no engine"""
+    _check_restarts(o)
+    _check_maxsum_tracking(o)
+    _check_until_quiescent(o)
+    return o
 
 
 def _run_until_quiescent(eng, cycles, until_quiescent):
@@ -142,18 +233,6 @@ def _run_until_quiescent(eng, cycles, until_quiescent):
     ran = eng.run_until_quiescent(int(cycles))["cycles_run"]
     q = eng.quiescence()
     return ran, {"quiescent": q["quiescent"], "quiescent_cycle": q["cycle"], "active_edges": q["active"]}
-
-
-def _maxsum_track(eng, algo, cycles, cost_every, best_every, infinity, devices=1):
-    """algo="maxsum" with cost_every / best_every: switch the engine's device-side tracking on (one evaluation period
-    for both: the record and the curve come from the same evaluations).  -> the period, 0 when there is none."""
-    every = int(best_every) or int(cost_every)
-    if algo != "maxsum" or every <= 0:
-        return 0
-    if devices and int(devices) > 1:
-        return 0                     # (the sharded engine keeps the host loop of _run_and_trace)
-    eng.track_best(every, infinity, trace=int(cycles) // every + 2)
-    return every
 
 
 def _maxsum_result(eng, cycles, cost_every, best_every, infinity):
@@ -168,42 +247,36 @@ def _maxsum_result(eng, cycles, cost_every, best_every, infinity):
     return curve, (best["idx"], {"best_cycle": best["cycle"]})
 
 
-def _dsa_best(eng, algo, restarts, best_every, infinity):
-    """algo="dsa" or "gdba" with restarts / best_every: (idx of the best replica -- its record when tracking, else its
-    final state --, the result's extra keys); the device cost only ranks.  Else None."""
-    if algo not in ("dsa", "gdba") or (int(restarts) == 1 and int(best_every) == 0):
-        return None
-    if int(best_every) == 0:
-        eng.track_best(0, infinity)         # (no records: ranks the final states)
-    best = eng.best()
-    costs, _ = eng.replica_costs(infinity)
-    return best["idx"], {"replica": best["replica"], "best_cycle": best["cycle"],
-                         "replica_costs": [float(c) for c in costs]}
+def _solve(graph: FlatGraph, params: Params, o: dict, device_cost: bool):
+    """One run of o["algo"] on the compiled instance, `o` as _checked returns it.  -> (idx of the selected assignment,
+    the cycles run, the cost curve, the result's extra keys, with `device_cost` the engine's (cost, violation) of idx)"""
+    A, cycles, cost_every, infinity = _ALGOS.get(o["algo"], _NO_ALGO), o["cycles"], o["cost_every"], o["infinity"]
+    with _engine_for(graph, params, o) as eng:
+        tracked = A.start(eng, o)
+        if int(o["until_quiescent"]) > 0:
+            cycles, ended = _run_until_quiescent(eng, cycles, o["until_quiescent"])
+            curve = []
+        else:
+            curve, ended = _run_and_trace(eng, A.from_start, cycles, 0 if tracked else cost_every, infinity), {}  # (tracked: ONE run call)
+        idx, _ = eng.assignment()
+        extra = {**A.end(eng), **ended}
+        best = A.best(eng, o)
+        if tracked:
+            curve, best = _maxsum_result(eng, cycles, cost_every, o["best_every"], infinity)
+        if best:
+            idx, more = best
+            extra.update(more)
+        measured = None
+        if device_cost:
+            measured = eng.eval_cost(idx, infinity=infinity) if best else eng.eval_cost(infinity=infinity)
+    return idx, cycles, curve, extra, measured
 
 
-def _mgm_best(eng, algo, restarts, infinity):
-    """algo="mgm" (keyed draws) or "mgm2" with restarts: (idx of the best replica's final state, the result's extra
-    keys); the device cost only ranks.  Else None."""
-    if algo not in ("mgm", "mgm2") or int(restarts) == 1:
-        return None
-    best = eng.best(infinity)
-    costs, _ = eng.replica_costs(infinity)
-    return best["idx"], {"replica": best["replica"], "replica_costs": [float(c) for c in costs]}
-
-
-def _dba_best(eng, algo, restarts):
-    """algo="dba" with restarts: (idx of the best replica's state -- fewest violated constraints, then earliest stop,
-    ranked from the device's counts --, the result's extra keys).  Else None."""
-    if algo != "dba" or int(restarts) == 1:
-        return None
-    best = eng.best()
-    return best["idx"], {"replica": best["replica"], "replica_violations": [int(v) for v in eng.violations()],
-                         "stop_rounds": eng.stop_rounds}
-
-
-def _dba_end(eng, algo):
-    """DBA stops by itself: the rounds it ran and whether a termination counter reached max_distance"""
-    return {"cycle": eng.cycle_count, "finished": eng.finished} if algo == "dba" else {}
+def _values(graph: FlatGraph, idx) -> Dict:
+    """the assignment by variable name and domain value; an instance without names: v0, v1, ... and the indices"""
+    if graph.var_names is not None and graph.domains is not None:
+        return assignment_to_values(graph, idx)
+    return {f"v{i}": int(x) for i, x in enumerate(idx)}
 
 
 def compile_dcop(dcop, noise: float = 0.0, seed: int = 0) -> FlatGraph:
@@ -283,32 +356,15 @@ def solve_dcop(dcop, cycles: int = 30, *, damping: float = 0.5, damping_nodes: s
     every run having completed it; "each": a run that stops is frozen, the others run on for `cycles` rounds or until
     all have stopped.  The result gains "replica", "replica_violations" and "stop_rounds" (0: that run has not
     stopped); "cycle" is the rounds the engine ran, "finished" whether it has ended.  `best_every` stays refused."""
-    _check_restarts(algo, restarts, best_every, draws, dba_stop)
-    _check_maxsum_tracking(algo, cost_every, best_every, devices)
-    _check_until_quiescent(algo, until_quiescent, devices)
-    graph = compile_dcop(dcop, noise=noise if algo in ("maxsum", "amaxsum") else 0.0, seed=seed)
+    o = _checked(algo=algo, cycles=cycles, infinity=infinity, device=device, devices=devices, lib_path=lib_path,
+                 cost_every=cost_every, until_quiescent=until_quiescent, variant=variant, probability=probability,
+                 p_mode=p_mode, seed=seed, threshold=threshold, favor=favor, modifier=modifier, violation=violation,
+                 increase_mode=increase_mode, dba_infinity=dba_infinity, max_distance=max_distance, restarts=restarts,
+                 best_every=best_every, draws=draws, dba_stop=dba_stop)
+    graph = compile_dcop(dcop, noise=noise if _ALGOS.get(algo, _NO_ALGO).noisy else 0.0, seed=seed)
     params = Params(mode=dcop.objective, damping=damping, damping_nodes=damping_nodes,
                     stability=stability, start_messages=start_messages, dtype=precision)
-    algo_kw = _algo_kw(algo, variant, probability, p_mode, seed, threshold, favor, modifier, violation, increase_mode,
-                       dba_infinity, max_distance, restarts, draws, best_every, dba_stop)
-    with _engine_for(graph, params, device, devices, lib_path, algo, algo_kw) as eng:
-        if algo in ("dsa", "gdba") and int(best_every) > 0:
-            eng.track_best(int(best_every), infinity)
-        tracked = _maxsum_track(eng, algo, cycles, cost_every, best_every, infinity, devices)
-        if int(until_quiescent) > 0:
-            cycles, ended = _run_until_quiescent(eng, cycles, until_quiescent)
-            curve = []
-        else:
-            curve, ended = _run_and_trace(eng, algo, cycles, 0 if tracked else cost_every, infinity), {}  # (tracked: ONE run call)
-        idx, _ = eng.assignment()
-        extra = {**_dba_end(eng, algo), **ended}
-        best = (_dsa_best(eng, algo, restarts, best_every, infinity) or _mgm_best(eng, algo, restarts, infinity)
-                or _dba_best(eng, algo, restarts))
-        if tracked:
-            curve, best = _maxsum_result(eng, cycles, cost_every, best_every, infinity)
-        if best:
-            idx, more = best
-            extra.update(more)
+    idx, cycles, curve, extra, _ = _solve(graph, params, o, device_cost=False)
     assignment = assignment_to_values(graph, idx)
     violation, cost = dcop.solution_cost(assignment, infinity)
     return {"assignment": assignment, "cost": cost, "violation": violation, "cycle": cycles,
@@ -329,36 +385,24 @@ def solve_flat(graph: FlatGraph, objective: str = "min", cycles: int = 30, *, da
     wanted, is already folded into `graph.var_cost` by whoever compiled the instance."""
     params = Params(mode=objective, damping=damping, damping_nodes=damping_nodes,
                     stability=stability, start_messages=start_messages, dtype=precision)
-    _check_restarts(algo, restarts, best_every, draws, dba_stop)
-    _check_maxsum_tracking(algo, cost_every, best_every, devices)
-    _check_until_quiescent(algo, until_quiescent, devices)
-    algo_kw = _algo_kw(algo, variant, probability, p_mode, seed, threshold, favor, modifier, violation, increase_mode,
-                       dba_infinity, max_distance, restarts, draws, best_every, dba_stop)
-    with _engine_for(graph, params, device, devices, lib_path, algo, algo_kw) as eng:
-        if algo in ("dsa", "gdba") and int(best_every) > 0:
-            eng.track_best(int(best_every), infinity)
-        tracked = _maxsum_track(eng, algo, cycles, cost_every, best_every, infinity, devices)
-        if int(until_quiescent) > 0:
-            cycles, ended = _run_until_quiescent(eng, cycles, until_quiescent)
-            curve = []
-        else:
-            curve, ended = _run_and_trace(eng, algo, cycles, 0 if tracked else cost_every, infinity), {}  # (tracked: ONE run call)
-        idx, _ = eng.assignment()
-        extra = {**_dba_end(eng, algo), **ended}
-        best = (_dsa_best(eng, algo, restarts, best_every, infinity) or _mgm_best(eng, algo, restarts, infinity)
-                or _dba_best(eng, algo, restarts))
-        if tracked:
-            curve, best = _maxsum_result(eng, cycles, cost_every, best_every, infinity)
-        if best:
-            idx, more = best
-            extra.update(more)
-        cost, violation = eng.eval_cost(idx, infinity=infinity) if best else eng.eval_cost(infinity=infinity)
-    if graph.var_names is not None and graph.domains is not None:
-        assignment = assignment_to_values(graph, idx)
-    else:
-        assignment = {f"v{i}": int(x) for i, x in enumerate(idx)}
-    return {"assignment": assignment, "cost": cost, "violation": violation, "cycle": cycles,
+    o = _checked(algo=algo, cycles=cycles, infinity=infinity, device=device, devices=devices, lib_path=lib_path,
+                 cost_every=cost_every, until_quiescent=until_quiescent, variant=variant, probability=probability,
+                 p_mode=p_mode, seed=seed, threshold=threshold, favor=favor, modifier=modifier, violation=violation,
+                 increase_mode=increase_mode, dba_infinity=dba_infinity, max_distance=max_distance, restarts=restarts,
+                 best_every=best_every, draws=draws, dba_stop=dba_stop)
+    idx, cycles, curve, extra, (cost, violation) = _solve(graph, params, o, device_cost=True)
+    return {"assignment": _values(graph, idx), "cost": cost, "violation": violation, "cycle": cycles,
             "cost_curve": curve, **extra}
+
+
+def _solve_dpop(graph: FlatGraph, params: Params, tree, max_bytes, device, lib_path, infinity=None):
+    """UTIL and VALUE on `tree` (None: `build_pseudotree` over the instance's order).  -> (idx, with an `infinity` the
+    engine's (cost, violation) of it)"""
+    from .dpop import DpopEngine
+    with DpopEngine(graph, params, tree=tree, max_bytes=max_bytes, device=device, lib_path=lib_path) as eng:
+        eng.solve()
+        idx, _ = eng.assignment()
+        return idx, (None if infinity is None else eng.eval_cost(infinity=infinity))
 
 
 def solve_dcop_dpop(dcop, *, precision: str = "f64", infinity: float = 10000, device: int = 0, max_bytes: int = 0,
@@ -370,12 +414,8 @@ def solve_dcop_dpop(dcop, *, precision: str = "f64", infinity: float = 10000, de
     plugin.install()
     from pydcop.computations_graph import pseudotree_fast
     from pydcop_amd.algorithms.dpop_gpu import compile_pseudotree
-    from .dpop import DpopEngine
     graph, tree = compile_pseudotree(pseudotree_fast.build_computation_graph(dcop).nodes)
-    with DpopEngine(graph, Params(mode=dcop.objective, dtype=precision), tree=tree, max_bytes=max_bytes,
-                    device=device, lib_path=lib_path) as eng:
-        eng.solve()
-        idx, _ = eng.assignment()
+    idx, _ = _solve_dpop(graph, Params(mode=dcop.objective, dtype=precision), tree, max_bytes, device, lib_path)
     assignment = assignment_to_values(graph, idx)
     violation, cost = dcop.solution_cost(assignment, infinity)
     return {"assignment": assignment, "cost": cost, "violation": violation, "cycle": 0, "cost_curve": []}
@@ -385,17 +425,9 @@ def solve_flat_dpop(graph: FlatGraph, objective: str = "min", *, precision: str 
                     device: int = 0, max_bytes: int = 0, lib_path: Optional[str] = None) -> Dict:
     """`solve_dcop_dpop` for a compiled instance: the tree is `build_pseudotree` over the instance's variable
     and factor order; cost and violations are evaluated by the engine."""
-    from .dpop import DpopEngine
-    with DpopEngine(graph, Params(mode=objective, dtype=precision), max_bytes=max_bytes, device=device,
-                    lib_path=lib_path) as eng:
-        eng.solve()
-        idx, _ = eng.assignment()
-        cost, violation = eng.eval_cost(infinity=infinity)
-    if graph.var_names is not None and graph.domains is not None:
-        assignment = assignment_to_values(graph, idx)
-    else:
-        assignment = {f"v{i}": int(x) for i, x in enumerate(idx)}
-    return {"assignment": assignment, "cost": cost, "violation": violation, "cycle": 0, "cost_curve": []}
+    idx, (cost, violation) = _solve_dpop(graph, Params(mode=objective, dtype=precision), None, max_bytes, device, lib_path,
+                                         infinity)
+    return {"assignment": _values(graph, idx), "cost": cost, "violation": violation, "cycle": 0, "cost_curve": []}
 
 
 def solve_yaml(paths, cycles: int = 30, **kw) -> Dict:
@@ -431,17 +463,12 @@ def main(argv=None):
     ap.add_argument("--export", metavar="OUT.npz", default=None,
                     help="compile the YAML DCOP (noise folded in) and write it as an instance file")
     args = ap.parse_args(argv)
-    kinds = {"damping": float, "stability": float, "noise": float, "seed": int,
-             "damping_nodes": str, "start_messages": str, "precision": str, "devices": int,
-             "variant": str, "probability": float, "p_mode": str, "threshold": float, "favor": str,
-             "modifier": str, "violation": str, "increase_mode": str, "infinity": int, "max_distance": int,
-             "restarts": int, "best_every": int, "draws": str, "dba_stop": str}
     kw = {}
     for item in args.algo_params:
         name, _, value = item.partition(":")
-        if name not in kinds:
-            raise SystemExit(f"Error: unknown parameter {name!r} (one of {sorted(kinds)})")
-        kw[name] = kinds[name](value)
+        if name not in CLI_PARAMS:
+            raise SystemExit(f"Error: unknown parameter {name!r} (one of {sorted(CLI_PARAMS)})")
+        kw[name] = CLI_PARAMS[name](value)
     if "infinity" in kw:          # (`--infinity` is the one of DCOP.solution_cost; this one is dba.py:266)
         kw["dba_infinity"] = kw.pop("infinity")
     t0 = time.perf_counter()
@@ -458,12 +485,12 @@ def main(argv=None):
     if len(args.dcop_files) == 1 and args.dcop_files[0].endswith(".npz"):
         graph, header = FlatGraph.load(args.dcop_files[0])
         kw.pop("noise", None)  # folded into the instance when it was compiled
-        if args.algo not in ("dsa", "mgm", "mgm2", "gdba", "dba"):
-            kw.pop("seed", None)
         if args.algo == "dpop":
             res = solve_flat_dpop(graph, header.get("objective", "min"), infinity=args.infinity,
                                   precision=kw.get("precision", "f64"))
         else:
+            if not _ALGOS[args.algo].seeded:       # (Max-Sum's seed is the noise's)
+                kw.pop("seed", None)
             res = solve_flat(graph, header.get("objective", "min"), args.cycles, infinity=args.infinity,
                              cost_every=args.cost_every, algo=args.algo, until_quiescent=args.until_quiescent, **kw)
     elif args.algo == "dpop":
